@@ -5,8 +5,14 @@ regime (config C3: 65,536 independent rounds per GPU per step, one wavefront per
 round).  A "step" is one launch of ``batched_round_kernel`` over the resident
 65,536-round batch: every round is a complete ``Oracle(...).consensus()``.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the
+line.  ``--full`` adds every secondary entry to the line (the CPU baselines, the vector-only
+kernel time, C5, C4, the medium rounds, the fp64 covariance, the drop-in C1 / C2), each of which
+takes runs of its own; ``--no-cpu-baseline``, ``--c5-steps`` and ``--no-c4`` narrow a full run.
+``--dump-outputs DIR`` writes what the last timed step returned (see :func:`dump_outputs`).
 
 ``--gpus N > 1`` with no launcher (WORLD_SIZE unset) starts the second form itself as a
 child job before touching the GPU; WORLD_SIZE set and different from ``--gpus`` is an
@@ -529,12 +535,50 @@ def rank_devices(world, dev):
     return [dict(rank=r, **v) for r, v in enumerate(allv)]
 
 
+DUMP_ROUNDS = 1536  # rounds of the last timed step that --dump-outputs writes
+DUMP_SEED = 7       # of the sample of rounds (fixed: two builds write the same rounds)
+
+
+def dump_outputs(out, path, B):
+    """``--dump-outputs``: the result dict of the last timed step, as a caller of
+    ``consensus_batched`` receives it, one ``<name>.npy`` per output in float64 (the int32 outputs
+    widened).  The whole step's outputs are 1.4 GB, so a fixed, seeded sample of DUMP_ROUNDS
+    rounds is written, in ascending round order; ``round_index.npy`` holds their indices.
+
+    Every file holds finite numbers only, so two dumps compare entry by entry.  NaN is part of the
+    result (``original`` keeps the missing reports as NaN, a round whose certainty sum is masked
+    has NaN certainty, reward and author bonus, as in the reference), so each floating-point
+    output comes with ``<name>_nonfinite.npy`` (float32: 0 finite, 1 NaN, 2 +inf, 3 -inf) and has
+    0.0 at the entries marked there.  About 48 MB at 50 x 20."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=min(B, DUMP_ROUNDS), replace=False))
+    np.save(os.path.join(path, "round_index.npy"), idx.astype(np.float64))
+    for name, x in out.items():
+        if name.startswith("_"):  # the inputs kept alive, not outputs
+            continue
+        sel = torch.as_tensor(idx, device=x.device)
+        a = x.index_select(0, sel).to(torch.float64).cpu().numpy()
+        if x.dtype.is_floating_point:
+            code = np.where(np.isnan(a), 1, np.where(a == np.inf, 2, np.where(a == -np.inf, 3, 0))).astype(np.float32)
+            a[code != 0] = 0.0
+            np.save(os.path.join(path, name + "_nonfinite.npy"), code)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=ROUNDS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (a seeded sample of rounds)")
+    ap.add_argument("--full", action="store_true",
+                    help="add the secondary entries: CPU baselines, vector-only kernel time, C5, C4, medium "
+                         "rounds, fp64 covariance, drop-in C1 / C2 (narrowed by the three options below)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--c5-steps", type=int, default=3, help="timed 1M x 4k consensus runs (0 = skip)")
     ap.add_argument("--no-c4", dest="c4", action="store_false", help="skip the 100k x 1k (C4) entry")
@@ -543,6 +587,11 @@ def main():
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr, flush=True)
         sys.exit(2)
+    if args.steps < 1:
+        print("bench.py: --steps must be >= 1", file=sys.stderr, flush=True)
+        sys.exit(2)
+    if not args.full:  # a plain run: the headline alone
+        args.no_cpu_baseline, args.c5_steps, args.c4 = True, 0, False
     if env_world is None and args.gpus > 1:
         # no launcher: start one rank per GPU ourselves, before anything touches the GPU
         sys.exit(launch_ranks(args.gpus))
@@ -588,14 +637,15 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(dev)
-    # the vector outputs only (no N x E matrices), for reference
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(torch.cuda.current_stream(dev))
-    for _ in range(5):
-        step(False)
-    e1.record(torch.cuda.current_stream(dev))
-    torch.cuda.synchronize(dev)
-    vec_ms = e0.elapsed_time(e1) / 5
+    vec_ms = None
+    if args.full:  # the vector outputs only (no N x E matrices), for reference
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(torch.cuda.current_stream(dev))
+        for _ in range(5):
+            step(False)
+        e1.record(torch.cuda.current_stream(dev))
+        torch.cuda.synchronize(dev)
+        vec_ms = e0.elapsed_time(e1) / 5
 
     def barrier():
         if world > 1:
@@ -661,10 +711,13 @@ def main():
                                   "note": "VALU issue time of the launch's instructions (SQ_INSTS_VALU, "
                                           "profiles/pmc_traffic.json) at 4 cycles each on 1024 SIMDs at "
                                           "2.4 GHz, over the kernel time"}},
-            "vectors_only_kernel_ms": vec_ms,
             "launcher": os.environ.get(LAUNCHER_ENV, "external (WORLD_SIZE=%d)" % world if world > 1 else "none"),
             "devices": devices,
         }
+        if vec_ms is not None:
+            line["vectors_only_kernel_ms"] = vec_ms
+        if args.dump_outputs:
+            dump_outputs(out, args.dump_outputs, B)
         if not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline()
     del Rd, out

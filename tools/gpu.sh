@@ -7,7 +7,7 @@
 #   tests        every -m gpu test (the driver's round-end tier)
 #   tests:EXPR   the -m gpu tests selected by -k EXPR
 #   smoke        __graft_entry__.smoke()
-#   bench        the default bench line (C3 headline + C5 + C4 + medium) -> bench.json
+#   bench        the full bench line (bench.py --full: C3 headline + C5 + C4 + medium) -> bench.json
 #   profile      rocprofv3 kernel trace of a short bench + FETCH / WRITE / VALU PMC passes, summarised
 #                into pmc_traffic.json (tools/pmc_summary.py) and kernel_stats.csv
 #   pmc_c5       PMC passes over one C5 consensus, per kernel (k_gemm_i8 split into grid / mixed)
@@ -50,11 +50,11 @@ for STEP in "$@"; do
       timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo "smoke rc=$?"; tail -20 $O/smoke.log; exit 12; }
       tail -1 $O/smoke.log ;;
     bench)
-      timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || { echo "bench rc=$?"; tail -20 $O/bench.err; exit 13; }
+      timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench rc=$?"; tail -20 $O/bench.err; exit 13; }
       python3 -c "import json; d=json.load(open('$O/bench.json')); print('C3', round(d['value']/1e6,2), 'M/s kernel', round(d['roofline']['kernel_ms'],3), 'ms frac', round(d['roofline']['frac'],3), '| C5', round(d['c5']['latency_ms'],1), d['c5'].get('latency_ms_all'), '| C4', round(d['c4']['latency_ms'],2), '| medium', round(d['medium']['rounds_per_s']/1e6,2), 'M/s')"
       c5_line $O/bench.json bench ;;
     profile)
-      ARGS="--steps 5 --warmup 1 --no-cpu-baseline --c5-steps 1 --no-c4"
+      ARGS="--full --steps 5 --warmup 1 --no-cpu-baseline --c5-steps 1 --no-c4"
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o kt -- python3 bench.py $ARGS > $O/kt.log 2>&1 || { echo "kernel-trace rc=$?"; tail -5 $O/kt.log; exit 14; }
       for C in FETCH_SIZE WRITE_SIZE SQ_INSTS_VALU; do
         timeout -k 10 300 rocprofv3 --pmc $C --output-format csv -d $O/$C -o pmc -- python3 bench.py $ARGS > $O/$C.log 2>&1 || { echo "pmc $C rc=$?"; tail -5 $O/$C.log; exit 15; }
@@ -67,7 +67,7 @@ for STEP in "$@"; do
       cp "$KS" $O/kernel_stats.csv
       echo profile ok ;;
     pmc_c5)
-      ARGS="--steps 1 --warmup 0 --rounds 4096 --no-cpu-baseline --no-c4 --c5-steps 1"
+      ARGS="--full --steps 1 --warmup 0 --rounds 4096 --no-cpu-baseline --no-c4 --c5-steps 1"
       i=0
       for P in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU" \
                "FETCH_SIZE" "WRITE_SIZE TCC_HIT_sum TCC_MISS_sum" \
@@ -91,11 +91,11 @@ for STEP in "$@"; do
       timeout -k 10 240 python -u -m pytest tests/test_dist_gpu.py -x -v --timeout 200 --timeout-method thread > $O/pytest_dist.log 2>&1 || { echo "pytest dist rc=$?"; tail -40 $O/pytest_dist.log; exit 20; }
       tail -1 $O/pytest_dist.log
       PCX_DIST_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-          --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 1 --c5-steps 2 \
+          --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 5 --warmup 1 --c5-steps 2 \
           --no-cpu-baseline > $O/bench2.json 2> $O/bench2.err || { echo "bench2 rc=$?"; tail -30 $O/bench2.err; exit 21; }
       c5_line $O/bench2.json "N=2 gloo" ;;
     selfdist)  # bench.py --gpus 2 with NO launcher: it must start the 2 ranks itself (gloo: both on cuda:0)
-      PCX_DIST_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --steps 5 --warmup 1 --c5-steps 2 \
+      PCX_DIST_BACKEND=gloo timeout -k 10 400 python bench.py --full --gpus 2 --steps 5 --warmup 1 --c5-steps 2 \
           --no-cpu-baseline > $O/bench_self2.json 2> $O/bench_self2.err || { echo "selfdist rc=$?"; tail -30 $O/bench_self2.err; exit 30; }
       python3 -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); c=d['c5']; print('self-launched: n_gpus', d['n_gpus'], 'launcher', d['launcher'], 'devices', [x['device'] for x in d['devices']], '| C5 n_gpus', c['n_gpus'], 'comm', c['comm'], 'ctx_world', c['ctx_world'], 'rccl_world', c['rccl_world'])" $O/bench_self2.json
       c5_line $O/bench_self2.json "N=2 self gloo" ;;
@@ -108,13 +108,13 @@ for STEP in "$@"; do
     ab_med=*)  # the medium-round (100 x 50) line of several libpcx builds, alternating twice
       IFS=, read -ra LIBS <<< "${STEP#ab_med=}"
       for i in 1 2; do for L in "${LIBS[@]}"; do
-        PCX_LIB=$L timeout -k 10 200 python bench.py --no-cpu-baseline --c5-steps 0 --steps 5 > $O/abm.json 2> $O/abm.err || { echo "ab_med rc=$? ($L)"; tail -3 $O/abm.err; exit 33; }
+        PCX_LIB=$L timeout -k 10 200 python bench.py --full --no-cpu-baseline --c5-steps 0 --steps 5 > $O/abm.json 2> $O/abm.err || { echo "ab_med rc=$? ($L)"; tail -3 $O/abm.err; exit 33; }
         python3 -c "import json,sys; d=json.load(open(sys.argv[1])); m=d['medium']; print('%-28s medium %.3f ms  %.3fM rounds/s' % (sys.argv[2], m['ms'], m['rounds_per_s']/1e6))" $O/abm.json "$L"
       done; done ;;
     ab_c5=*)
       IFS=, read -ra LIBS <<< "${STEP#ab_c5=}"
       for i in 1 2; do for L in "${LIBS[@]}"; do
-        PCX_LIB=$L timeout -k 10 300 python bench.py --no-cpu-baseline --no-c4 --c5-steps 3 --steps 3 > $O/ab.json 2> $O/ab.err || { echo "ab rc=$? ($L)"; tail -3 $O/ab.err; exit 23; }
+        PCX_LIB=$L timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-c4 --c5-steps 3 --steps 3 > $O/ab.json 2> $O/ab.err || { echo "ab rc=$? ($L)"; tail -3 $O/ab.err; exit 23; }
         c5_line $O/ab.json "$L"
       done; done ;;
     kt_c5=*)
@@ -122,7 +122,7 @@ for STEP in "$@"; do
       i=0
       for L in "${LIBS[@]}"; do
         i=$((i+1))
-        PCX_LIB=$L timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/kt$i -o kt -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --c5-steps 1 --no-c4 > $O/kt$i.log 2>&1 || { echo "kt_c5 rc=$? ($L)"; tail -5 $O/kt$i.log; exit 30; }
+        PCX_LIB=$L timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/kt$i -o kt -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --c5-steps 1 --no-c4 > $O/kt$i.log 2>&1 || { echo "kt_c5 rc=$? ($L)"; tail -5 $O/kt$i.log; exit 30; }
         echo "== $L"
         python3 tools/kt_top.py $(find $O/kt$i -name "kt_kernel_trace.csv" | head -1) -1 ${KT_TOP:-14} ${KT_LAUNCHES:-k_sel_hist} || exit 31
       done ;;
