@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define PCX_ABI_VERSION 8
+#define PCX_ABI_VERSION 9
 
 enum pcx_status {
     PCX_OK = 0,
@@ -155,6 +155,76 @@ typedef struct {
 } pcx_batch_result;
 
 int pcx_consensus_batched_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_result* out);
+
+/* ------------------------------------------------------------------------ */
+/* Monte Carlo simulator (ABI >= 9): the Simulator.jl-style driver of the       */
+/* batched regime (README.rst:52-56) on the device.  It draws random rounds     */
+/* with a counter-based generator (Philox4x32-10; DESIGN.md "Simulator" is the  */
+/* specification), runs pcx_consensus_batched_f64 on them, scores each round    */
+/* against the truth it drew and carries smooth_rep into the next timestep's    */
+/* reputation.  Replaces nothing in the reference (it has no generator).        */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+    int64_t  n_rounds;            /* B                                           */
+    int64_t  n_reporters;         /* N                                           */
+    int64_t  n_events;            /* E                                           */
+    int64_t  n_timesteps;         /* T in [1, 2^24)                              */
+    uint64_t seed;                /* Philox key (low word, high word)            */
+    double  liar_frac;            /* P(a reporter lies), the same person in every timestep */
+    double  collude_frac;         /* P(a liar reports the event's shared lie, not a random value) */
+    double  distort;              /* P(an honest report is a random value)       */
+    double  na_frac;              /* P(a report is missing: NaN)                 */
+    double  scaled_frac;          /* P(an event is scaled)                       */
+    double  scaled_tol;           /* a scaled outcome is correct within scaled_tol * (hi - lo) of the truth */
+    /* the consensus parameters of pcx_batch (k-means and cokurtosis are refused:
+       they need host-drawn code books / caller scores) */
+    double  catch_tolerance;
+    double  alpha;
+    int32_t algorithm;
+    int32_t max_components;
+    double  variance_threshold;
+    double  hierarchy_threshold;
+    double  cluster_threshold;
+    const double* reputation0;    /* [B][N] reputation of timestep 0 (device), or NULL = uniform */
+} pcx_sim;
+
+/* One timestep's rounds.  Any pointer may be NULL (not written) except where a function
+ * says otherwise. */
+typedef struct {
+    double*  reports;             /* [B][N][E], NaN = missing                    */
+    uint8_t* scaled;              /* [B][E]                                      */
+    double*  lo;                  /* [B][E] (binary events: 1)                   */
+    double*  hi;                  /* [B][E] (binary events: 2)                   */
+    double*  truth;               /* [B][E] the outcome an honest reporter sees  */
+    uint8_t* liar;                /* [B][N] bit 0: liar, bit 1: a liar that colludes */
+} pcx_sim_rounds;
+
+#define PCX_SIM_NMETRICS 6        /* correct, liar_rep_before, liar_rep_after, liars_bonus, beats, n_liars */
+
+typedef struct {
+    double* metrics;              /* [T][B][PCX_SIM_NMETRICS]                    */
+    double* summary;              /* [T][PCX_SIM_NMETRICS] mean over the rounds  */
+    double* reputation;           /* [B][N] smooth_rep of the last timestep      */
+    pcx_sim_rounds   last;        /* the last timestep's rounds                  */
+    pcx_batch_result last_out;    /* the last timestep's consensus outputs       */
+} pcx_sim_result;
+
+/* Philox4x32-10 on the host (the generator's only source of randomness). */
+void pcx_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+/* The rounds of one timestep on the CPU, HOST pointers, no context: the same inline code
+ * as the device kernel (csrc/pcx_sim.h), bit for bit. */
+int pcx_sim_generate_host(const pcx_sim* sim, int timestep, pcx_sim_rounds* out);
+/* The same on the device; asynchronous on the context's stream. */
+int pcx_sim_generate_f64(pcx_ctx* ctx, const pcx_sim* sim, int timestep, pcx_sim_rounds* out);
+/* Score B rounds: metrics [B][PCX_SIM_NMETRICS] (required), summary [PCX_SIM_NMETRICS] or
+ * NULL.  rounds->scaled, lo, hi, truth and liar are required.  Asynchronous. */
+int pcx_sim_metrics_f64(pcx_ctx* ctx, const pcx_sim* sim, const pcx_sim_rounds* rounds, const double* old_rep,
+                        const double* smooth_rep, const double* outcomes_final, double* metrics, double* summary);
+/* T timesteps of generate -> pcx_consensus_batched_f64 -> metrics -> reputation carry.  The
+ * work buffers live in the context (kept between calls, freed by pcx_release_workspace).
+ * Asynchronous, without a host synchronisation in the loop, when the shape takes an
+ * asynchronous batched regime (N <= 256 and E <= 64). */
+int pcx_simulate_f64(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* result);
 
 /* ------------------------------------------------------------------------ */
 /* Single-matrix regime: one N x E report matrix, optionally sharded by        */

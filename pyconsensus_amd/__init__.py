@@ -5,8 +5,12 @@
 
 Batched Monte Carlo rounds: :func:`consensus_batched`.  Single huge matrices,
 row-sharded over GPUs: :func:`pyconsensus_amd.pipeline.consensus_matrix`.
+Monte Carlo trajectories generated, run and scored on the device: :func:`simulate`
+(with :func:`generate`, :func:`generate_host` and the metric names :data:`METRICS`; the
+module's other names: ``from pyconsensus_amd.simulate import ...``).
 """
 __version__ = "0.1.0"
 
 from .batched import consensus_batched  # noqa: E402,F401
 from .oracle import Oracle  # noqa: E402,F401
+from .simulate import METRICS, generate, generate_host, simulate  # noqa: E402,F401

@@ -1,7 +1,7 @@
 """ctypes mirror of include/pcx.h (structs and constants).  Keep in sync with the header."""
 import ctypes as C
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 OK, EINVAL, EHIP, ENOMEM, ECOMM = 0, -1, -2, -3, -4
 BRANCH_SET1, BRANCH_SET2, BRANCH_TIE_SET1, BRANCH_TIE_SET2, BRANCH_NONE = 1, 2, 3, 4, 5
@@ -66,6 +66,36 @@ class BatchResult(C.Structure):
 
 def out_shape(kind, B, N, E):
     return {"N": (B, N), "E": (B, E), "1": (B,), "NE": (B, N, E)}[kind]
+
+
+# ---------------------------------------------------------------- Monte Carlo simulator
+SIM_NMETRICS = 6                 # PCX_SIM_NMETRICS
+
+
+class Sim(C.Structure):
+    _fields_ = [
+        ("n_rounds", C.c_int64), ("n_reporters", C.c_int64), ("n_events", C.c_int64),
+        ("n_timesteps", C.c_int64), ("seed", C.c_uint64),
+        ("liar_frac", C.c_double), ("collude_frac", C.c_double), ("distort", C.c_double),
+        ("na_frac", C.c_double), ("scaled_frac", C.c_double), ("scaled_tol", C.c_double),
+        ("catch_tolerance", C.c_double), ("alpha", C.c_double),
+        ("algorithm", C.c_int32), ("max_components", C.c_int32),
+        ("variance_threshold", C.c_double), ("hierarchy_threshold", C.c_double),
+        ("cluster_threshold", C.c_double), ("reputation0", C.c_void_p)]
+
+
+# name, per-round shape kind, dtype
+SIM_ROUNDS = [("reports", "NE", "f8"), ("scaled", "E", "u1"), ("lo", "E", "f8"), ("hi", "E", "f8"),
+              ("truth", "E", "f8"), ("liar", "N", "u1")]
+
+
+class SimRounds(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name, _, _ in SIM_ROUNDS]
+
+
+class SimResult(C.Structure):
+    _fields_ = [("metrics", C.c_void_p), ("summary", C.c_void_p), ("reputation", C.c_void_p),
+                ("last", SimRounds), ("last_out", BatchResult)]
 
 
 # ---------------------------------------------------------------- single-matrix regime

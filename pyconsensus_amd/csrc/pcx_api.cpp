@@ -180,6 +180,7 @@ int pcx_release_workspace(pcx_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     pcx::workspace_free(ctx);
     pcx::io_bufs_free(ctx);
+    pcx::sim_free(ctx);
     return PCX_OK;
 }
 
@@ -205,6 +206,11 @@ void ctx_host_free(pcx_ctx* c) {
     c->side_stream = nullptr;
     io_bufs_free(c);
 }
+void sim_free(pcx_ctx* c) {
+    if (c->sim_buf) (void)hipFree(c->sim_buf);
+    c->sim_buf = nullptr;
+    c->sim_bytes = 0;
+}
 void io_bufs_free(pcx_ctx* c) {
     for (auto& b : c->io_bufs)
         if (b.first) (void)hipFree(b.first);
@@ -221,6 +227,7 @@ void pcx_destroy(pcx_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     pcx::ctx_host_free(ctx);
     pcx::workspace_free(ctx);
+    pcx::sim_free(ctx);
     delete ctx->comm;
     delete ctx;
 }
@@ -607,6 +614,204 @@ int pcx_selftest_chunked_copy(int64_t bytes, int64_t chunk, int slots, int threa
 int pcx_test_inject_enomem(pcx_ctx* ctx, int worker) {
     if (!ctx) return fail(PCX_EINVAL, "pcx_test_inject_enomem: null context");
     ctx->test_enomem_worker = worker;
+    return PCX_OK;
+}
+
+// ---------------------------------------------------------------- Monte Carlo simulator
+namespace {
+// the argument checks every simulator entry shares (no device needed); 0 = ok
+int sim_check(const pcx_sim* s, const char* who) {
+    const std::string w = std::string(who) + ": ";
+    if (s->n_rounds < 0 || s->n_rounds > 0x7fffffff) return fail(PCX_EINVAL, w + "n_rounds must be in [0, 2^31)");
+    if (s->n_reporters < 1 || s->n_reporters > 0x7fffffff)
+        return fail(PCX_EINVAL, w + "n_reporters must be in [1, 2^31)");
+    if (s->n_events < 1 || s->n_events > 65536) return fail(PCX_EINVAL, w + "n_events must be in [1, 65536]");
+    if (s->n_timesteps < 1 || s->n_timesteps >= (1 << 24))
+        return fail(PCX_EINVAL, w + "n_timesteps must be in [1, 2^24)");
+    const struct {
+        const char* name;
+        double p;
+    } probs[] = {{"liar_frac", s->liar_frac}, {"collude_frac", s->collude_frac}, {"distort", s->distort},
+                 {"na_frac", s->na_frac},     {"scaled_frac", s->scaled_frac}};
+    for (const auto& q : probs)
+        if (!(q.p >= 0.0 && q.p <= 1.0))  // false for NaN too
+            return fail(PCX_EINVAL, w + q.name + " must be a probability in [0, 1]");
+    if (!(s->scaled_tol >= 0.0) || !std::isfinite(s->scaled_tol))
+        return fail(PCX_EINVAL, w + "scaled_tol must be finite and >= 0");
+    if (s->algorithm < PCX_ALG_PCA || s->algorithm > PCX_ALG_CLUSTERFECK)
+        return fail(PCX_EINVAL, w + "algorithm must be an enum pcx_algorithm value (0..7)");
+    if (s->algorithm == PCX_ALG_KMEANS)
+        return fail(PCX_EINVAL, w + "k-means is not simulated (its code books are drawn on the host)");
+    if (s->algorithm == PCX_ALG_COKURTOSIS)
+        return fail(PCX_EINVAL, w + "cokurtosis is not simulated (it needs the caller's scores)");
+    // what pcx_consensus_batched_f64 would refuse, before anything is generated
+    if (s->algorithm == PCX_ALG_HIERARCHICAL && std::isnan(s->hierarchy_threshold))
+        return fail(PCX_EINVAL, w + "hierarchy_threshold is NaN");
+    if (s->algorithm == PCX_ALG_BIG_FIVE && (s->max_components < 1 || s->max_components > s->n_events))
+        return fail(PCX_EINVAL, w + "big-five needs 1 <= max_components <= n_events");
+    if (s->algorithm == PCX_ALG_FIXED_VARIANCE && !std::isfinite(s->variance_threshold))
+        return fail(PCX_EINVAL, w + "variance_threshold must be finite");
+    if (!std::isfinite(s->catch_tolerance) || !std::isfinite(s->alpha))
+        return fail(PCX_EINVAL, w + "catch_tolerance/alpha must be finite");
+    return PCX_OK;
+}
+
+int sim_check_timestep(int t, const char* who) {
+    if (t < 0 || t >= (1 << 24)) return fail(PCX_EINVAL, std::string(who) + ": timestep must be in [0, 2^24)");
+    return PCX_OK;
+}
+
+uint64_t sim_threshold(double p) { return (uint64_t)std::floor(p * 4294967296.0); }
+
+pcx::sim::Gen sim_gen(const pcx_sim* s) {
+    pcx::sim::Gen g;
+    g.key0 = (uint32_t)s->seed;
+    g.key1 = (uint32_t)(s->seed >> 32);
+    g.thr_liar = sim_threshold(s->liar_frac);
+    g.thr_collude = sim_threshold(s->collude_frac);
+    g.thr_distort = sim_threshold(s->distort);
+    g.thr_na = sim_threshold(s->na_frac);
+    g.thr_scaled = sim_threshold(s->scaled_frac);
+    return g;
+}
+
+int sim_reserve(pcx_ctx* ctx, size_t need) {
+    if (ctx->sim_bytes >= need) return PCX_OK;
+    pcx::sim_free(ctx);
+    const hipError_t e = hipMalloc(&ctx->sim_buf, need);
+    if (e != hipSuccess) {
+        ctx->sim_buf = nullptr;
+        return fail(e == hipErrorOutOfMemory ? PCX_ENOMEM : PCX_EHIP,
+                    std::string("pcx_simulate_f64: hipMalloc(work buffers): ") + hipGetErrorString(e));
+    }
+    ctx->sim_bytes = need;
+    return PCX_OK;
+}
+}  // namespace
+
+void pcx_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+    const pcx::sim::U4 r = pcx::sim::philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1]);
+    out[0] = r.w0;
+    out[1] = r.w1;
+    out[2] = r.w2;
+    out[3] = r.w3;
+}
+
+int pcx_sim_generate_host(const pcx_sim* sim, int timestep, pcx_sim_rounds* out) {
+    if (!sim || !out) return fail(PCX_EINVAL, "pcx_sim_generate_host: null argument");
+    if (const int rc = sim_check(sim, "pcx_sim_generate_host")) return rc;
+    if (const int rc = sim_check_timestep(timestep, "pcx_sim_generate_host")) return rc;
+    pcx::sim_generate_host(sim_gen(sim), sim->n_rounds, sim->n_reporters, sim->n_events, (uint32_t)timestep, *out);
+    return PCX_OK;
+}
+
+int pcx_sim_generate_f64(pcx_ctx* ctx, const pcx_sim* sim, int timestep, pcx_sim_rounds* out) {
+    if (!ctx || !sim || !out) return fail(PCX_EINVAL, "pcx_sim_generate_f64: null argument");
+    if (const int rc = sim_check(sim, "pcx_sim_generate_f64")) return rc;
+    if (const int rc = sim_check_timestep(timestep, "pcx_sim_generate_f64")) return rc;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    e = pcx::launch_sim_generate(sim_gen(sim), sim->n_rounds, sim->n_reporters, sim->n_events, (uint32_t)timestep,
+                                 *out, ctx->stream);
+    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_sim_generate launch");
+}
+
+int pcx_sim_metrics_f64(pcx_ctx* ctx, const pcx_sim* sim, const pcx_sim_rounds* rounds, const double* old_rep,
+                        const double* smooth_rep, const double* outcomes_final, double* metrics, double* summary) {
+    if (!ctx || !sim || !rounds || !old_rep || !smooth_rep || !outcomes_final || !metrics)
+        return fail(PCX_EINVAL, "pcx_sim_metrics_f64: null argument");
+    if (!rounds->scaled || !rounds->lo || !rounds->hi || !rounds->truth || !rounds->liar)
+        return fail(PCX_EINVAL, "pcx_sim_metrics_f64: rounds needs scaled, lo, hi, truth and liar");
+    if (const int rc = sim_check(sim, "pcx_sim_metrics_f64")) return rc;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    e = pcx::launch_sim_metrics(sim->n_rounds, sim->n_reporters, sim->n_events, sim->scaled_tol, *rounds, old_rep,
+                                smooth_rep, outcomes_final, metrics, ctx->stream);
+    if (e == hipSuccess && summary) e = pcx::launch_sim_summary(metrics, sim->n_rounds, summary, ctx->stream);
+    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_sim_metrics / k_sim_summary launch");
+}
+
+int pcx_simulate_f64(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* res) {
+    if (!ctx || !sim || !res) return fail(PCX_EINVAL, "pcx_simulate_f64: null argument");
+    if (const int rc = sim_check(sim, "pcx_simulate_f64")) return rc;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    const int64_t B = sim->n_rounds, N = sim->n_reporters, E = sim->n_events, T = sim->n_timesteps;
+    const size_t bn = (size_t)B * N, be = (size_t)B * E;
+    // work buffers, doubles first: reports, lo, hi, truth, outcomes_final, old_rep, two smooth_rep
+    // (ping-pong: a timestep reads one as its reputation and writes the other), metrics; then
+    // the bytes scaled and liar
+    const size_t n_f64 = bn * E + 4 * be + 3 * bn + (size_t)B * PCX_SIM_NMETRICS;
+    if (const int rc = sim_reserve(ctx, std::max<size_t>(n_f64 * sizeof(double) + be + bn, 16))) return rc;
+    double* p = (double*)ctx->sim_buf;
+    auto take = [&p](size_t n) {
+        double* q = p;
+        p += n;
+        return q;
+    };
+    pcx_sim_rounds work;
+    work.reports = take(bn * E);
+    work.lo = take(be);
+    work.hi = take(be);
+    work.truth = take(be);
+    double* w_outcomes = take(be);
+    double* w_old = take(bn);
+    double* w_smooth[2] = {take(bn), take(bn)};
+    double* w_metrics = take((size_t)B * PCX_SIM_NMETRICS);
+    work.scaled = (uint8_t*)p;
+    work.liar = work.scaled + be;
+    const pcx::sim::Gen g = sim_gen(sim);
+    const double* rep = sim->reputation0;
+    for (int64_t t = 0; t < T; t++) {
+        const bool last = t == T - 1;
+        pcx_sim_rounds r = work;
+        pcx_batch_result o{};
+        if (last) {  // the caller's buffers where given
+            const pcx_sim_rounds& u = res->last;
+            if (u.reports) r.reports = u.reports;
+            if (u.scaled) r.scaled = u.scaled;
+            if (u.lo) r.lo = u.lo;
+            if (u.hi) r.hi = u.hi;
+            if (u.truth) r.truth = u.truth;
+            if (u.liar) r.liar = u.liar;
+            o = res->last_out;
+        }
+        if (!o.old_rep) o.old_rep = w_old;
+        if (!o.smooth_rep) o.smooth_rep = w_smooth[t & 1];
+        if (!o.outcomes_final) o.outcomes_final = w_outcomes;
+        e = pcx::launch_sim_generate(g, B, N, E, (uint32_t)t, r, ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "k_sim_generate launch");
+        pcx_batch in{};
+        in.n_rounds = B;
+        in.n_reporters = N;
+        in.n_events = E;
+        in.reports = r.reports;
+        in.reputation = rep;
+        in.scaled = r.scaled;
+        in.lo = r.lo;
+        in.hi = r.hi;
+        in.catch_tolerance = sim->catch_tolerance;
+        in.alpha = sim->alpha;
+        in.algorithm = sim->algorithm;
+        in.max_components = sim->max_components;
+        in.variance_threshold = sim->variance_threshold;
+        in.hierarchy_threshold = sim->hierarchy_threshold;
+        in.cluster_threshold = sim->cluster_threshold;
+        if (const int rc = pcx_consensus_batched_f64(ctx, &in, &o)) return rc;
+        if (res->metrics || res->summary) {
+            double* m = res->metrics ? res->metrics + (size_t)t * B * PCX_SIM_NMETRICS : w_metrics;
+            e = pcx::launch_sim_metrics(B, N, E, sim->scaled_tol, r, o.old_rep, o.smooth_rep, o.outcomes_final, m,
+                                        ctx->stream);
+            if (e == hipSuccess && res->summary)
+                e = pcx::launch_sim_summary(m, B, res->summary + (size_t)t * PCX_SIM_NMETRICS, ctx->stream);
+            if (e != hipSuccess) return hip_fail(e, "k_sim_metrics / k_sim_summary launch");
+        }
+        rep = o.smooth_rep;  // the next timestep's reputation
+    }
+    if (res->reputation && bn) {
+        e = hipMemcpyAsync(res->reputation, rep, bn * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "pcx_simulate_f64: reputation copy");
+    }
     return PCX_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/pcx.h"
+#include "pcx_sim.h"
 
 // Kernel-side view of one single-matrix consensus on one rank: problem, scratch and
 // outputs as device pointers (built by pcx_runner.cpp, passed by value to every
@@ -214,6 +215,17 @@ bool medium_fits(const BatchArgs& a);
 int64_t medium_chunk(const BatchArgs& a, size_t scratch_bytes);
 hipError_t launch_medium(const BatchArgs& a, int64_t b0, int64_t nb, double* Fscr, double* Cscr, hipStream_t st);
 
+// ---------------------------------------------------------------- Monte Carlo simulator (pcx_sim.hip)
+// one timestep's rounds on the device / on the host (the same inline generator, pcx_sim.h)
+hipError_t launch_sim_generate(const sim::Gen& g, int64_t B, int64_t N, int64_t E, uint32_t t,
+                               const pcx_sim_rounds& out, hipStream_t st);
+void sim_generate_host(const sim::Gen& g, int64_t B, int64_t N, int64_t E, uint32_t t, const pcx_sim_rounds& out);
+// metrics [B][PCX_SIM_NMETRICS] of B scored rounds; summary [PCX_SIM_NMETRICS], their means in a fixed order
+hipError_t launch_sim_metrics(int64_t B, int64_t N, int64_t E, double scaled_tol, const pcx_sim_rounds& r,
+                              const double* old_rep, const double* smooth_rep, const double* outcomes_final,
+                              double* metrics, hipStream_t st);
+hipError_t launch_sim_summary(const double* metrics, int64_t B, double* summary, hipStream_t st);
+
 // ---------------------------------------------------------------- single-matrix stages
 // Internal stage ids (pcx_stage_name); the runner (pcx_runner.cpp) sequences them.
 enum mat_stage_id {
@@ -368,6 +380,9 @@ struct pcx_ctx {
     size_t pin_small_bytes = 0;
     // the host path's copy of `filled` back, run beside the device work that follows k_wcd
     hipStream_t side_stream = nullptr;
+    // the simulator's work buffers (pcx_simulate_f64): one allocation, kept between calls
+    void* sim_buf = nullptr;
+    size_t sim_bytes = 0;
 };
 
 namespace pcx {
@@ -386,4 +401,5 @@ void rounds_free(pcx_ctx* c);
 // events, the workgroup-per-round scratch): pcx_destroy and rounds_free (the pool's worker contexts)
 void ctx_host_free(pcx_ctx* c);
 void io_bufs_free(pcx_ctx* c);  // the host path's cached device copies (pcx_ctx.io_bufs)
+void sim_free(pcx_ctx* c);      // the simulator's work buffers (pcx_ctx.sim_buf)
 }  // namespace pcx
