@@ -447,6 +447,10 @@ int pcx_selftest_chunked_copy(int64_t bytes, int64_t chunk, int slots, int threa
  * makes its worker `worker` report PCX_ENOMEM for its first round without running it (the
  * hand-back path); -1 clears it.  Consumed by that call.  For the tests only. */
 int pcx_test_inject_enomem(pcx_ctx* ctx, int worker);
+/* Dynamic LDS bytes one round of pcx_consensus_batched_f64 asks for (n_reporters <= 64, n_events
+ * <= 32, algorithm as in pcx_batch): what bounds the rounds resident per CU (LDS is handed out in
+ * 1,280-byte units of the CU's 160 KiB).  No device needed.  For the tests and the tools. */
+int64_t pcx_batched_lds_bytes(int n_reporters, int n_events, int algorithm);
 
 #ifdef __cplusplus
 }

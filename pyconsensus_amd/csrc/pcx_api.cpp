@@ -611,6 +611,10 @@ int pcx_selftest_rounds_sched(int workers, int64_t rounds, int enomem_worker, in
 int pcx_selftest_chunked_copy(int64_t bytes, int64_t chunk, int slots, int threads, int64_t fail_chunk) {
     return pcx::selftest_chunked_copy(bytes, chunk, slots, threads, fail_chunk);
 }
+int64_t pcx_batched_lds_bytes(int n_reporters, int n_events, int algorithm) {
+    if (n_reporters < 1 || n_reporters > 64 || n_events < 1 || n_events > 32) return -1;
+    return (int64_t)pcx::batched_lds_bytes(n_reporters, n_events, algorithm);
+}
 int pcx_test_inject_enomem(pcx_ctx* ctx, int worker) {
     if (!ctx) return fail(PCX_EINVAL, "pcx_test_inject_enomem: null context");
     ctx->test_enomem_worker = worker;

@@ -622,11 +622,11 @@ __device__ PCX_OUTLINE double rank_avg(const double* v, int E) {
 
 struct Smem {
     double* F;      // [N][ES] rescaled, then filled reports
-    double* C;      // [E][ES] covariance (phase aliases: see carve)
-    double* M;      // [max(E*ES, MED_SCR)] power-iteration / Jacobi working matrix
+    double* C;      // [E][ES] covariance (phase aliases: see carve; packed: runs on into M's region)
+    double* M;      // [max(E*ES, MED_SCR)] power-iteration / Jacobi working matrix (packed: scratch only)
     double* rep;    // [N] (aliases C: dead once the covariance has its tokens)
-    double* n1;     // [N] normalize(set1) (aliases C)
-    double* n2;     // [N] normalize(set2) (aliases C)
+    double* n1;     // [N] normalize(set1) (aliases C; packed: M)
+    double* n2;     // [N] normalize(set2) (aliases C; packed: M)
     double* smooth; // [N] (aliases C)
     double* mu;     // [E] full layout only (the clusterings' mean; the rest read lane registers)
     double* tot;    // [E] present-reputation totals of the interpolation medians (aliases M)
@@ -652,6 +652,15 @@ struct Smem {
 //   the power-iteration vector, the loading and the weighted mean are lane registers, read
 //      by other lanes through readlane / ds_bpermute (no LDS); the full layout keeps mu
 //      (the clusterings read it) and x | ld as the Jacobi rotations' cos | sin.
+// The packed layouts (PCA, plain and caller-scored rounds) square the iterated matrix in registers
+// (square_scaled_reg) and write its triangle over C for the matrix-vector steps, C's operands
+// waiting in registers meanwhile, so no region is sized for a matrix of its own:
+//   "C" holds guess | rep before the covariance and smooth | adj | old after the scores;
+//   "M" holds the median scratch and the totals in both median phases, n1 | n2 | nv1 | nv2
+//      between the scores and the reputation update, then the certainty's hit masks;
+//   C, the packed covariance, is live from the covariance to the scores only, when all of
+//      those are dead, and spans both regions ("M" directly follows "C").
+// 50 x 20: F 1,000 + "C" 90 + "M" 159 + miss 20 = 1,269 doubles = 10,152 bytes, eight units.
 // The integer tokens are recomputed from rep where the covariance needs them.  Per-row
 // vectors hold N entries, per-event vectors E (rounded up to even).  LDS is allocated in
 // 1,280-byte units (160 KiB / 128; measured with PCX_BATCHED_LDS_PAD: a 50 x 20 round of
@@ -668,18 +677,28 @@ __host__ __device__ inline int smem_evs(int E) { return (E + 1) & ~1; }
 // general V), or -- every other algorithm -- packed lower triangles (both are symmetric:
 // the squared M bitwise too).
 __host__ __device__ inline int smem_mat(int E, int ES, bool pk) { return pk ? E * (E + 1) / 2 : E * ES; }
+// Packed layouts: the squared matrix has no LDS of its own (it shares C's), so one triangle needs
+// LDS, from the covariance to the scores, when every vector of both regions is dead: C spans the
+// "C" and "M" regions, which are contiguous (carve), and each region is sized for its vectors alone.
 __host__ __device__ inline int smem_c_size(int N, int E, int ES, bool pk) {
+    if (pk) return smem_rows(N) + 2 * smem_evs(E);  // smooth | adj | old (before: guess | rep)
     const int need = 3 * smem_rows(N) + 2 * smem_evs(E);
     return smem_mat(E, ES, pk) > need ? smem_mat(E, ES, pk) : need;
 }
-__host__ __device__ inline int smem_m_size(int E, int ES, int NR, bool pk) {
+__host__ __device__ inline int smem_m_size(int N, int E, int ES, int NR, bool pk) {
     const int scr = med_scr(NR) + smem_evs(E);  // the median scratch and the totals beside it
+    if (pk) {
+        const int vec = 2 * smem_rows(N) + 2 * smem_evs(E);  // n1 | n2 | nv1 | nv2
+        const int rest = smem_mat(E, ES, pk) - smem_c_size(N, E, ES, pk);  // C's tail past the "C" region
+        const int need = scr > vec ? scr : vec;
+        return need > rest ? need : rest;
+    }
     const int need = scr > 2 * smem_evs(E) ? scr : 2 * smem_evs(E);
     return smem_mat(E, ES, pk) > need ? smem_mat(E, ES, pk) : need;
 }
 
 __host__ __device__ inline size_t smem_doubles(int N, int E, int ES, int NR, bool pk) {
-    return (size_t)smem_f_size(N, E, ES) + smem_c_size(N, E, ES, pk) + smem_m_size(E, ES, NR, pk) +
+    return (size_t)smem_f_size(N, E, ES) + smem_c_size(N, E, ES, pk) + smem_m_size(N, E, ES, NR, pk) +
            (pk ? 1 : 4) * (size_t)smem_evs(E);
 }
 
@@ -698,7 +717,7 @@ __device__ Smem carve(double* base, int N, int E, int ES, int NR, bool pk) {
     double* p = base;
     s.F = p; p += smem_f_size(N, E, ES);
     s.C = p; p += smem_c_size(N, E, ES, pk);
-    s.M = p; p += smem_m_size(E, ES, NR, pk);
+    s.M = p; p += smem_m_size(N, E, ES, NR, pk);
     s.miss = reinterpret_cast<uint64_t*>(p); p += ne;
     s.mu = s.x = s.ld = nullptr;
     if (!pk) {
@@ -710,13 +729,23 @@ __device__ Smem carve(double* base, int N, int E, int ES, int NR, bool pk) {
     s.tot = s.M + med_scr(NR);
     s.rep = s.C + ne;  // (beside guess, C[0, E))
     s.guess = s.C;
-    s.n1 = s.C;
-    s.n2 = s.C + nr;
-    s.smooth = s.C + 2 * nr;
-    s.adj = s.C + 3 * nr;
-    s.old = s.C + 3 * nr + ne;
-    s.nv1 = s.M;
-    s.nv2 = s.M + ne;
+    if (pk) {
+        s.smooth = s.C;
+        s.adj = s.C + nr;
+        s.old = s.C + nr + ne;
+        s.n1 = s.M;
+        s.n2 = s.M + nr;
+        s.nv1 = s.M + 2 * nr;
+        s.nv2 = s.M + 2 * nr + ne;
+    } else {
+        s.n1 = s.C;
+        s.n2 = s.C + nr;
+        s.smooth = s.C + 2 * nr;
+        s.adj = s.C + 3 * nr;
+        s.old = s.C + 3 * nr + ne;
+        s.nv1 = s.M;
+        s.nv2 = s.M + ne;
+    }
     return s;
 }
 
@@ -788,6 +817,153 @@ __device__ PCX_OUTLINE void square_scaled(double* M, int ES, int E) {
         if (j1 < E && k1 < E && (!PK || k1 <= j1)) M[sym_at<PK>(j1, k1, ES)] = scaled(t11[r]);
     }
     wsync();
+}
+
+// ---- packed layouts: the iterated matrix in registers ----------------------------------------
+// Lane (ml = l & 15, kq = l >> 4) holds the MFMA operands of k-step s (columns 4s .. 4s + 3) of a
+// symmetric E x E matrix M, zero outside it:
+//   a0[s] = M[ml][4s + kq]        (row tile 0)
+//   a1[s] = M[16 + ml][4s + kq]   (row tile 1, E > 16 only)
+// NS = k-steps held: ceil(E / 4) of a compiled shape, 8 otherwise.
+template <int NS>
+struct SymOps {
+    double a0[NS], a1[NS];
+};
+// (Build parameters for A/B runs; the defaults are what measured fastest)
+#ifndef PCX_BATCHED_T01_MOVES  // 1: E <= 20 takes t01 from t10 by cross-lane moves; 0: always a fourth MFMA chain
+#define PCX_BATCHED_T01_MOVES 1
+#endif
+#ifndef PCX_BATCHED_MV_MFMA  // 1: the matrix-vector steps by MFMA from the operand registers; 0: matvec_unit
+#define PCX_BATCHED_MV_MFMA 0  // on the packed triangle written over C (C's operands wait in registers)
+#endif
+
+__device__ __forceinline__ double bpermute_d(int src_lane, double v) {  // lane l <- lane src_lane's v
+    const uint64_t u = (uint64_t)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane * 4, (int)(uint32_t)u);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane * 4, (int)(uint32_t)(u >> 32));
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
+// the operands of the packed lower triangle C in LDS (the reads square_scaled<true> makes)
+template <int NS>
+__device__ __forceinline__ void load_sym_ops(const double* C, int E, SymOps<NS>& m) {
+    const int l = lane_id(), ml = l & 15, kq = l >> 4;
+    const bool two = E > 16;
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+        m.a0[s] = 0.0;
+        m.a1[s] = 0.0;
+        if (4 * s < E) {
+            const int mm = 4 * s + kq;
+            const bool ok = mm < E;
+            if (ok && ml < E) m.a0[s] = C[sym_at<true>(ml, mm, 0)];
+            if (two && ok && 16 + ml < E) m.a1[s] = C[sym_at<true>(16 + ml, mm, 0)];
+        }
+    }
+}
+
+// the inverse: the operands' lower triangle back into the packed triangle C in LDS
+template <int NS>
+__device__ __forceinline__ void store_sym_ops(double* C, int E, const SymOps<NS>& m) {
+    const int l = lane_id(), ml = l & 15, kq = l >> 4;
+    const bool two = E > 16;
+    wsync();
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+        if (4 * s < E) {
+            const int mm = 4 * s + kq;
+            if (mm <= ml && ml < E) C[sym_at<true>(ml, mm, 0)] = m.a0[s];
+            if (two && mm <= 16 + ml && 16 + ml < E) C[sym_at<true>(16 + ml, mm, 0)] = m.a1[s];
+        }
+    }
+    wsync();
+}
+
+// square_scaled with M in registers, before and after.  The squared matrix is symmetric bit for
+// bit (entry (j, k) and (k, j) are the same products in the same m order), and accumulator r of
+// a tile is entry (kq + 4r, ml): read as entry (ml, 4r + kq) it IS the next squaring's operand of
+// k-step r (t00), of k-step 4 + r in row tile 0 (t10) and in row tile 1 (t11).  Row tile 1's
+// operands of the k-steps below 16 are the upper tile t01, a fourth MFMA chain.  No LDS store,
+// reload, index arithmetic or wave barrier; the maximum and the scaling as in square_scaled.
+template <int NS>
+__device__ PCX_OUTLINE void square_scaled_reg(SymOps<NS>& m, int E) {
+    const int l = lane_id(), ml = l & 15, kq = l >> 4;
+    const bool two = E > 16;
+    // E <= 20: t01's live entries (kq + 4r, 16 + ml), ml < 4, are t10's accumulator 0 of lane
+    // (4r + kq, kq' = ml) -- four cross-lane moves instead of a fourth MFMA chain
+    const bool t01_moves = PCX_BATCHED_T01_MOVES && E <= 20;
+    d4v t00 = {0, 0, 0, 0}, t01 = {0, 0, 0, 0}, t10 = {0, 0, 0, 0}, t11 = {0, 0, 0, 0};
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+        if (4 * s < E) {
+            t00 = mfma_f64(m.a0[s], m.a0[s], t00);
+            if (two) {
+                if (!t01_moves) t01 = mfma_f64(m.a0[s], m.a1[s], t01);
+                t10 = mfma_f64(m.a1[s], m.a0[s], t10);
+                t11 = mfma_f64(m.a1[s], m.a1[s], t11);
+            }
+        }
+    }
+    double mx = 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {  // (t01 holds t10's values)
+        const int j0 = kq + 4 * r, j1 = 16 + kq + 4 * r, k0 = ml, k1 = 16 + ml;
+        if (j0 < E && k0 < E) mx = fmax(mx, fabs(t00[r]));
+        if (j1 < E && k0 < E) mx = fmax(mx, fabs(t10[r]));
+        if (j1 < E && k1 < E) mx = fmax(mx, fabs(t11[r]));
+    }
+    mx = wave_max(mx);
+    const bool pow2 = mx >= DBL_MIN_ && __builtin_isfinite(mx);
+    const double sc = pow2 ? ldexp(1.0, -ilogb(mx)) : 1.0;
+    auto keep = [&](auto scaled) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int j0 = kq + 4 * r, j1 = 16 + kq + 4 * r, k0 = ml, k1 = 16 + ml;
+            if (r < NS) m.a0[r] = (j0 < E && k0 < E) ? scaled(t00[r]) : 0.0;
+            if (two) {
+                if (r < NS) {
+                    if (t01_moves) {
+                        const double s10 = (16 + kq < E && k0 < E) ? scaled(t10[0]) : 0.0;
+                        const double v = bpermute_d(16 * (ml & 3) + 4 * r + kq, s10);
+                        m.a1[r] = (j0 < E && k1 < E) ? v : 0.0;
+                    } else {
+                        m.a1[r] = (j0 < E && k1 < E) ? scaled(t01[r]) : 0.0;
+                    }
+                }
+                if (4 + r < NS) {
+                    m.a0[4 + r] = (j1 < E && k0 < E) ? scaled(t10[r]) : 0.0;
+                    m.a1[4 + r] = (j1 < E && k1 < E) ? scaled(t11[r]) : 0.0;
+                }
+            }
+        }
+    };
+    if (pow2)  // (wave-uniform: the division stays off the common path)
+        keep([&](double t) { return t * sc; });
+    else
+        keep([&](double t) { return mx > 0.0 ? t / mx : t; });
+}
+
+// matvec_unit on those operands.  With A[i][k] = x_k (every row) and B[k][j] = M[j][k] the MFMA
+// leaves y_j = fma(x_k, M[j][k], acc) over k ascending from +0 -- matvec_unit's chain, the
+// product commuted -- in every accumulator of lane (ml = j, any kq): lane l < 16 reads its y
+// from row tile 0, lane 16 + ml (kq = 1) from row tile 1.  x_{4s + kq} comes by ds_bpermute.
+template <int NS>
+__device__ PCX_OUTLINE double matvec_unit_reg(const SymOps<NS>& m, double xv, int E) {
+    const int l = lane_id(), kq = l >> 4;
+    const bool two = E > 16;
+    d4v y0 = {0, 0, 0, 0}, y1 = {0, 0, 0, 0};
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+        if (4 * s < E) {
+            const double xk = bpermute_d(4 * s + kq, xv);  // (xv is 0.0 on lanes >= E)
+            y0 = mfma_f64(xk, m.a0[s], y0);
+            if (two) y1 = mfma_f64(xk, m.a1[s], y1);
+        }
+    }
+    const double acc = l < 16 ? y0[0] : y1[0];
+    const double y = l < E ? acc : 0.0;
+    const double nrm = sqrt(tree_sum(l < E ? y * y : 0.0));
+    return l < E ? y / nrm : 0.0;
 }
 
 // ---- "big-five" / "fixed-variance" eigenpairs: SPEC jacobi_eig of
@@ -1545,14 +1721,15 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
             auto put = [&](int j, int k, double acc) {  // j >= k
                 const double c = acc / denom;
                 S.C[sym_at<PK>(j, k, ES)] = c;
-                S.M[sym_at<PK>(j, k, ES)] = c;
                 if (!PK) {
+                    S.M[sym_at<PK>(j, k, ES)] = c;
                     S.C[k * ES + j] = c;
                     S.M[k * ES + j] = c;
                 }
                 nonzero |= c != 0.0;
                 finite &= __builtin_isfinite(c) != 0;
             };
+            if constexpr (PK) wsync();  // packed C lies over rep, which the loop above read
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const int j0 = kq + 4 * r, j1 = 16 + kq + 4 * r, k0 = ml, k1 = 16 + ml;
@@ -1581,11 +1758,38 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
             double x0 = col ? S.C[sym_at<PK>(l, kd, ES)] : 0.0;
             const double n0 = sqrt(tree_sum(x0 * x0));
             xv = col ? x0 / n0 : 0.0;
+            // packed: M starts as C's operands and is squared in registers (the covariance
+            // accumulators cannot seed it: (d_j tok) d_k and (d_k tok) d_j round differently, and C
+            // is its lower triangle mirrored); the matrix-vector steps read M's triangle from C's
+            // place in LDS, and C's operands (creg) are written back for the polish steps
+            constexpr int NS = !PK ? 1 : ET > 0 ? (ET + 3) / 4 : EMAX / 4;
+            constexpr bool MVM = PK && PCX_BATCHED_MV_MFMA, MVL = PK && !PCX_BATCHED_MV_MFMA;
+            SymOps<NS> mreg, creg;
+            if constexpr (PK) load_sym_ops<NS>(S.C, E, mreg);
+            if constexpr (MVL) creg = mreg;
+            auto square = [&](bool in_loop) {
+                if constexpr (MVM) {
+                    square_scaled_reg<NS>(mreg, E);
+                } else if constexpr (MVL) {  // (M's triangle lies over C in LDS between the squarings)
+                    if (in_loop) load_sym_ops<NS>(S.C, E, mreg);
+                    square_scaled_reg<NS>(mreg, E);
+                    if (in_loop) store_sym_ops<NS>(S.C, E, mreg);
+                } else {
+                    square_scaled<PK>(S.M, ES, E);
+                }
+            };
+            auto step = [&](const double* Mlds, double x) {
+                if constexpr (MVM)
+                    return matvec_unit_reg<NS>(mreg, x, E);
+                else
+                    return matvec_unit<PK>(Mlds, ES, x, E);
+            };
             int sqn = 0;
-            for (; sqn < PI_PRESQUARE; sqn++) square_scaled<PK>(S.M, ES, E);
+            for (; sqn < PI_PRESQUARE; sqn++) square(false);
+            if constexpr (MVL) store_sym_ops<NS>(S.C, E, mreg);
             int it = 0, since = 0;
             for (;;) {
-                const double y = matvec_unit<PK>(S.M, ES, xv, E);
+                const double y = step(PK ? S.C : S.M, xv);
                 const double d = wave_max(col ? fabs(y - xv) : 0.0);
                 xv = y;
                 it++;
@@ -1596,12 +1800,15 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
                     break;
                 }
                 if (since >= PI_SQUARE_EVERY && sqn < PI_MAX_SQUARINGS) {
-                    square_scaled<PK>(S.M, ES, E);
+                    square(true);
                     sqn++;
                     since = 0;
                 }
             }
-            for (int p = 0; p < PI_POLISH; p++) xv = matvec_unit<PK>(S.C, ES, xv, E);
+            // the polish steps run on C itself
+            if constexpr (MVM) load_sym_ops<NS>(S.C, E, mreg);
+            if constexpr (MVL) store_sym_ops<NS>(S.C, E, creg);
+            for (int p = 0; p < PI_POLISH; p++) xv = step(S.C, xv);
             // SPEC sign: first nonzero component negative; a unit vector e_k is +e_k
             const uint64_t nzm = ballot(col && xv != 0.0);
             if (nzm) {
@@ -1765,6 +1972,16 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
 
     STAMP(8);
     // ---- a12/a13: outcomes (:510-538) -------------------------------------
+    // The compiled shapes load the scaled columns' bounds again here (L2 hits, in flight over the
+    // np.dot and the medians) instead of holding four registers since the rescale: under the
+    // 128-register budget the allocator otherwise spills them and reloads them per rescaled column.
+    double lo2 = NT > 0 ? 0.0 : loj, hi2 = NT > 0 ? 0.0 : hij;  // (read by scaled columns only)
+    if constexpr (NT > 0) {
+        if (col && scj) {
+            lo2 = a.lo[bo + l];
+            hi2 = a.hi[bo + l];
+        }
+    }
     double rawj = col ? ob_vecmat(S.smooth, S.F + l, ES, N, E, l) : 0.0;  // np.dot(smooth_rep, F) (:510)
     STAMP(15);
     if (scaled_mask) {
@@ -1805,8 +2022,8 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
     if (col) {
         if (scj) {
             adjj = rawj;
-            finj = adjj * (hij - loj);
-            finj = finj + loj;
+            finj = adjj * (hi2 - lo2);
+            finj = finj + lo2;
         } else {
             adjj = catch_(rawj, a.catch_tol);
             finj = adjj;

@@ -1,7 +1,7 @@
 """Throughput of batched_round_kernel against resident rounds per CU (diagnostic).
 
 Pads the kernel's dynamic LDS (PCX_BATCHED_LDS_PAD, read once per process) so that
-at most k rounds fit one CU's 160 KiB, for k = 10 (unpadded) down to 6, and times the
+at most k rounds fit one CU's 160 KiB, for k = 16 (unpadded) down to 8, and times the
 C3 launch (65,536 50x20 rounds) with HIP events.  If time scales like 1/k the kernel is
 latency bound and more resident rounds (less LDS / fewer VGPRs per round) pay off.
 
@@ -42,11 +42,15 @@ def child():
 
 
 def main():
-    # batched_lds_bytes(50, 20, PCA): smem_doubles() in pcx_batched.hip -- F [50][21], packed C
-    # (210), M (the median scratch, 239), rep, five event vectors
-    base = 8 * (50 * 21 + 210 + 239 + 50 + 5 * 20)
-    for k in (12, 10, 9, 8, 6):
-        pad = max(0, LDS_CU // k - base - 256) if k < LDS_CU // base else 0
+    # batched_lds_bytes(50, 20, PCA): smem_doubles() in pcx_batched.hip -- F [50][20] (1,000
+    # doubles), "C" (90), "M" (159), miss (20): 10,152 bytes, eight 1,280-byte units.  LDS is handed
+    # out in those units, so k rounds fit a CU when each takes 128 // k of them.
+    sys.path.insert(0, ROOT)
+    from pyconsensus_amd import _lib
+
+    base = int(_lib.lib().pcx_batched_lds_bytes(50, 20, 0))
+    for k in (16, 14, 12, 10, 8):
+        pad = max(0, (128 // k) * 1280 - base)
         env = dict(os.environ, PCX_BATCHED_LDS_PAD=str(pad))
         r = subprocess.run([sys.executable, __file__, "--child"], env=env, capture_output=True, text=True,
                            timeout=300)
