@@ -76,10 +76,11 @@ int      pcx_synchronize(pcx_ctx* ctx);
 /* style Monte Carlo, README.rst:52-56).  Each round is the complete            */
 /* Oracle(reports, event_bounds, reputation).consensus() of __init__.py:102-611. */
 /* N <= 64, E <= 32: one round per wavefront, asynchronous on the stream.      */
-/* N <= 256, E <= 64 (all but the clusterings): one 256-thread workgroup per    */
-/* round (the same SPEC order), asynchronous.  Any other shape or algorithm     */
-/* (E <= 65536): each round is one single-matrix consensus, a pool of worker    */
-/* streams keeps many in flight (PCX_ROUND_WORKERS, default 16); synchronous.   */
+/* N <= 256, E <= 64 (every algorithm; k-means with kmeans_k <= 16): one        */
+/* 256-thread workgroup per round (the same SPEC order), asynchronous.  Any      */
+/* other shape (E <= 65536) or code-book size: each round is one single-matrix   */
+/* consensus, a pool of worker streams keeps many in flight (PCX_ROUND_WORKERS,  */
+/* default 16); synchronous.  pcx_batched_route tells which of the three.        */
 /* ------------------------------------------------------------------------ */
 typedef struct {
     int64_t n_rounds;             /* B                                           */
@@ -451,6 +452,18 @@ int pcx_test_inject_enomem(pcx_ctx* ctx, int worker);
  * <= 32, algorithm as in pcx_batch): what bounds the rounds resident per CU (LDS is handed out in
  * 1,280-byte units of the CU's 160 KiB).  No device needed.  For the tests and the tools. */
 int64_t pcx_batched_lds_bytes(int n_reporters, int n_events, int algorithm);
+/* The same for the workgroup-per-round kernel (rounds above 64 x 32 up to 256 x 64, every
+ * algorithm): at most the 160 KiB a workgroup may use; 0 for a shape or algorithm it does not take. */
+int64_t pcx_medium_lds_bytes(int n_reporters, int n_events, int algorithm);
+
+/* Where pcx_consensus_batched_f64 runs a batch of n_reporters x n_events rounds: one wavefront per
+ * round (up to 64 x 32), one workgroup per round (up to 256 x 64; k-means with kmeans_k <= 16), both
+ * ONE asynchronous launch, or the round scheduler (host threads, returns when every output is
+ * written).  kmeans_k matters for PCX_ALG_KMEANS only.  -1: arguments that call would refuse.  A
+ * pure function of its arguments -- no context, no device, and the PCX_NO_MEDIUM diagnostic override
+ * is not consulted; pcx_consensus_batched_f64 decides with the same code. */
+enum pcx_route { PCX_ROUTE_WAVE = 0, PCX_ROUTE_WORKGROUP = 1, PCX_ROUTE_SCHEDULER = 2 };
+int pcx_batched_route(int n_reporters, int n_events, int algorithm, int kmeans_k);
 
 #ifdef __cplusplus
 }

@@ -70,14 +70,17 @@ def _declare(lib):
         ("pcx_selftest_chunked_copy", i32, [i64, i64, i32, i32, i64]),
         ("pcx_test_inject_enomem", i32, [vp, i32]),
         ("pcx_batched_lds_bytes", i64, [i32, i32, i32]),
+        ("pcx_medium_lds_bytes", i64, [i32, i32, i32]),
+        ("pcx_batched_route", i32, [i32, i32, i32, i32]),
         ("pcx_philox4x32_10", None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         ("pcx_sim_generate_host", i32, [C.POINTER(_abi.Sim), i32, C.POINTER(_abi.SimRounds)]),
         ("pcx_sim_generate_f64", i32, [vp, C.POINTER(_abi.Sim), i32, C.POINTER(_abi.SimRounds)]),
         ("pcx_sim_metrics_f64", i32, [vp, C.POINTER(_abi.Sim), C.POINTER(_abi.SimRounds), vp, vp, vp, vp, vp]),
         ("pcx_simulate_f64", i32, [vp, C.POINTER(_abi.Sim), C.POINTER(_abi.SimResult)]),
     ]:
-        if name == "pcx_batched_lds_bytes" and os.environ.get("PCX_LIB") and not hasattr(lib, name):
-            continue  # an A/B build of a revision before this query (tools/ab_build.sh)
+        if (name in ("pcx_batched_lds_bytes", "pcx_medium_lds_bytes", "pcx_batched_route")
+                and os.environ.get("PCX_LIB") and not hasattr(lib, name)):
+            continue  # an A/B build of a revision before these queries (tools/ab_build.sh)
         f = getattr(lib, name)
         f.restype = res
         f.argtypes = args

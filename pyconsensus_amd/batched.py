@@ -4,8 +4,10 @@ Each round is exactly ``Oracle(reports[b], event_bounds_b, reputation[b]).consen
 (pyconsensus/__init__.py:102-611).  This is the regime of Simulator.jl-style Monte
 Carlo drivers (README.rst:52-56), which loop consensus() over many random rounds.
 Rounds of at most 64 reporters x 32 events run in one wavefront each of
-``batched_round_kernel`` (csrc/pcx_batched.hip); larger rounds run as single-matrix
-consensuses, many in flight on a pool of worker streams (csrc/pcx_rounds.cpp).
+``batched_round_kernel`` (csrc/pcx_batched.hip); rounds up to 256 x 64 in one workgroup each of
+``medium_round_kernel`` (csrc/pcx_medium.hip), every algorithm (k-means with up to 16 codes);
+larger rounds run as single-matrix consensuses, many in flight on a pool of worker streams
+(csrc/pcx_rounds.cpp).  :func:`route` tells which of the three a shape takes.
 """
 from __future__ import annotations
 
@@ -24,6 +26,9 @@ def kmeans_k(N):
     return int(np.ceil(np.sqrt(N)))
 
 
+kmeans_k_default = kmeans_k  # (route()'s parameter shadows the name)
+
+
 def kmeans_draws(B, N, restarts=_abi.KMEANS_RESTARTS, random_state=None):
     """Initial code-book rows of B k-means rounds, [B][restarts][k] int32.
 
@@ -38,6 +43,25 @@ def kmeans_draws(B, N, restarts=_abi.KMEANS_RESTARTS, random_state=None):
         for r in range(restarts):
             out[b, r] = rs.choice(N, size=k, replace=False)
     return out
+
+
+ROUTES = ("wave", "workgroup", "scheduler")  # include/pcx.h enum pcx_route
+
+
+def route(N, E, algorithm="PCA", kmeans_k=None):
+    """Where ``consensus_batched`` runs rounds of N x E: ``"wave"`` (one wavefront per round, up to
+    64 x 32) and ``"workgroup"`` (one workgroup per round, up to 256 x 64; k-means with at most 16
+    codes) are ONE asynchronous kernel launch; ``"scheduler"`` is the host-driven round scheduler,
+    which returns once every output is written.  ``kmeans_k`` defaults to :func:`kmeans_k` (N).
+    Needs no GPU; raises ValueError for arguments ``consensus_batched`` refuses."""
+    alg = _abi.ALGORITHMS.get(algorithm)
+    if alg is None:
+        raise NotImplementedError("algorithm %r is not on the GPU path" % (algorithm,))
+    k = kmeans_k_default(N) if kmeans_k is None else int(kmeans_k)
+    r = _lib.lib().pcx_batched_route(int(N), int(E), alg, k)
+    if r < 0:
+        raise ValueError("no batched route for %d x %d rounds, algorithm %r, kmeans_k %d" % (N, E, algorithm, k))
+    return ROUTES[r]
 
 
 def clusterfeck_threshold(E):
@@ -69,12 +93,13 @@ def consensus_batched(reports, reputation=None, scaled=None, lo=None, hi=None,
                 copy) -- the drop-in's per-call path, where each separate small copy costs ~10 us
 
     Returns a dict of torch tensors on the device, named like the ABI fields
-    (``smooth_rep``, ``outcomes_final``, ...).  Three regimes:
-    rounds up to 64 x 32 (one wave per round) and up to 256 x 64 (one workgroup per round,
-    any non-clustering algorithm) are ONE kernel launch, asynchronous on torch's current
-    stream -- synchronise before reading the outputs on the host; the round scheduler (the
-    clusterings above 64 x 32, or rounds above 256 x 64) returns only once every output is
-    written.
+    (``smooth_rep``, ``outcomes_final``, ...).  Three regimes (:func:`route`):
+    rounds up to 64 x 32 (one wave per round) and up to 256 x 64 (one workgroup per round; every
+    algorithm, the clusterings included, k-means with code books of at most 16 rows -- the
+    reference's own ceil(sqrt(N)) up to there; kmeans_init is read on the device) are ONE kernel
+    launch, asynchronous on torch's current stream -- synchronise before reading the outputs on
+    the host; the round scheduler (rounds above 256 x 64, k-means with larger code books) returns
+    only once every output is written.
     """
     t = _device.require_gpu()
     dev = t.device(device) if device is not None else t.device("cuda", t.cuda.current_device())

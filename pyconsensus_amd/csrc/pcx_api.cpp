@@ -245,6 +245,19 @@ int pcx_synchronize(pcx_ctx* ctx) {
     return e == hipSuccess ? PCX_OK : hip_fail(e, "pcx_synchronize");
 }
 
+// where a batch of n_reporters x n_events rounds runs (pcx_batched_route and the call itself)
+static int batched_route(int64_t N, int64_t E, int alg, int k) {
+    if (N < 1 || N > 0x7fffffff || E < 1 || E > 65536 || alg < PCX_ALG_PCA || alg > PCX_ALG_CLUSTERFECK) return -1;
+    const bool large = N > 64 || E > 32;  // beyond one wavefront per round
+    if (alg == PCX_ALG_KMEANS && (k < 1 || k > (large ? 1024 : 8) || k > N)) return -1;
+    if (!large) return PCX_ROUTE_WAVE;
+    return pcx::medium_fits((int)N, (int)E, alg, k) ? PCX_ROUTE_WORKGROUP : PCX_ROUTE_SCHEDULER;
+}
+
+int pcx_batched_route(int n_reporters, int n_events, int algorithm, int kmeans_k) {
+    return batched_route(n_reporters, n_events, algorithm, kmeans_k);
+}
+
 int pcx_consensus_batched_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_result* out) {
     if (!ctx || !in || !out) return fail(PCX_EINVAL, "pcx_consensus_batched_f64: null argument");
     if (in->n_rounds < 0 || in->n_rounds > 0x7fffffff)
@@ -322,12 +335,14 @@ int pcx_consensus_batched_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_resul
     a.components = out->components;
     a.original = out->original;
     a.filled = out->filled;
-    if (large) {
-        if (pcx::medium_fits(a) && !getenv("PCX_NO_MEDIUM")) {
+    const int route = batched_route(in->n_reporters, in->n_events, in->algorithm, in->kmeans_k);
+    if (route < 0) return fail(PCX_EINVAL, "batched: invalid shape or algorithm");  // (refused above)
+    if (route != PCX_ROUTE_WAVE) {
+        if (route == PCX_ROUTE_WORKGROUP && !getenv("PCX_NO_MEDIUM")) {
             // one workgroup per round (pcx_medium.hip), in chunks of bounded scratch
             const size_t cap = (size_t)2 << 30;
             const int64_t chunk = pcx::medium_chunk(a, cap);
-            const size_t per = ((a.filled ? 0 : (size_t)a.N * a.E) + (size_t)a.E * a.E) * sizeof(double);
+            const size_t per = pcx::medium_scratch_per_round(a);
             const size_t need = per * (size_t)chunk;
             if (ctx->mscr_bytes < need) {
                 if (ctx->mscr) (void)hipFree(ctx->mscr);
@@ -339,6 +354,7 @@ int pcx_consensus_batched_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_resul
             }
             double* Fscr = (double*)ctx->mscr;
             double* Cscr = Fscr + (a.filled ? 0 : (size_t)chunk * a.N * a.E);
+            double* Xscr = Cscr + (size_t)chunk * a.E * a.E;  // the clusterings' cluster sums / observations
             const char* mst = getenv("PCX_STAMPS");
             if (mst && mst[0] == '1') {  // diagnostic: per-phase clock breakdown
                 long long* d = nullptr;
@@ -348,7 +364,7 @@ int pcx_consensus_batched_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_resul
                 }
             }
             for (int64_t b0 = 0; b0 < a.B && e == hipSuccess; b0 += chunk)
-                e = pcx::launch_medium(a, b0, std::min<int64_t>(chunk, a.B - b0), Fscr, Cscr, ctx->stream);
+                e = pcx::launch_medium(a, b0, std::min<int64_t>(chunk, a.B - b0), Fscr, Cscr, Xscr, ctx->stream);
             if (a.stamps) {  // stamps 0..15 in program order (pcx_medium.hip MSTAMP(k))
                 std::vector<long long> h(a.B * 32);
                 (void)hipMemcpyAsync(h.data(), a.stamps, h.size() * sizeof(long long), hipMemcpyDeviceToHost,
@@ -611,6 +627,11 @@ int pcx_selftest_rounds_sched(int workers, int64_t rounds, int enomem_worker, in
 int pcx_selftest_chunked_copy(int64_t bytes, int64_t chunk, int slots, int threads, int64_t fail_chunk) {
     return pcx::selftest_chunked_copy(bytes, chunk, slots, threads, fail_chunk);
 }
+int64_t pcx_medium_lds_bytes(int n_reporters, int n_events, int algorithm) {
+    if (!pcx::medium_fits(n_reporters, n_events, algorithm, 1)) return 0;
+    return (int64_t)pcx::medium_lds_bytes(n_reporters, n_events, algorithm);
+}
+
 int64_t pcx_batched_lds_bytes(int n_reporters, int n_events, int algorithm) {
     if (n_reporters < 1 || n_reporters > 64 || n_events < 1 || n_events > 32) return -1;
     return (int64_t)pcx::batched_lds_bytes(n_reporters, n_events, algorithm);

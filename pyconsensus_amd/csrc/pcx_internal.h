@@ -210,10 +210,14 @@ struct BatchArgs {
 
 size_t batched_lds_bytes(int N, int E, int algorithm);
 hipError_t launch_batched(const BatchArgs& a, hipStream_t stream);
-// rounds above one wavefront (N <= 256, E <= 64; PCA / absolute / cokurtosis): one workgroup each
-bool medium_fits(const BatchArgs& a);
+// rounds above one wavefront (N <= 256, E <= 64; every algorithm, k-means up to 16 codes): one
+// workgroup each.  Xscr: the clusterings' per-round N x E scratch (unused by the other algorithms).
+bool medium_fits(int N, int E, int algorithm, int kmeans_k);
+size_t medium_lds_bytes(int N, int E, int algorithm);
+size_t medium_scratch_per_round(const BatchArgs& a);
 int64_t medium_chunk(const BatchArgs& a, size_t scratch_bytes);
-hipError_t launch_medium(const BatchArgs& a, int64_t b0, int64_t nb, double* Fscr, double* Cscr, hipStream_t st);
+hipError_t launch_medium(const BatchArgs& a, int64_t b0, int64_t nb, double* Fscr, double* Cscr, double* Xscr,
+                         hipStream_t st);
 
 // ---------------------------------------------------------------- Monte Carlo simulator (pcx_sim.hip)
 // one timestep's rounds on the device / on the host (the same inline generator, pcx_sim.h)

@@ -16,8 +16,9 @@
 // region (power-iteration matrices / median scratch / staged covariance rows / np.dot block
 // partials), the per-element NA flags and the row / event vectors; the filled matrix and the
 // covariance live in a per-round global scratch (L2-resident).  DESIGN.md 5.3.
-// Algorithms: PCA, "absolute", "big-five", "fixed-variance", "cokurtosis" (the clusterings take
-// the round scheduler).
+// Algorithms: all eight; "hierarchical", "clusterfeck" and "k-means" (code books up to 16) in a
+// second instantiation of the kernel, their cluster sums / whitened observations in a second
+// per-round global scratch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -576,9 +577,503 @@ __device__ int component_scores(const BatchArgs& a, const double* C, double* A, 
     return a.algorithm == PCX_ALG_FIXED_VARIANCE ? used : -1;
 }
 
-struct MedLds {  // offsets (doubles) into the dynamic LDS
-    int M, T, vN, vE, flags;
+// ---- clustering algorithms (SPEC hier_nc / feck_nc / kmeans_nc), the CLUS instantiation only ----
+// Each turns the filled reports into the nonconformity vector nc (LDS, one row per thread:
+// N <= MT).  L is the LDS work region (medium_region doubles); X is this round's N x E global
+// scratch, laid out event-major ([k][i]) so that a thread per row or per cluster reads it
+// coalesced.
+static_assert(MT >= MN, "one thread per reporter row");
+constexpr int M_KMAX = 16;          // k-means code books: ceil(sqrt(256))
+constexpr int M_KMEANS_MAXIT = 4096;  // Lloyd steps per restart (the SPEC's guard)
+
+// first thread of the smallest key among the candidate threads (block call; -1: none), the key
+// through *kmin.  shd / shi: MT / 64 slots each, free again after the caller's next barrier.
+__device__ int bfirstmin(bool cand, double key, double* shd, int* shi, double* kmin) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const double v = cand ? key : __builtin_inf();
+    double m = v;
+    for (int s = 1; s < 64; s <<= 1) m = fmin(m, __shfl_xor(m, s, 64));
+    const unsigned long long at = __ballot(cand && v == m);
+    if (lane == 0) {
+        shd[wv] = m;
+        shi[wv] = at ? wv * 64 + __builtin_ctzll(at) : -1;
+    }
+    __syncthreads();
+    int bi = -1;
+    double bm = __builtin_inf();
+    for (int w = 0; w < MT / 64; w++)
+        if (shi[w] >= 0 && (bi < 0 || shd[w] < bm)) {
+            bm = shd[w];
+            bi = shi[w];
+        }
+    *kmin = bm;
+    return bi;
+}
+
+// SPEC nc_from_sizes: (size - min size) / sum, the integer sum exact, equal sizes 0/0 = NaN
+__device__ void mnc_from_sizes(int size, int N, double* nc, int* red) {
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        red[0] = 0x7fffffff;
+        red[1] = 0;
+    }
+    __syncthreads();
+    if (tid < N) atomicMin(&red[0], size);
+    __syncthreads();
+    const int mn = red[0];
+    if (tid < N) atomicAdd(&red[1], size - mn);
+    __syncthreads();
+    if (tid < N) nc[tid] = (double)(size - mn) / (double)red[1];
+    __syncthreads();
+}
+
+// hierarchical: the connected components of {sqrt(d2_ij) <= t}, d2_ij the sequential sum of the
+// squared wcd differences; thread i owns row i's adjacency mask, labels settle by min-label
+// propagation with one pointer jump per sweep
+__device__ __noinline__ void mhier_nc(const double* F, const double* mu, int N, int E, double t, double* X, double* L,
+                                      double* nc) {
+    const int tid = threadIdx.x;
+    for (int e = tid; e < N * E; e += MT) X[(e % E) * N + e / E] = F[e] - mu[e % E];
+    unsigned long long* adj = (unsigned long long*)L;  // [N][4]
+    int* lab = (int*)(L + 4 * N);                      // [N]
+    int* cnt = lab + N;                                // [N]
+    int* red = cnt + N;                                // [2]
+    __syncthreads();
+    const bool row = tid < N;
+    if (row) {
+#pragma unroll
+        for (int w = 0; w < MN / 64; w++) {
+            unsigned long long mw = 0;
+            const int jend = N < 64 * w + 64 ? N : 64 * w + 64;
+            for (int j0 = 64 * w; j0 < jend; j0 += 4) {
+                double d2[4] = {0.0, 0.0, 0.0, 0.0};
+                int jj[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) jj[q] = j0 + q < N ? j0 + q : N - 1;
+                for (int k = 0; k < E; k++) {
+                    const double di = X[k * N + tid];
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        const double df = di - X[k * N + jj[q]];
+                        d2[q] = d2[q] + df * df;
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < 4; q++)
+                    if (j0 + q < N && j0 + q != tid && sqrt(d2[q]) <= t) mw |= 1ull << (j0 + q - 64 * w);
+            }
+            adj[tid * 4 + w] = mw;
+        }
+        lab[tid] = tid;
+        cnt[tid] = 0;
+    }
+    __syncthreads();
+    for (;;) {
+        int nl = 0;
+        bool changed = false;
+        if (row) {
+            const int old = lab[tid];
+            nl = old;
+            for (int w = 0; w < MN / 64; w++) {
+                unsigned long long m = adj[tid * 4 + w];
+                while (m) {
+                    const int j = 64 * w + __builtin_ctzll(m);
+                    m &= m - 1;
+                    const int lj = lab[j];
+                    nl = lj < nl ? lj : nl;
+                }
+            }
+            const int lj = lab[nl];
+            nl = lj < nl ? lj : nl;
+            changed = nl != old;
+        }
+        __syncthreads();
+        if (row) lab[tid] = nl;
+        if (!__syncthreads_or(changed)) break;
+    }
+    if (row) atomicAdd(&cnt[lab[tid]], 1);
+    __syncthreads();
+    mnc_from_sizes(row ? cnt[lab[tid]] : 0, N, nc, red);
+}
+
+// clusterfeck's running clusters: thread x = cluster x
+struct MFeck {
+    double* sumT;   // [E][N] (global) sum(vec * repVec, axis=0), running in member order
+    double* meanT;  // [E][N] (global) SPEC feck_mean: the founding row of a singleton, else sumT / crep --
+                    // kept current as a cluster changes (one per row), so the distances divide nothing
+    double* crep;   // [N] running member weight
+    double* dx;     // [N] per-cluster distance to the mode
+    int* of;        // [N] cluster of each row, -1 = none
+    const int* rnan;  // [N] the row holds a NaN
+    const double* w;  // [N] member weights
+    const double* F;
+    int N, E;
 };
+
+// one cluster() pass (SPEC feck_pass + feck_rowdist): rows in order, the existing clusters'
+// distances in parallel (numpy pairwise sums), first minimum; dm = the rows' distances for this
+// pass's mode; returns the mode's distance to outc (every thread alike)
+__device__ __noinline__ double mfeck_pass(const MFeck& f, double thr, const double* outc, double* mm, double* dm,
+                                          double* shd, int* shi) {
+    const int tid = threadIdx.x, N = f.N, E = f.E;
+    // (no cluster at all: every row holds a NaN; the mode's mean stays defined)
+    if (tid < E) f.meanT[tid * N] = f.F[tid];
+    if (tid == 0) f.crep[0] = 0.0;
+    __syncthreads();
+    int ncl = 0;
+    for (int i = 0; i < N; i++) {
+        const double* Fi = f.F + i * E;
+        const bool valid = tid < ncl;
+        double d = 0.0;
+        if (valid) d = sqrt(mpw([&](int k) { const double t = Fi[k] - f.meanT[k * N + tid]; return t * t; }, E));
+        double dmin;
+        const int bx = bfirstmin(valid && d < 0x1p255, d, shd, shi, &dmin);
+        const double wi = f.w[i];
+        if (bx >= 0 && dmin < thr) {
+            if (tid < 64) {  // wave 0 (E <= 64): every lane reads the weight before lane 0 updates it
+                const double nr = f.crep[bx] + wi;
+                mwsync();
+                if (tid < E) {
+                    const double sm = f.sumT[tid * N + bx] + Fi[tid] * wi;
+                    f.sumT[tid * N + bx] = sm;
+                    f.meanT[tid * N + bx] = sm / nr;
+                }
+                if (tid == 0) {
+                    f.crep[bx] = nr;
+                    f.of[i] = bx;
+                }
+            }
+        } else if (!f.rnan[i]) {
+            const int x = ncl++;
+            if (tid < E) {
+                f.sumT[tid * N + x] = Fi[tid] * wi;
+                f.meanT[tid * N + x] = Fi[tid];
+            }
+            if (tid == 0) {
+                f.crep[x] = wi;
+                f.of[i] = x;
+            }
+        } else if (tid == 0) {
+            f.of[i] = -1;
+        }
+        __syncthreads();
+    }
+    const bool valid = tid < ncl;
+    const double r = valid ? f.crep[tid] : 0.0;
+    double top;
+    int mode = bfirstmin(valid && r > 0.0, -r, shd, shi, &top);  // first cluster of largest weight
+    if (mode < 0) mode = 0;
+    if (tid < E) mm[tid] = f.meanT[tid * N + mode];
+    __syncthreads();
+    if (valid) f.dx[tid] = sqrt(mpw([&](int k) { const double t = mm[k] - f.meanT[k * N + tid]; return t * t; }, E));
+    const double dmode = sqrt(mpw([&](int k) { const double t = mm[k] - outc[k]; return t * t; }, E));
+    __syncthreads();
+    if (tid < N) {
+        const int o = f.of[tid];
+        dm[tid] = o >= 0 ? f.dx[o] : 0.0;
+    }
+    __syncthreads();
+    return dmode;
+}
+
+__device__ __noinline__ void mfeck_nc(const BatchArgs& a, const double* F, const double* tok, int N, int E, double* X,
+                                      double* L, double* nc, double* scal) {
+    const int tid = threadIdx.x;
+    MFeck f;
+    f.sumT = X;
+    f.meanT = X + N * E;
+    f.crep = L;
+    f.dx = L + N;
+    double* w = L + 2 * N;
+    double* dm1 = L + 3 * N;
+    double* dm2 = L + 4 * N;
+    double* outc = L + 5 * N;
+    double* mm = outc + E;
+    double* shd = mm + E;  // [4]
+    f.of = (int*)(shd + 4);
+    int* rnan = f.of + N;
+    int* shi = rnan + N;  // [4]
+    f.rnan = rnan;
+    f.w = w;
+    f.F = F;
+    f.N = N;
+    f.E = E;
+    if (tid < N) {
+        w[tid] = tok[tid] == 0.0 ? 0.00001 : tok[tid];
+        int nn = 0;
+        for (int k = 0; k < E; k++) nn |= __builtin_isnan(F[tid * E + k]) ? 1 : 0;
+        rnan[tid] = nn;
+    }
+    double thr = a.cluster_threshold;
+    if (!(thr > 0.0)) {
+        thr = log10((double)E) / 1.77;
+        if (thr == 0.0) thr = 0.3;
+    }
+    __syncthreads();
+    if (tid == 0) scal[0] = mpw([&](int i) { return w[i]; }, N);
+    __syncthreads();
+    if (tid < E) {  // outcomes = np.ma.average(features, axis=0, weights=rep)
+        double num;
+        if (E == 1) {
+            num = mpw([&](int i) { return F[i * E + tid] * w[i]; }, N);
+        } else {
+            num = F[tid] * w[0];
+            for (int i = 1; i < N; i++) num = num + F[i * E + tid] * w[i];
+        }
+        outc[tid] = num / scal[0];
+    }
+    __syncthreads();
+    const double d1 = mfeck_pass(f, thr, outc, mm, dm1, shd, shi);
+    const double* dm = dm1;
+    if (d1 > 1.07) {  // a far mode re-clusters once with 3 x thr; the closer mode wins
+        const double d2 = mfeck_pass(f, thr * 3, outc, mm, dm2, shd, shi);
+        if (d2 < d1) dm = dm2;
+    }
+    if (tid == 0) {  // np.amax: NaN propagates
+        double mx = dm[0];
+        for (int i = 1; i < N; i++)
+            if (__builtin_isnan(dm[i]) || dm[i] > mx) mx = __builtin_isnan(mx) ? mx : dm[i];
+        scal[1] = mx;
+    }
+    __syncthreads();
+    if (tid < N) w[tid] = fabs(1.0 - dm[tid] / (scal[1] + 0.00000001));  // (the weights are done)
+    __syncthreads();
+    if (tid == 0) {  // normalize
+        const double S = mpw([&](int i) { return w[i]; }, N);
+        scal[2] = S;
+        scal[3] = S == 0 ? mpw([&](int i) { return w[i] + 1.0; }, N) : S;
+    }
+    __syncthreads();
+    if (tid < N) nc[tid] = scal[2] == 0 ? (w[tid] + 1.0) / scal[3] : w[tid] / scal[3];
+    __syncthreads();
+}
+
+// scipy _vq.vq distance^2 (SPEC vq_d2) of one observation x(k) against four codes at a time (c: the
+// first one's row, stride E; rows past `nc` codes are clamped and their result unused): E < 5 the
+// naive loop; else -2 x.c (one fma chain for E < 32, eight interleaved chains summed as a tree
+// from 32) + |x|^2 + |c|^2.  The observation is read eight events ahead, once for the four codes.
+template <class XG>
+__device__ __forceinline__ void mvq_d2x4(XG x, const double* c, int nc, int E, double xs, const double* cs, double* d) {
+    const double* cq[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) cq[q] = c + (q < nc ? q : nc - 1) * E;
+    if (E < 32) {
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int k = 0; k < E; k += 8) {
+            double xv[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) xv[u] = k + u < E ? x(k + u) : 0.0;
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                if (k + u >= E) break;
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    if (E < 5) {
+                        const double t = xv[u] - cq[q][k + u];
+                        acc[q] = acc[q] + t * t;
+                    } else {
+                        acc[q] = fma(xv[u], cq[q][k + u], acc[q]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++) d[q] = E < 5 ? acc[q] : (-2.0 * acc[q] + xs) + cs[q < nc ? q : nc - 1];
+        return;
+    }
+    double a[4][8];
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+#pragma unroll
+        for (int u = 0; u < 8; u++) a[q][u] = 0.0;
+    for (int k = 0; k < E; k += 8) {
+        double xv[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) xv[u] = k + u < E ? x(k + u) : 0.0;
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            if (k + u >= E) break;
+#pragma unroll
+            for (int q = 0; q < 4; q++) a[q][u] = fma(xv[u], cq[q][k + u], a[q][u]);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const double dot = ((a[q][0] + a[q][1]) + (a[q][2] + a[q][3])) + ((a[q][4] + a[q][5]) + (a[q][6] + a[q][7]));
+        d[q] = (-2.0 * dot + xs) + cs[q < nc ? q : nc - 1];
+    }
+}
+
+// k-means (SPEC kmeans_nc): whiten(wcd) into X, scipy kmeans over the caller's restarts (best mean
+// distortion, strict <), vq labels, cluster sizes.  Thread i = observation i in vq; threads take
+// (code, event) pairs in the mean update, the member sums in row order.
+__device__ __noinline__ void mkmeans_nc(const BatchArgs& a, int64_t b, const double* F, const double* mu, int N, int E,
+                                        double* X, double* L, double* nc, double* scal) {
+    const int tid = threadIdx.x;
+    const bool row = tid < N;
+    double* book = L;                  // [M_KMAX][E]
+    double* best = book + M_KMAX * E;  // [M_KMAX][E]
+    double* sd = best + M_KMAX * E;    // [E]
+    double* csq = sd + E;              // [M_KMAX]
+    double* dist = csq + M_KMAX;       // [N]
+    int* lab = (int*)(dist + N);       // [N]
+    int* cntc = lab + N;               // [M_KMAX]
+    int* red = cntc + M_KMAX;          // [2]
+    // np.std(wcd, axis=0): sequential column sums (pairwise when E == 1); 0 -> 1
+    if (tid < E) {
+        const int j = tid;
+        double s, v;
+        if (E == 1) {
+            s = mpw([&](int i) { return F[i * E + j] - mu[j]; }, N);
+        } else {
+            s = 0.0;
+            for (int i = 0; i < N; i++) s = s + (F[i * E + j] - mu[j]);
+        }
+        const double m = s / (double)N;
+        if (E == 1) {
+            v = mpw([&](int i) { const double d = (F[i * E + j] - mu[j]) - m; return d * d; }, N);
+        } else {
+            v = 0.0;
+            for (int i = 0; i < N; i++) {
+                const double d = (F[i * E + j] - mu[j]) - m;
+                v = v + d * d;
+            }
+        }
+        double sj = sqrt(v / (double)N);
+        if (sj == 0.0) sj = 1.0;
+        sd[j] = sj;
+    }
+    __syncthreads();
+    for (int e = tid; e < N * E; e += MT) X[(e % E) * N + e / E] = (F[e] - mu[e % E]) / sd[e % E];
+    __syncthreads();
+    auto obs = [&](int k) { return X[k * N + tid]; };
+    double xs = 0.0;
+    if (row)
+        for (int k = 0; k < E; k++) xs = xs + obs(k) * obs(k);
+    // labels and distortions against `codes` (ncodes of them); the mean distortion in scal[0]
+    auto vq = [&](const double* codes, int ncodes) {
+        if (tid < ncodes) {
+            double s = 0.0;
+            for (int k = 0; k < E; k++) s = s + codes[tid * E + k] * codes[tid * E + k];
+            csq[tid] = s;
+        }
+        __syncthreads();
+        if (row) {
+            int li = 0;
+            double low = __builtin_inf();
+            for (int c0 = 0; c0 < ncodes; c0 += 4) {  // in code order, first minimum
+                double d[4];
+                mvq_d2x4(obs, codes + c0 * E, ncodes - c0, E, xs, csq + c0, d);
+#pragma unroll
+                for (int q = 0; q < 4; q++)
+                    if (c0 + q < ncodes && d[q] < low) {
+                        low = d[q];
+                        li = c0 + q;
+                    }
+            }
+            lab[tid] = li;
+            dist[tid] = low > 0 ? sqrt(low) : 0.0;
+        }
+        __syncthreads();
+    };
+    const int K = a.kmeans_k, RS = a.kmeans_restarts;
+    const int32_t* init = a.kmeans_init + b * (int64_t)RS * K;
+    double best_d = __builtin_inf();
+    int best_n = 0;
+    for (int r = 0; r < RS; r++) {
+        for (int o = tid; o < K * E; o += MT) {
+            const int c = o / E, k = o - c * E;
+            const int r0 = init[r * K + c];
+            book[o] = X[k * N + (r0 < 0 ? 0 : r0 >= N ? N - 1 : r0)];
+        }
+        int ncodes = K;
+        double prev0 = __builtin_inf(), prev1 = __builtin_inf();
+        for (int it = 0;; it++) {
+            __syncthreads();
+            vq(book, ncodes);
+            if (tid == 0) scal[0] = mpw([&](int i) { return dist[i]; }, N) / (double)N;
+            if (tid < ncodes) {
+                int n = 0;
+                for (int i = 0; i < N; i++) n += lab[i] == tid;
+                cntc[tid] = n;
+            }
+            __syncthreads();
+            prev0 = prev1;
+            prev1 = scal[0];
+            // update_cluster_means: member sums in row order, / count; empty codes dropped
+            unsigned nonempty = 0;
+            for (int c = 0; c < ncodes; c++) nonempty |= cntc[c] > 0 ? 1u << c : 0u;
+            double nv[M_KMAX * MEV / MT];
+            int nk[M_KMAX * MEV / MT];
+#pragma unroll
+            for (int q = 0; q < M_KMAX * MEV / MT; q++) {
+                const int p = tid + MT * q;
+                nk[q] = -1;
+                nv[q] = 0.0;
+                if (p < ncodes * E) {
+                    const int c = p / E, k = p - c * E;
+                    const int n = cntc[c];
+                    if (n > 0) {
+                        double sm = 0.0;
+                        for (int i = 0; i < N; i += 8) {  // in row order, loads eight ahead
+                            double xv[8];
+                            int lb[8];
+#pragma unroll
+                            for (int u = 0; u < 8; u++) {
+                                const int iu = i + u < N ? i + u : N - 1;
+                                xv[u] = X[k * N + iu];
+                                lb[u] = i + u < N ? lab[iu] : -1;
+                            }
+#pragma unroll
+                            for (int u = 0; u < 8; u++)
+                                if (lb[u] == c) sm = sm + xv[u];
+                        }
+                        nv[q] = sm / (double)n;
+                        nk[q] = __popc(nonempty & ((1u << c) - 1u)) * E + k;
+                    }
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < M_KMAX * MEV / MT; q++)
+                if (nk[q] >= 0) book[nk[q]] = nv[q];
+            ncodes = __popc(nonempty);
+            if (!(fabs(prev0 - prev1) > 1e-5) || it + 1 >= M_KMEANS_MAXIT) break;
+        }
+        __syncthreads();
+        if (prev1 < best_d) {  // block-uniform
+            best_d = prev1;
+            best_n = ncodes;
+            for (int o = tid; o < ncodes * E; o += MT) best[o] = book[o];
+        }
+    }
+    __syncthreads();
+    if (best_n == 0) {  // no restart with a finite distortion: the reference raises
+        if (row) nc[tid] = __builtin_nan("");
+        __syncthreads();
+        return;
+    }
+    vq(best, best_n);
+    if (tid < best_n) {
+        int n = 0;
+        for (int i = 0; i < N; i++) n += lab[i] == tid;
+        cntc[tid] = n;
+    }
+    __syncthreads();
+    mnc_from_sizes(row ? cntc[lab[tid]] : 0, N, nc, red);
+}
+
+// doubles of a round's clustering scratch: wcd / the whitened observations; clusterfeck's sums and means
+__host__ __device__ __forceinline__ int medium_xscratch(int N, int E, int alg) {
+    return alg == PCX_ALG_CLUSTERFECK ? 2 * N * E : alg >= PCX_ALG_KMEANS ? N * E : 0;
+}
+// doubles of the clusterings' LDS region (the carvings of mhier_nc / mfeck_nc / mkmeans_nc)
+__host__ __device__ __forceinline__ int medium_clus(int N, int E, int alg) {
+    if (alg == PCX_ALG_HIERARCHICAL) return 5 * N + 2;
+    if (alg == PCX_ALG_CLUSTERFECK) return 6 * N + 2 * E + 8;
+    if (alg == PCX_ALG_KMEANS) return 2 * M_KMAX * E + E + 2 * M_KMAX + 2 * N + 12;
+    return 0;
+}
 
 // N-vectors (each N doubles)
 enum { VN_REP = 0, VN_TOK, VN_S, VN_SET1, VN_SET2, VN_NW1, VN_NW2, VN_U, VN_THIS, VN_SMOOTH, VN_XS, VN_COUNT };
@@ -605,6 +1100,11 @@ __host__ __device__ __forceinline__ int medium_work(int N, int E, int alg) {
     const int m = mt > wq ? mt : wq;
     return m > vb ? m : vb;  // and bvecmat's block partials
 }
+// the work region with the clusterings' carvings (the other algorithms: medium_work)
+__host__ __device__ __forceinline__ int medium_region(int N, int E, int alg) {
+    const int w = medium_work(N, E, alg), c = medium_clus(N, E, alg);
+    return w > c ? w : c;
+}
 
 // diagnostic phase stamps (PCX_STAMPS=1): shader-clock reads at phase boundaries
 #define MSTAMP(k)                                                                 \
@@ -618,7 +1118,11 @@ __host__ __device__ __forceinline__ int medium_work(int N, int E, int alg) {
 #ifndef PCX_MEDIUM_WAVES  // waves per SIMD the VGPR budget is sized for (a build parameter for A/B runs)
 #define PCX_MEDIUM_WAVES 3
 #endif
-__global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(BatchArgs a, int64_t b0, double* Fscr, double* Cscr) {
+// CLUS: the instantiation that also holds the clusterings (their code and registers stay out of
+// the other one); Xscr is their per-round N x E scratch
+template <bool CLUS>
+__global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(BatchArgs a, int64_t b0, double* Fscr, double* Cscr,
+                                                                            double* Xscr) {
     extern __shared__ __attribute__((aligned(16))) double mlds[];
     __shared__ double sh[MT];
     __shared__ double scal[16];
@@ -629,7 +1133,7 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(Batc
     double* Tm = M + E * ES;
     // work region: M and Tm in the power iteration / Jacobi, per wave the median operands and
     // sort scratch in the interpolation, the outcomes and the certainty
-    double* vN = mlds + medium_work(N, E, a.algorithm);
+    double* vN = mlds + medium_region(N, E, a.algorithm);
     double* vE = vN + VN_COUNT * N;
     // NA flags [N][E], two bits per element (bit 0 NaN, bit 1 zero), sixteen to a word
     uint32_t* flw = (uint32_t*)(vE + VE_COUNT * E);
@@ -814,7 +1318,8 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(Batc
     __syncthreads();
     MSTAMP(4);
     int comps = -1;
-    if (alg == PCX_ALG_PCA || alg == PCX_ALG_BIG_FIVE || alg == PCX_ALG_FIXED_VARIANCE) {
+    const bool clustering = CLUS && alg >= PCX_ALG_KMEANS;  // they call wpca too: loading only
+    if (alg == PCX_ALG_PCA || alg == PCX_ALG_BIG_FIVE || alg == PCX_ALG_FIXED_VARIANCE || clustering) {
         // --- a5: weighted mean (np.ma.average, :317-319)
         double* mu = VEp(VE_MU);
         if (tid == 0) scal[4] = mpw([&](int i) { return rep[i]; }, N);
@@ -1058,7 +1563,9 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(Batc
         for (int j = tid; j < E; j += MT) loading[j] = x[j] / scal[9];
         __syncthreads();
         MSTAMP(7);
-        if (alg == PCX_ALG_PCA) {
+        if (clustering) {
+            // scores stay zeros
+        } else if (alg == PCX_ALG_PCA) {
             for (int i = tid; i < N; i += MT) {  // scores (:337)
                 double acc = 0.0;
                 for (int j = 0; j < E; j++) acc = fma(F[i * E + j] - mu[j], loading[j], acc);
@@ -1074,7 +1581,16 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(Batc
     }
     __syncthreads();
     MSTAMP(8);
-    if (alg != PCX_ALG_ABSOLUTE) {
+    if (clustering) {
+        // --- nc from the clusters (SPEC hier_nc / kmeans_nc / feck_nc); the work region is free
+        double* X = Xscr + (int64_t)blockIdx.x * medium_xscratch(N, E, alg);
+        if (alg == PCX_ALG_HIERARCHICAL)
+            mhier_nc(F, VEp(VE_MU), N, E, a.hierarchy_threshold, X, mlds, nc);
+        else if (alg == PCX_ALG_KMEANS)
+            mkmeans_nc(a, b, F, VEp(VE_MU), N, E, X, mlds, nc, scal);
+        else
+            mfeck_nc(a, F, tok, N, E, X, mlds, nc, scal);
+    } else if (alg != PCX_ALG_ABSOLUTE) {
         // --- a8/a9: nonconformity_rank (:487-500), tie -> nonconformity (:475-485)
         double* set1 = VNp(VN_SET1);
         double* set2 = VNp(VN_SET2);
@@ -1359,30 +1875,40 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(Batc
 
 }  // namespace
 
-bool medium_fits(const BatchArgs& a) {
-    return a.N >= 1 && a.N <= MN && a.E >= 1 && a.E <= MEV &&
-           a.algorithm >= PCX_ALG_PCA && a.algorithm <= PCX_ALG_COKURTOSIS;
+bool medium_fits(int N, int E, int alg, int kmeans_k) {
+    return N >= 1 && N <= MN && E >= 1 && E <= MEV && alg >= PCX_ALG_PCA && alg <= PCX_ALG_CLUSTERFECK &&
+           (alg != PCX_ALG_KMEANS || (kmeans_k >= 1 && kmeans_k <= M_KMAX));
 }
 
 size_t medium_lds_bytes(int N, int E, int alg) {
-    return ((size_t)medium_work(N, E, alg) + (size_t)VN_COUNT * N + (size_t)VE_COUNT * E) * sizeof(double) +
+    return ((size_t)medium_region(N, E, alg) + (size_t)VN_COUNT * N + (size_t)VE_COUNT * E) * sizeof(double) +
            (size_t)((N * E + 15) >> 4) * 4 + 16;
 }
 
-// rounds in chunks whose scratch (filled matrix unless the caller keeps it, covariance) fits
-// `scratch_bytes`; returns the chunk size used through *chunk
+// scratch bytes of one round: the filled matrix unless the caller keeps it, the covariance, the
+// clusterings' N x E (clusterfeck: two)
+size_t medium_scratch_per_round(const BatchArgs& a) {
+    const size_t ne = (size_t)a.N * a.E;
+    return ((a.filled ? 0 : ne) + (size_t)a.E * a.E + (size_t)medium_xscratch(a.N, a.E, a.algorithm)) * sizeof(double);
+}
+
+// rounds in chunks whose scratch fits `scratch_bytes`
 int64_t medium_chunk(const BatchArgs& a, size_t scratch_bytes) {
-    const size_t per = ((a.filled ? 0 : (size_t)a.N * a.E) + (size_t)a.E * a.E) * sizeof(double);
+    const size_t per = medium_scratch_per_round(a);
     int64_t c = (int64_t)(scratch_bytes / (per ? per : 1));
     return c < 1 ? 1 : (c > a.B ? a.B : c);
 }
 
-hipError_t launch_medium(const BatchArgs& a, int64_t b0, int64_t nb, double* Fscr, double* Cscr, hipStream_t st) {
+hipError_t launch_medium(const BatchArgs& a, int64_t b0, int64_t nb, double* Fscr, double* Cscr, double* Xscr,
+                         hipStream_t st) {
     if (nb <= 0) return hipSuccess;
     const size_t lds = medium_lds_bytes(a.N, a.E, a.algorithm);
     // (dynamic LDS above 64 KB needs no attribute on gfx950: the launch checks it against 160 KB)
     (void)hipGetLastError();  // report launch errors only
-    hipLaunchKernelGGL(medium_round_kernel, dim3((unsigned)nb), dim3(MT), lds, st, a, b0, Fscr, Cscr);
+    if (a.algorithm >= PCX_ALG_KMEANS)
+        hipLaunchKernelGGL(medium_round_kernel<true>, dim3((unsigned)nb), dim3(MT), lds, st, a, b0, Fscr, Cscr, Xscr);
+    else
+        hipLaunchKernelGGL(medium_round_kernel<false>, dim3((unsigned)nb), dim3(MT), lds, st, a, b0, Fscr, Cscr, Xscr);
     return hipGetLastError();
 }
 

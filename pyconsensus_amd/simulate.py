@@ -128,8 +128,9 @@ def simulate(B, N=50, E=20, T=1, seed=0, liar_frac=0.3, collude_frac=0.5, distor
     adds ``outputs`` (the last timestep's consensus outputs, as ``consensus_batched``).
 
     Stream semantics are ``consensus_batched``'s: rounds up to 256 x 64 are asynchronous on
-    torch's current stream -- synchronise before reading on the host; "k-means" and
-    "cokurtosis" are refused (they need host draws / caller scores)."""
+    torch's current stream with no host in the loop, "hierarchical" and "clusterfeck" included
+    (one workgroup per round above 64 x 32) -- synchronise before reading on the host; "k-means"
+    and "cokurtosis" are refused (they need host draws / caller scores)."""
     tc = _device.require_gpu()
     dev = tc.device(device) if device is not None else tc.device("cuda", tc.cuda.current_device())
     rep = _device.as_device(reputation, tc.float64, dev)
