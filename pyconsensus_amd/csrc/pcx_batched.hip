@@ -1452,6 +1452,19 @@ __host__ __device__ constexpr int compiled_es(int E) { return PCX_BATCHED_ES_EVE
 #ifndef PCX_BATCHED_WAVES  // waves per SIMD the compiled packed shapes' VGPR budget is sized for (4: 128 VGPRs)
 #define PCX_BATCHED_WAVES 4
 #endif
+// Build parameters of the instruction-count steps (0 builds the form before each):
+#ifndef PCX_BATCHED_ROWMASKS  // the rescale loop keeps per-row NaN / zero bit masks, no live ballots
+#define PCX_BATCHED_ROWMASKS 1
+#endif
+#ifndef PCX_BATCHED_RESCALE_WALK  // (with ROWMASKS) only scaled columns fetch bounds; no row mask on the ballots
+#define PCX_BATCHED_RESCALE_WALK 1
+#endif
+#ifndef PCX_BATCHED_KERNARG_OUT  // the output pointers are read from the kernel arguments where they are used
+#define PCX_BATCHED_KERNARG_OUT 1
+#endif
+#ifndef PCX_BATCHED_D12_ONE_PASS  // np.dot(n1, F) on lanes 0.., np.dot(n2, F) on lanes 32.. in one pass
+#define PCX_BATCHED_D12_ONE_PASS 1
+#endif
 
 // NT/ET > 0: the round shape is a compile-time constant (the Monte Carlo shapes the
 // launcher specialises, e.g. the 50 x 20 of config C3): every loop bound is known, so
@@ -1468,6 +1481,20 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
     const bool row = l < N, col = l < E;
     const int64_t bo = a.bounds_shared ? 0 : b * E;
     const bool has_bounds = a.scaled != nullptr;
+
+    // The output pointers are read from the kernel-argument segment where they are used (scalar
+    // loads, the segment's address made opaque at each use): as fields of `a` all of them are
+    // fetched at kernel entry and held -- 60 scalar registers spilled to lanes until the epilogue.
+#if PCX_BATCHED_KERNARG_OUT
+    typedef const __attribute__((address_space(4))) BatchArgs* KernArgs;
+    auto out_args = [&]() -> KernArgs {
+        uint64_t p = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();  // `a` is the only argument: offset 0
+        asm volatile("" : "+s"(p));
+        return (KernArgs)p;
+    };
+#else
+    auto out_args = [&]() { return &a; };
+#endif
 
     long long mprof[3] = {0, 0, 0};  // diagnostic: median sort / walk cycles (PCX_STAMPS)
     STAMP(0);
@@ -1523,9 +1550,58 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
     // ---- a2: rescale (:266-269) + NA masks (:278) -------------------------
     // (the next column's value is loaded before this column's stores: a load after a store to
     // the same LDS array would otherwise wait for it)
-    double xnext = row ? S.F[l * ES] : 0.0;
     // per-lane counts, 7 bits each: row l's zeros (bits 0-7) and NaNs (8-15), column l's zeros (16-23)
     uint32_t nacnt = 0;
+#if PCX_BATCHED_ROWMASKS
+    // Each row lane collects its own row's NaN / zero columns as bits of two 32-bit masks straight
+    // from the compares (E <= 32), and lane j takes column j's zero count when column j is visited,
+    // so a column's two ballots die with it.  (Summed from the ballots' bits instead, the whole
+    // accumulation sank to its first use after the certainty, and forty ballots waited for it in
+    // spilled scalar registers.)
+    // WALK: only a scaled column (a wave-uniform branch on scaled_mask) fetches its bounds and
+    // divides, and the lanes past the last row hold 1.0, neither NaN nor zero, so the compares are
+    // the ballots with no row mask applied.
+    constexpr bool WALK = PCX_BATCHED_RESCALE_WALK;
+    double xnext = row ? S.F[l * ES] : (WALK ? 1.0 : 0.0);
+    uint32_t nanb = 0, zerob = 0;
+    int zcol = 0;  // column l's zero count (lanes < E)
+    // (the compiled shapes' loop unrolled: left rolled, as the compiler leaves it with the
+    // scaled columns' branch inside, a column's load runs only one column ahead)
+#pragma unroll(ET > 0 ? ET : 1)
+    for (int j = 0; j < E; j++) {
+        const bool sc = (scaled_mask >> j) & 1;
+        double x = xnext;
+        if (j + 1 < E) xnext = row ? S.F[l * ES + j + 1] : (WALK ? 1.0 : 0.0);
+        if constexpr (WALK) {
+            if (sc) {  // wave-uniform
+                const double lo = bcast(loj, j), hi = bcast(hij, j);
+                if (row) {
+                    x = (x - lo) / (hi - lo);
+                    if (a.int_dtype) x = trunc(x);
+                    S.F[l * ES + j] = x;
+                }
+            }
+        } else {
+            const double lo = bcast(loj, j), hi = bcast(hij, j);
+            if (row && sc) {
+                x = (x - lo) / (hi - lo);
+                if (a.int_dtype) x = trunc(x);
+                S.F[l * ES + j] = x;
+            }
+        }
+        const bool xn = (WALK || row) && __builtin_isnan(x), xz = (WALK || row) && x == 0.0;
+        nanb |= xn ? 1u << j : 0u;
+        zerob |= xz ? 1u << j : 0u;
+        const uint64_t zm = ballot(xz), mm = ballot(xn) | zm;
+        zcol = l == j ? popc(zm) : zcol;
+        if (l == 0) S.miss[j] = mm;
+        // the three registers are formed here: without this the compiler sinks their updates to
+        // the first use again and keeps every column's compare masks alive for them
+        asm volatile("" : "+v"(nanb), "+v"(zerob), "+v"(zcol));
+    }
+    nacnt = (uint32_t)__popc(zerob) | ((uint32_t)__popc(nanb) << 8) | ((uint32_t)zcol << 16);
+#else
+    double xnext = row ? S.F[l * ES] : 0.0;
     for (int j = 0; j < E; j++) {
         const bool sc = (scaled_mask >> j) & 1;
         const double lo = bcast(loj, j), hi = bcast(hij, j);
@@ -1543,10 +1619,11 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
         nacnt += (uint32_t)((zm >> l) & 1) + ((uint32_t)((nm >> l) & 1) << 8) + (l == j ? (uint32_t)popc(zm) << 16 : 0u);
         if (l == 0) S.miss[j] = nm | zm;
     }
+#endif
     wsync();
     // result["original"] (the rescaled reports), from LDS in row-major order: every store
     // instruction writes 64 consecutive doubles (whole lines), not one column's 50 strided ones
-    if (a.original) round_to_global(a.original + b * (int64_t)N * E, S.F, N, E, ES, NT, ET);
+    if (double* const og = out_args()->original) round_to_global(og + b * (int64_t)N * E, S.F, N, E, ES, NT, ET);
 
     STAMP(2);
     // ---- a3: interpolation guesses (:284-313), column phase ----------------
@@ -1659,7 +1736,7 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
         }
     }
     wsync();
-    if (a.filled) round_to_global(a.filled + b * (int64_t)N * E, S.F, N, E, ES, NT, ET);
+    if (double* const fg = out_args()->filled) round_to_global(fg + b * (int64_t)N * E, S.F, N, E, ES, NT, ET);
 
     STAMP(3);
     // ---- old = rep . F (np.dot) -------------------------------------------
@@ -1923,9 +2000,29 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
         if (col) S.old[l] = oldj;
         wsync();
         double d1 = 0.0, d2 = 0.0;
+#if PCX_BATCHED_D12_ONE_PASS
+        {
+            // both products in one pass over the rows: lane j < E runs column j on n1, lane 32 + j
+            // the same column on n2 (E <= 32) -- one instruction stream, each lane its own vector
+            // and its column's own order (block, tail or ddot), then d2 moves down to lane j
+            const int jc = l & 31;
+            double d = 0.0;
+            if (jc < E) d = ob_vecmat(l < 32 ? S.n1 : S.n2, S.F + jc, ES, N, E, jc);  // np.dot(normalize(set), F) (:492)
+            const uint64_t du = (uint64_t)__double_as_longlong(d);
+            const int up = ((l + 32) & 63) << 2;
+            const uint32_t ulo = (uint32_t)__builtin_amdgcn_ds_bpermute(up, (int)(uint32_t)du);
+            const uint32_t uhi = (uint32_t)__builtin_amdgcn_ds_bpermute(up, (int)(uint32_t)(du >> 32));
+            if (col) {
+                d1 = d;
+                d2 = __longlong_as_double((long long)(((uint64_t)uhi << 32) | ulo));
+            }
+        }
+#endif
         if (col) {
+#if !PCX_BATCHED_D12_ONE_PASS
             d1 = ob_vecmat(S.n1, S.F + l, ES, N, E, l);  // np.dot(normalize(set1), F) (:492)
             d2 = ob_vecmat(S.n2, S.F + l, ES, N, E, l);
+#endif
             const double t = 0.01 * oldj;
             S.nv1[l] = d1 + t;
             S.nv2[l] = d2 + t;
@@ -2145,36 +2242,37 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
 
     STAMP(11);
     // ---- write the round ---------------------------------------------------
+    const auto oa = out_args();
     if (row) {
         const int64_t o = b * N + l;
-        if (a.old_rep) a.old_rep[o] = rep;
-        if (a.this_rep) a.this_rep[o] = this_i;
-        if (a.smooth_rep) a.smooth_rep[o] = smooth_i;
-        if (a.scores) a.scores[o] = sc_i;
-        if (a.na_row) a.na_row[o] = narow;
-        if (a.participation_rows) a.participation_rows[o] = pr;
-        if (a.relative_part) a.relative_part[o] = rel;
-        if (a.reporter_bonus) a.reporter_bonus[o] = (rowmasked || rep_masked) ? rel : rel * pna + smooth_i * (1.0 - pna);
+        if (oa->old_rep) oa->old_rep[o] = rep;
+        if (oa->this_rep) oa->this_rep[o] = this_i;
+        if (oa->smooth_rep) oa->smooth_rep[o] = smooth_i;
+        if (oa->scores) oa->scores[o] = sc_i;
+        if (oa->na_row) oa->na_row[o] = narow;
+        if (oa->participation_rows) oa->participation_rows[o] = pr;
+        if (oa->relative_part) oa->relative_part[o] = rel;
+        if (oa->reporter_bonus) oa->reporter_bonus[o] = (rowmasked || rep_masked) ? rel : rel * pna + smooth_i * (1.0 - pna);
     }
     if (col) {
         const int64_t o = b * E + l;
-        if (a.adj_first_loadings) a.adj_first_loadings[o] = ld_j;
-        if (a.outcomes_raw) a.outcomes_raw[o] = rawj;
-        if (a.outcomes_adjusted) a.outcomes_adjusted[o] = adjj;
-        if (a.outcomes_final) a.outcomes_final[o] = finj;
-        if (a.certainty) a.certainty[o] = certj;
-        if (a.consensus_reward) a.consensus_reward[o] = reward;
-        if (a.nas_filled) a.nas_filled[o] = nzj;
-        if (a.participation_columns) a.participation_columns[o] = rep_masked ? 1.0 : pcj;
-        if (a.author_bonus) a.author_bonus[o] = rep_masked ? 1.0 : relc * pna + reward * (1.0 - pna);
+        if (oa->adj_first_loadings) oa->adj_first_loadings[o] = ld_j;
+        if (oa->outcomes_raw) oa->outcomes_raw[o] = rawj;
+        if (oa->outcomes_adjusted) oa->outcomes_adjusted[o] = adjj;
+        if (oa->outcomes_final) oa->outcomes_final[o] = finj;
+        if (oa->certainty) oa->certainty[o] = certj;
+        if (oa->consensus_reward) oa->consensus_reward[o] = reward;
+        if (oa->nas_filled) oa->nas_filled[o] = nzj;
+        if (oa->participation_columns) oa->participation_columns[o] = rep_masked ? 1.0 : pcj;
+        if (oa->author_bonus) oa->author_bonus[o] = rep_masked ? 1.0 : relc * pna + reward * (1.0 - pna);
     }
     if (l == 0) {
-        if (a.participation) a.participation[b] = 1.0 - pna;
-        if (a.avg_certainty) a.avg_certainty[b] = avg_cert;
-        if (a.branch) a.branch[b] = branch;
-        if (a.flags) a.flags[b] = flags;
-        if (a.pi_iters) a.pi_iters[b] = iters;
-        if (a.components) a.components[b] = comps;
+        if (oa->participation) oa->participation[b] = 1.0 - pna;
+        if (oa->avg_certainty) oa->avg_certainty[b] = avg_cert;
+        if (oa->branch) oa->branch[b] = branch;
+        if (oa->flags) oa->flags[b] = flags;
+        if (oa->pi_iters) oa->pi_iters[b] = iters;
+        if (oa->components) oa->components[b] = comps;
     }
     STAMP(12);
     if (a.stamps && threadIdx.x == 0) {
