@@ -158,6 +158,42 @@ typedef struct {
 int pcx_consensus_batched_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_result* out);
 
 /* ------------------------------------------------------------------------ */
+/* Ragged batches (added under ABI 9; detect by symbol): B rounds of DIFFERENT  */
+/* shapes N_b x E_b in one launch of the one-wave round kernel.  The arrays are */
+/* the rounds' own arrays laid end to end in round order, with no padding (a     */
+/* padded row or column would change the reputation normalisation, the           */
+/* participation figures and the fills).  Every algorithm but k-means (its       */
+/* code-book size depends on N_b); "big-five" caps max_components at E_b per      */
+/* round (:134-137); "clusterfeck" with cluster_threshold <= 0 takes the          */
+/* log10(E_b)/1.77 rule per round.  Asynchronous on the context's stream.        */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+    int64_t n_rounds;
+    const int32_t* n_reporters;   /* HOST [B]: N_b in [1, 64]                                 */
+    const int32_t* n_events;      /* HOST [B]: E_b in [1, 32]                                 */
+    const double*  reports;       /* DEVICE, round after round, each N_b x E_b row-major      */
+    const double*  reputation;    /* DEVICE [sum N_b] or NULL (uniform)                       */
+    const uint8_t* scaled;        /* DEVICE [sum E_b] or NULL (event_bounds None), with lo/hi */
+    const double  *lo, *hi;
+    int32_t int_dtype, algorithm;
+    double  catch_tolerance, alpha;
+    int32_t max_components;  double variance_threshold;
+    const double* aux_scores;     /* cokurtosis: DEVICE [sum N_b]                             */
+    double  hierarchy_threshold, cluster_threshold;
+} pcx_ragged;
+
+/* Pure (no context, no device): validates the shapes and the algorithm of a ragged batch.
+ * totals = {sum N_b, sum E_b, sum N_b * E_b}, the lengths of the flat arrays; *lds_bytes = the
+ * launch's dynamic LDS (the largest round's).  On refusal returns PCX_EINVAL with *bad_round = the
+ * first offending round (-1: the algorithm); pcx_last_error names it.  Any output may be NULL. */
+int pcx_ragged_plan(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int algorithm,
+                    int64_t totals[3], int64_t* lds_bytes, int64_t* bad_round);
+/* The outputs are pcx_batch_result's: per-reporter arrays [sum N_b], per-event arrays [sum E_b],
+ * original / filled [sum N_b * E_b], the rest [B]; all in round order.  n_rounds == 0 succeeds and
+ * launches nothing.  On a pcx_create_devices context the call runs on device_ids[0]. */
+int pcx_consensus_ragged_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_result* out);
+
+/* ------------------------------------------------------------------------ */
 /* Monte Carlo simulator (ABI >= 9): the Simulator.jl-style driver of the       */
 /* batched regime (README.rst:52-56) on the device.  It draws random rounds     */
 /* with a counter-based generator (Philox4x32-10; DESIGN.md "Simulator" is the  */

@@ -68,6 +68,34 @@ def out_shape(kind, B, N, E):
     return {"N": (B, N), "E": (B, E), "1": (B,), "NE": (B, N, E)}[kind]
 
 
+class Ragged(C.Structure):
+    """pcx_ragged: B rounds of different shapes, their arrays laid end to end in round order."""
+    _fields_ = [
+        ("n_rounds", C.c_int64),
+        ("n_reporters", C.c_void_p),      # HOST int32 [B]
+        ("n_events", C.c_void_p),         # HOST int32 [B]
+        ("reports", C.c_void_p),
+        ("reputation", C.c_void_p),
+        ("scaled", C.c_void_p),
+        ("lo", C.c_void_p),
+        ("hi", C.c_void_p),
+        ("int_dtype", C.c_int32),
+        ("algorithm", C.c_int32),
+        ("catch_tolerance", C.c_double),
+        ("alpha", C.c_double),
+        ("max_components", C.c_int32),
+        ("variance_threshold", C.c_double),
+        ("aux_scores", C.c_void_p),
+        ("hierarchy_threshold", C.c_double),
+        ("cluster_threshold", C.c_double),
+    ]
+
+
+def ragged_out_len(kind, B, totals):
+    """Flat length of a ragged output; totals = (sum N_b, sum E_b, sum N_b * E_b)."""
+    return {"N": totals[0], "E": totals[1], "1": B, "NE": totals[2]}[kind]
+
+
 # ---------------------------------------------------------------- Monte Carlo simulator
 SIM_NMETRICS = 6                 # PCX_SIM_NMETRICS
 

@@ -77,8 +77,11 @@ def _declare(lib):
         ("pcx_sim_generate_f64", i32, [vp, C.POINTER(_abi.Sim), i32, C.POINTER(_abi.SimRounds)]),
         ("pcx_sim_metrics_f64", i32, [vp, C.POINTER(_abi.Sim), C.POINTER(_abi.SimRounds), vp, vp, vp, vp, vp]),
         ("pcx_simulate_f64", i32, [vp, C.POINTER(_abi.Sim), C.POINTER(_abi.SimResult)]),
+        ("pcx_ragged_plan", i32, [i64, vp, vp, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+        ("pcx_consensus_ragged_f64", i32, [vp, C.POINTER(_abi.Ragged), C.POINTER(_abi.BatchResult)]),
     ]:
-        if (name in ("pcx_batched_lds_bytes", "pcx_medium_lds_bytes", "pcx_batched_route")
+        if (name in ("pcx_batched_lds_bytes", "pcx_medium_lds_bytes", "pcx_batched_route", "pcx_ragged_plan",
+                     "pcx_consensus_ragged_f64")
                 and os.environ.get("PCX_LIB") and not hasattr(lib, name)):
             continue  # an A/B build of a revision before these queries (tools/ab_build.sh)
         f = getattr(lib, name)

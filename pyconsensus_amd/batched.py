@@ -8,6 +8,8 @@ Rounds of at most 64 reporters x 32 events run in one wavefront each of
 ``medium_round_kernel`` (csrc/pcx_medium.hip), every algorithm (k-means with up to 16 codes);
 larger rounds run as single-matrix consensuses, many in flight on a pool of worker streams
 (csrc/pcx_rounds.cpp).  :func:`route` tells which of the three a shape takes.
+Rounds of DIFFERENT shapes (each at most 64 x 32) run in one launch of the one-wave kernel through
+:func:`consensus_ragged`.
 """
 from __future__ import annotations
 
@@ -212,4 +214,154 @@ def unpack_round(out, b=0):
     g = {}
     for name, o, nb, dt, shape in out["_layout"]:
         g[name] = host[o:o + nb].view(np.float64 if dt == "f8" else np.int32).reshape(shape)[b]
+    return g
+
+
+# ---------------------------------------------------------------- ragged batches
+def _ragged_vectors(seq, counts, dtype, what):
+    """B vectors of lengths ``counts`` (or None) -> one flat array, round after round."""
+    if seq is None:
+        return None
+    if len(seq) != len(counts):
+        raise ValueError("%s must hold one vector per round (%d), got %d" % (what, len(counts), len(seq)))
+    parts = []
+    for b, (v, n) in enumerate(zip(seq, counts)):
+        v = np.asarray(v, dtype=dtype)
+        if v.ndim != 1 or v.shape[0] != n:
+            raise ValueError("%s[%d] must be a vector of length %d, got shape %s" % (what, b, n, v.shape))
+        parts.append(v)
+    return np.concatenate(parts) if parts else np.zeros(0, dtype=dtype)
+
+
+def ragged_plan(shapes, algorithm="PCA"):
+    """(totals, lds_bytes) of a ragged batch of ``shapes`` [(N_b, E_b), ...]: totals = (sum N_b,
+    sum E_b, sum N_b * E_b), the flat arrays' lengths, and the launch's dynamic LDS.  Needs no GPU;
+    raises PcxError naming the first round the one-wave kernel does not take (or k-means)."""
+    alg = _abi.ALGORITHMS.get(algorithm)
+    if alg is None:
+        raise NotImplementedError("algorithm %r is not on the GPU path" % (algorithm,))
+    sh = np.ascontiguousarray(np.asarray(shapes, dtype=np.int32).reshape(-1, 2))
+    n, e = np.ascontiguousarray(sh[:, 0]), np.ascontiguousarray(sh[:, 1])
+    totals, lds, bad = (C.c_int64 * 3)(), C.c_int64(0), C.c_int64(-1)
+    _lib.check(_lib.lib().pcx_ragged_plan(len(sh), n.ctypes.data, e.ctypes.data, alg, totals, C.byref(lds),
+                                          C.byref(bad)))
+    return tuple(int(x) for x in totals), int(lds.value)
+
+
+def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *, catch_tolerance=0.1, alpha=0.1,
+                     int_dtype=False, algorithm="PCA", outputs=None, device=None, filled=False, original=False,
+                     max_components=5, variance_threshold=0.9, aux_scores=None, hierarchy_threshold=0.5,
+                     cluster_threshold=None):
+    """Run B rounds of DIFFERENT shapes in one launch of the one-wave round kernel.
+
+    reports:    a sequence of B arrays, round b an (N_b, E_b) matrix with N_b <= 64, E_b <= 32
+    reputation: a sequence of B vectors (N_b,) or None (uniform in every round)
+    scaled/lo/hi: sequences of B vectors (E_b,) or None (every event binary)
+    aux_scores: cokurtosis: a sequence of B vectors (N_b,)
+    algorithm:  as :func:`consensus_batched` but "k-means" (its code-book size depends on N_b);
+                "big-five" caps max_components at E_b per round, "clusterfeck" takes the reference's
+                log10(E_b)/1.77 cut per round unless cluster_threshold is given
+
+    Each round is exactly its own ``Oracle(...).consensus()``: nothing is padded.  The inputs travel
+    to the device in one copy.  Returns flat device tensors named as in :func:`consensus_batched`,
+    every round's values end to end in round order (per-reporter outputs [sum N_b], per-event outputs
+    [sum E_b], ``original`` / ``filled`` [sum N_b * E_b], the rest [B]), all views of one device
+    buffer ``"_packed"``; ``"_shapes"`` (B, 2) and the int64 [B + 1] offsets ``"_reporter_offsets"``,
+    ``"_event_offsets"``, ``"_cell_offsets"``.  :func:`ragged_round` slices one round out;
+    :func:`ragged_to_host` brings everything back in one copy.  Asynchronous on torch's current
+    stream, like the one-wave regime of :func:`consensus_batched`."""
+    mats = []
+    for b, r in enumerate(reports):
+        r = np.asarray(r, dtype=np.float64)
+        if r.ndim != 2:
+            raise ValueError("reports[%d] must be an (N, E) matrix, got shape %s" % (b, r.shape))
+        mats.append(r)
+    B = len(mats)
+    shapes = np.array([m.shape for m in mats], dtype=np.int32).reshape(B, 2)
+    ns, es = np.ascontiguousarray(shapes[:, 0]), np.ascontiguousarray(shapes[:, 1])
+    rep = _ragged_vectors(reputation, ns, np.float64, "reputation")
+    if (scaled is None) != (lo is None) or (scaled is None) != (hi is None):
+        raise ValueError("scaled, lo and hi are given together or not at all")
+    sc = _ragged_vectors(scaled, es, np.uint8, "scaled")
+    lo_ = _ragged_vectors(lo, es, np.float64, "lo")
+    hi_ = _ragged_vectors(hi, es, np.float64, "hi")
+    alg = _abi.ALGORITHMS.get(algorithm)
+    if alg is None:
+        raise NotImplementedError("algorithm %r is not on the GPU path" % (algorithm,))
+    aux = None
+    if alg == _abi.ALG_COKURTOSIS:
+        if aux_scores is None:
+            raise ValueError("cokurtosis needs aux_scores (aux['cokurt'] of every round)")
+        aux = _ragged_vectors(aux_scores, ns, np.float64, "aux_scores")
+    totals, _ = ragged_plan(shapes, algorithm)  # refuses k-means and rounds above one wave, by index
+    t = _device.require_gpu()
+    dev = t.device(device) if device is not None else t.device("cuda", t.cuda.current_device())
+    flat = np.concatenate([m.reshape(-1) for m in mats]) if B else np.zeros(0)
+    R, rep_d, sc_d, lo_d, hi_d, aux_d = _upload_packed(
+        [(flat, np.float64), (rep, np.float64), (sc, np.uint8), (lo_, np.float64), (hi_, np.float64),
+         (aux, np.float64)], dev)
+    inp = _abi.Ragged(B, ns.ctypes.data, es.ctypes.data, _device.ptr(R), _device.ptr(rep_d), _device.ptr(sc_d),
+                      _device.ptr(lo_d), _device.ptr(hi_d), int(bool(int_dtype)), alg, float(catch_tolerance),
+                      float(alpha), int(max_components), float(variance_threshold), _device.ptr(aux_d),
+                      float(hierarchy_threshold), 0.0 if cluster_threshold is None else float(cluster_threshold))
+    res = _abi.BatchResult()
+    want = [(name, kind, dt) for name, kind, dt in _abi.BATCH_OUTPUTS
+            if not (name == "filled" and not filled or name == "original" and not original)
+            and not (outputs is not None and name not in outputs and name not in ("filled", "original"))]
+    layout, off = [], 0
+    for name, kind, dt in want:
+        n = _abi.ragged_out_len(kind, B, totals)
+        nb = n * (8 if dt == "f8" else 4)
+        layout.append((name, off, nb, dt, (n,)))
+        off += (nb + 15) // 16 * 16
+    buf = t.empty(max(off, 16), dtype=t.uint8, device=dev)
+    outs = {}
+    for name, o, nb, dt, shape in layout:
+        x = buf[o:o + nb].view(t.float64 if dt == "f8" else t.int32)
+        outs[name] = x
+        setattr(res, name, x.data_ptr())
+    h = _lib.bind_stream(dev.index, _device.current_stream_handle(dev))
+    _lib.check(_lib.lib().pcx_consensus_ragged_f64(h, C.byref(inp), C.byref(res)))
+    zero = np.zeros(1, dtype=np.int64)
+    outs["_packed"] = buf
+    outs["_layout"] = layout
+    outs["_shapes"] = shapes
+    outs["_reporter_offsets"] = np.concatenate([zero, np.cumsum(ns, dtype=np.int64)])
+    outs["_event_offsets"] = np.concatenate([zero, np.cumsum(es, dtype=np.int64)])
+    outs["_cell_offsets"] = np.concatenate([zero, np.cumsum(ns.astype(np.int64) * es, dtype=np.int64)])
+    outs["_inputs"] = (R, rep_d, sc_d, lo_d, hi_d, aux_d)  # keep inputs alive until the caller syncs
+    return outs
+
+
+_RAGGED_KIND = {name: kind for name, kind, _ in _abi.BATCH_OUTPUTS}
+
+
+def ragged_round(out, b):
+    """Round ``b`` of a :func:`consensus_ragged` (or :func:`ragged_to_host`) result: every output as
+    a view, ``original`` / ``filled`` reshaped to (N_b, E_b), the per-round scalars as 0-d views."""
+    N, E = (int(x) for x in out["_shapes"][b])
+    r0, e0, c0 = (int(out[k][b]) for k in ("_reporter_offsets", "_event_offsets", "_cell_offsets"))
+    g = {}
+    for name, v in out.items():
+        if name.startswith("_"):
+            continue
+        kind = _RAGGED_KIND[name]
+        if kind == "N":
+            g[name] = v[r0:r0 + N]
+        elif kind == "E":
+            g[name] = v[e0:e0 + E]
+        elif kind == "NE":
+            g[name] = v[c0:c0 + N * E].reshape(N, E)
+        else:
+            g[name] = v[b]
+    return g
+
+
+def ragged_to_host(out):
+    """A :func:`consensus_ragged` result as flat numpy arrays, from ONE device-to-host copy (which
+    waits for the launch); the shapes and offsets are carried over for :func:`ragged_round`."""
+    host = out["_packed"].cpu().numpy()
+    g = {k: out[k] for k in ("_shapes", "_reporter_offsets", "_event_offsets", "_cell_offsets")}
+    for name, o, nb, dt, shape in out["_layout"]:
+        g[name] = host[o:o + nb].view(np.float64 if dt == "f8" else np.int32)
     return g

@@ -181,6 +181,7 @@ int pcx_release_workspace(pcx_ctx* ctx) {
     pcx::workspace_free(ctx);
     pcx::io_bufs_free(ctx);
     pcx::sim_free(ctx);
+    pcx::ragged_free(ctx);
     return PCX_OK;
 }
 
@@ -211,6 +212,17 @@ void sim_free(pcx_ctx* c) {
     c->sim_buf = nullptr;
     c->sim_bytes = 0;
 }
+void ragged_free(pcx_ctx* c) {
+    for (auto& s : c->rag) {
+        if (s.copy_ev) (void)hipEventSynchronize(s.copy_ev);  // the upload may still read the staging
+        if (s.kern_ev) (void)hipEventSynchronize(s.kern_ev);  // the launch may still read the table
+        if (s.pin) (void)hipHostFree(s.pin);
+        if (s.dev) (void)hipFree(s.dev);
+        if (s.copy_ev) (void)hipEventDestroy(s.copy_ev);
+        if (s.kern_ev) (void)hipEventDestroy(s.kern_ev);
+        s = pcx_ctx::RaggedSlot();
+    }
+}
 void io_bufs_free(pcx_ctx* c) {
     for (auto& b : c->io_bufs)
         if (b.first) (void)hipFree(b.first);
@@ -228,6 +240,7 @@ void pcx_destroy(pcx_ctx* ctx) {
     pcx::ctx_host_free(ctx);
     pcx::workspace_free(ctx);
     pcx::sim_free(ctx);
+    pcx::ragged_free(ctx);
     delete ctx->comm;
     delete ctx;
 }
@@ -443,6 +456,156 @@ int pcx_consensus_batched_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_resul
         fprintf(stderr, " median_sort:%.0f median_walk:%.0f\n", sort / (double)a.B, walk / (double)a.B);
     }
     return e == hipSuccess ? PCX_OK : hip_fail(e, "batched_round_kernel launch");
+}
+
+// ---------------------------------------------------------------- ragged batches
+int pcx_ragged_plan(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int algorithm,
+                    int64_t totals[3], int64_t* lds_bytes, int64_t* bad_round) {
+    if (bad_round) *bad_round = -1;
+    if (n_rounds < 0 || n_rounds > 0x7fffffff) return fail(PCX_EINVAL, "ragged: n_rounds must be in [0, 2^31)");
+    if (algorithm < PCX_ALG_PCA || algorithm > PCX_ALG_CLUSTERFECK)
+        return fail(PCX_EINVAL, "ragged: algorithm must be an enum pcx_algorithm value (0..7)");
+    if (algorithm == PCX_ALG_KMEANS)
+        return fail(PCX_EINVAL, "ragged: k-means is not supported (its code-book size depends on each round's N)");
+    if (n_rounds > 0 && (!n_reporters || !n_events)) return fail(PCX_EINVAL, "ragged: n_reporters / n_events is NULL");
+    int64_t tn = 0, te = 0, tc = 0;
+    size_t lds = 0;
+    for (int64_t b = 0; b < n_rounds; b++) {
+        const int32_t N = n_reporters[b], E = n_events[b];
+        if (N < 1 || N > 64 || E < 1 || E > 32) {
+            if (bad_round) *bad_round = b;
+            return fail(PCX_EINVAL, "ragged: round " + std::to_string(b) + " is " + std::to_string(N) + " x " +
+                                        std::to_string(E) + "; a round must be within [1, 64] x [1, 32]");
+        }
+        tn += N;
+        te += E;
+        tc += (int64_t)N * E;
+        lds = std::max(lds, pcx::ragged_lds_bytes(N, E, algorithm));
+    }
+    if (totals) {
+        totals[0] = tn;
+        totals[1] = te;
+        totals[2] = tc;
+    }
+    if (lds_bytes) *lds_bytes = (int64_t)lds;
+    return PCX_OK;
+}
+
+int pcx_consensus_ragged_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_result* out) {
+    if (!ctx || !in || !out) return fail(PCX_EINVAL, "pcx_consensus_ragged_f64: null argument");
+    int64_t lds = 0;
+    if (const int rc = pcx_ragged_plan(in->n_rounds, in->n_reporters, in->n_events, in->algorithm, nullptr, &lds,
+                                       nullptr))
+        return rc;
+    if (in->n_rounds == 0) return PCX_OK;
+    if (!in->reports) return fail(PCX_EINVAL, "ragged: reports is NULL");
+    if (in->scaled && (!in->lo || !in->hi)) return fail(PCX_EINVAL, "ragged: scaled given without lo/hi");
+    if (in->algorithm == PCX_ALG_HIERARCHICAL && std::isnan(in->hierarchy_threshold))
+        return fail(PCX_EINVAL, "ragged: hierarchy_threshold is NaN");
+    if (in->algorithm == PCX_ALG_BIG_FIVE && in->max_components < 1)  // (capped at E_b per round on the device)
+        return fail(PCX_EINVAL, "ragged: big-five needs max_components >= 1");
+    if (in->algorithm == PCX_ALG_FIXED_VARIANCE && !std::isfinite(in->variance_threshold))
+        return fail(PCX_EINVAL, "ragged: variance_threshold must be finite");
+    if (in->algorithm == PCX_ALG_COKURTOSIS && !in->aux_scores)
+        return fail(PCX_EINVAL, "ragged: cokurtosis needs aux_scores (aux[\"cokurt\"])");
+    if (!std::isfinite(in->catch_tolerance) || !std::isfinite(in->alpha))
+        return fail(PCX_EINVAL, "ragged: catch_tolerance/alpha must be finite");
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    // the descriptor table: built in this call's staging slot, uploaded on the stream
+    const int64_t B = in->n_rounds;
+    const size_t bytes = (size_t)B * sizeof(pcx::RaggedDesc);
+    pcx_ctx::RaggedSlot& s = ctx->rag[ctx->rag_next];
+    ctx->rag_next ^= 1;
+    if (s.used) {  // the slot's last upload has read the staging
+        e = hipEventSynchronize(s.copy_ev);
+        if (e != hipSuccess) return hip_fail(e, "ragged: hipEventSynchronize");
+    }
+    if (!s.copy_ev) {
+        e = hipEventCreateWithFlags(&s.copy_ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.kern_ev, hipEventDisableTiming);
+        if (e != hipSuccess) return hip_fail(e, "ragged: hipEventCreate");
+    }
+    if (s.bytes < bytes) {
+        if (s.used) {  // the slot's last launch has read the table
+            e = hipEventSynchronize(s.kern_ev);
+            if (e != hipSuccess) return hip_fail(e, "ragged: hipEventSynchronize");
+        }
+        if (s.pin) (void)hipHostFree(s.pin);
+        if (s.dev) (void)hipFree(s.dev);
+        s.pin = s.dev = nullptr;
+        s.bytes = 0;
+        s.used = false;
+        const size_t cap = std::max(bytes + bytes / 2, (size_t)4096);
+        e = hipHostMalloc(&s.pin, cap, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc(&s.dev, cap);
+        if (e != hipSuccess) {
+            if (s.pin) (void)hipHostFree(s.pin);
+            s.pin = nullptr;
+            return fail(e == hipErrorOutOfMemory ? PCX_ENOMEM : PCX_EHIP,
+                        std::string("ragged: descriptor table: ") + hipGetErrorString(e));
+        }
+        s.bytes = cap;
+    }
+    pcx::RaggedDesc* d = static_cast<pcx::RaggedDesc*>(s.pin);
+    int64_t cell = 0, row = 0, ev = 0;
+    for (int64_t b = 0; b < B; b++) {
+        const int32_t N = in->n_reporters[b], E = in->n_events[b];
+        d[b] = pcx::RaggedDesc{cell, row, ev, N, E};
+        cell += (int64_t)N * E;
+        row += N;
+        ev += E;
+    }
+    // (another stream's launch may still read this slot's table: the upload waits for it)
+    if (s.used) e = hipStreamWaitEvent(ctx->stream, s.kern_ev, 0);
+    if (e == hipSuccess) e = hipMemcpyAsync(s.dev, s.pin, bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(s.copy_ev, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "ragged: descriptor upload");
+    s.used = true;
+    pcx::BatchArgs a{};
+    a.B = B;
+    a.reports = in->reports;
+    a.reputation = in->reputation;
+    a.scaled = in->scaled;
+    a.lo = in->lo;
+    a.hi = in->hi;
+    a.int_dtype = in->int_dtype;
+    a.algorithm = in->algorithm;
+    a.max_components = in->max_components;
+    a.variance_threshold = in->variance_threshold;
+    a.aux_scores = in->aux_scores;
+    a.hierarchy_threshold = in->hierarchy_threshold;
+    a.cluster_threshold = in->cluster_threshold;
+    a.catch_tol = in->catch_tolerance;
+    a.alpha = in->alpha;
+    a.old_rep = out->old_rep;
+    a.this_rep = out->this_rep;
+    a.smooth_rep = out->smooth_rep;
+    a.scores = out->scores;
+    a.na_row = out->na_row;
+    a.participation_rows = out->participation_rows;
+    a.relative_part = out->relative_part;
+    a.reporter_bonus = out->reporter_bonus;
+    a.adj_first_loadings = out->adj_first_loadings;
+    a.outcomes_raw = out->outcomes_raw;
+    a.outcomes_adjusted = out->outcomes_adjusted;
+    a.outcomes_final = out->outcomes_final;
+    a.certainty = out->certainty;
+    a.consensus_reward = out->consensus_reward;
+    a.nas_filled = out->nas_filled;
+    a.participation_columns = out->participation_columns;
+    a.author_bonus = out->author_bonus;
+    a.participation = out->participation;
+    a.avg_certainty = out->avg_certainty;
+    a.branch = out->branch;
+    a.flags = out->flags;
+    a.pi_iters = out->pi_iters;
+    a.components = out->components;
+    a.original = out->original;
+    a.filled = out->filled;
+    e = pcx::launch_ragged(a, static_cast<const pcx::RaggedDesc*>(s.dev), (size_t)lds, ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(s.kern_ev, ctx->stream);
+    return e == hipSuccess ? PCX_OK : hip_fail(e, "ragged_round_kernel launch");
 }
 
 namespace {

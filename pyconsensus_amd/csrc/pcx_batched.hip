@@ -1466,820 +1466,20 @@ __host__ __device__ constexpr int compiled_es(int E) { return PCX_BATCHED_ES_EVE
 #define PCX_BATCHED_D12_ONE_PASS 1
 #endif
 
-// NT/ET > 0: the round shape is a compile-time constant (the Monte Carlo shapes the
-// launcher specialises, e.g. the 50 x 20 of config C3): every loop bound is known, so
-// the sequential column/row loops unroll and their LDS reads issue ahead of the
-// dependent adds.  NT = ET = 0: any N <= 64, E <= 32 at run time.  Same arithmetic.
-template <int NT, int ET, bool CLUS, bool PK>
-__global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) batched_round_kernel(BatchArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int N = NT > 0 ? NT : a.N, E = ET > 0 ? ET : a.E, ES = ET > 0 ? compiled_es(ET) : a.ES;
-    const int l = lane_id();
-    const int64_t b = blockIdx.x;
-    constexpr int NRM = NT > 0 ? NT : 64;  // median scratch rows
-    Smem S = carve(smem, N, E, ES, NRM, PK);
-    const bool row = l < N, col = l < E;
-    const int64_t bo = a.bounds_shared ? 0 : b * E;
-    const bool has_bounds = a.scaled != nullptr;
-
-    // The output pointers are read from the kernel-argument segment where they are used (scalar
-    // loads, the segment's address made opaque at each use): as fields of `a` all of them are
-    // fetched at kernel entry and held -- 60 scalar registers spilled to lanes until the epilogue.
-#if PCX_BATCHED_KERNARG_OUT
-    typedef const __attribute__((address_space(4))) BatchArgs* KernArgs;
-    auto out_args = [&]() -> KernArgs {
-        uint64_t p = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();  // `a` is the only argument: offset 0
-        asm volatile("" : "+s"(p));
-        return (KernArgs)p;
-    };
-#else
-    auto out_args = [&]() { return &a; };
-#endif
-
-    long long mprof[3] = {0, 0, 0};  // diagnostic: median sort / walk cycles (PCX_STAMPS)
-    STAMP(0);
-    // ---- load the round -------------------------------------------------
-    const double* Rg = a.reports + b * (int64_t)N * E;
-    bool scj = false;
-    double loj = 0.0, hij = 0.0;
-    if (col && has_bounds) {
-        scj = a.scaled[bo + l] != 0;
-        loj = a.lo[bo + l];
-        hij = a.hi[bo + l];
-    }
-    double raw = row && a.reputation ? a.reputation[b * N + l] : 0.0;
-    if constexpr (NT > 0 && ET > 0 && (NT * ET) % 2 == 0) {
-        // every 16-byte load of the round in flight at once, then the LDS scatter
-        constexpr int TOT2 = NT * ET / 2, NV = (TOT2 + W - 1) / W;
-        double2 v[NV];
-#pragma unroll
-        for (int q = 0; q < NV; q++)
-            if (l + W * q < TOT2) v[q] = reinterpret_cast<const double2*>(Rg)[l + W * q];
-#pragma unroll
-        for (int q = 0; q < NV; q++) {
-            const int idx = 2 * (l + W * q);
-            if (idx < NT * ET) {
-                const int i0 = idx / ET, j0 = idx - i0 * ET;
-                const int i1 = (idx + 1) / ET, j1 = idx + 1 - i1 * ET;
-                S.F[i0 * ES + j0] = v[q].x;
-                S.F[i1 * ES + j1] = v[q].y;
-            }
-        }
-    } else {
-        for (int idx = l; idx < N * E; idx += W) {
-            const int i = idx / E, j = idx - i * E;
-            S.F[i * ES + j] = Rg[idx];
-        }
-    }
-    const uint64_t scaled_mask = ballot(col && scj);
-
-    // ---- a1: reputation (__init__.py:138-146) -----------------------------
-    double rep;
-    if (a.reputation) {
-        const double tot = wave_pw_sum(raw, row);
-        rep = raw / tot;
-    } else {
-        rep = 1.0 / (double)N;
-    }
-    const double tok = trunc(rep * 1e6);
-    if (row) S.rep[l] = rep;
-    const double denom = tree_sum(row ? tok : 0.0) - 1.0;  // exact integer sum
-    wsync();
-
-    STAMP(1);
-    // ---- a2: rescale (:266-269) + NA masks (:278) -------------------------
-    // (the next column's value is loaded before this column's stores: a load after a store to
-    // the same LDS array would otherwise wait for it)
-    // per-lane counts, 7 bits each: row l's zeros (bits 0-7) and NaNs (8-15), column l's zeros (16-23)
-    uint32_t nacnt = 0;
-#if PCX_BATCHED_ROWMASKS
-    // Each row lane collects its own row's NaN / zero columns as bits of two 32-bit masks straight
-    // from the compares (E <= 32), and lane j takes column j's zero count when column j is visited,
-    // so a column's two ballots die with it.  (Summed from the ballots' bits instead, the whole
-    // accumulation sank to its first use after the certainty, and forty ballots waited for it in
-    // spilled scalar registers.)
-    // WALK: only a scaled column (a wave-uniform branch on scaled_mask) fetches its bounds and
-    // divides, and the lanes past the last row hold 1.0, neither NaN nor zero, so the compares are
-    // the ballots with no row mask applied.
-    constexpr bool WALK = PCX_BATCHED_RESCALE_WALK;
-    double xnext = row ? S.F[l * ES] : (WALK ? 1.0 : 0.0);
-    uint32_t nanb = 0, zerob = 0;
-    int zcol = 0;  // column l's zero count (lanes < E)
-    // (the compiled shapes' loop unrolled: left rolled, as the compiler leaves it with the
-    // scaled columns' branch inside, a column's load runs only one column ahead)
-#pragma unroll(ET > 0 ? ET : 1)
-    for (int j = 0; j < E; j++) {
-        const bool sc = (scaled_mask >> j) & 1;
-        double x = xnext;
-        if (j + 1 < E) xnext = row ? S.F[l * ES + j + 1] : (WALK ? 1.0 : 0.0);
-        if constexpr (WALK) {
-            if (sc) {  // wave-uniform
-                const double lo = bcast(loj, j), hi = bcast(hij, j);
-                if (row) {
-                    x = (x - lo) / (hi - lo);
-                    if (a.int_dtype) x = trunc(x);
-                    S.F[l * ES + j] = x;
-                }
-            }
-        } else {
-            const double lo = bcast(loj, j), hi = bcast(hij, j);
-            if (row && sc) {
-                x = (x - lo) / (hi - lo);
-                if (a.int_dtype) x = trunc(x);
-                S.F[l * ES + j] = x;
-            }
-        }
-        const bool xn = (WALK || row) && __builtin_isnan(x), xz = (WALK || row) && x == 0.0;
-        nanb |= xn ? 1u << j : 0u;
-        zerob |= xz ? 1u << j : 0u;
-        const uint64_t zm = ballot(xz), mm = ballot(xn) | zm;
-        zcol = l == j ? popc(zm) : zcol;
-        if (l == 0) S.miss[j] = mm;
-        // the three registers are formed here: without this the compiler sinks their updates to
-        // the first use again and keeps every column's compare masks alive for them
-        asm volatile("" : "+v"(nanb), "+v"(zerob), "+v"(zcol));
-    }
-    nacnt = (uint32_t)__popc(zerob) | ((uint32_t)__popc(nanb) << 8) | ((uint32_t)zcol << 16);
-#else
-    double xnext = row ? S.F[l * ES] : 0.0;
-    for (int j = 0; j < E; j++) {
-        const bool sc = (scaled_mask >> j) & 1;
-        const double lo = bcast(loj, j), hi = bcast(hij, j);
-        double x = xnext;
-        if (j + 1 < E) xnext = row ? S.F[l * ES + j + 1] : 0.0;
-        if (row) {
-            if (sc) {
-                x = (x - lo) / (hi - lo);
-                if (a.int_dtype) x = trunc(x);
-                S.F[l * ES + j] = x;
-            }
-        }
-        const uint64_t nm = ballot(row && __builtin_isnan(x));
-        const uint64_t zm = ballot(row && x == 0.0);
-        nacnt += (uint32_t)((zm >> l) & 1) + ((uint32_t)((nm >> l) & 1) << 8) + (l == j ? (uint32_t)popc(zm) << 16 : 0u);
-        if (l == 0) S.miss[j] = nm | zm;
-    }
-#endif
-    wsync();
-    // result["original"] (the rescaled reports), from LDS in row-major order: every store
-    // instruction writes 64 consecutive doubles (whole lines), not one column's 50 strided ones
-    if (double* const og = out_args()->original) round_to_global(og + b * (int64_t)N * E, S.F, N, E, ES, NT, ET);
-
-    STAMP(2);
-    // ---- a3: interpolation guesses (:284-313), column phase ----------------
-    uint64_t miss_j = 0;
-    if (col) miss_j = S.miss[l];
-    constexpr int RKW = (ET > 0 ? ET + 3 : EMAX) / 4;  // interpolation-median ranks, a byte per column
-    uint32_t rkq[RKW];
-#pragma unroll
-    for (int k = 0; k < RKW; k++) rkq[k] = 0;
-    uint32_t rk_valid = 0;
-    {
-        // tot: the SPEC's sequential sum of the present reputations (a missing row adds
-        // +0.0, which leaves a sum that starts at +0.0 unchanged).  A binary column's
-        // guess only matters through catch(): the sum of (rep/tot)*F is formed cheaply as
-        // (sum rep*F)/tot, and the SPEC's exact sequential sum is replayed only for a
-        // column whose cheap value lies within 1e-12 * sum|rep*F|/tot of a catch threshold
-        // (the two differ by at most ~2*(N+2) ulp of that magnitude), so the caught value
-        // is the SPEC's bit for bit.  Scaled columns only need tot here (the median).
-        constexpr int NR = NT > 0 ? NT : 64;
-        double tot = 0.0, sp = 0.0, sa = 0.0;
-#pragma unroll 10
-        for (int i = 0; i < NR; i++) {
-            if (i < N) {
-                const bool miss = (miss_j >> i) & 1;
-                const double re = miss ? 0.0 : S.rep[i];
-                const double f = miss ? 0.0 : S.F[i * ES + (col ? l : 0)];
-                tot = tot + re;
-                sp = fma(re, f, sp);
-                sa = fma(fabs(re), fabs(f), sa);
-            }
-        }
-        const double t_lo = 1.5 - a.catch_tol, t_hi = 1.5 + a.catch_tol;  // catch_() thresholds
-        const double accf = sp / tot, margin = 1e-12 * (sa / tot);
-        const bool binary_fill = col && miss_j && !scj;
-        const bool fast = tot > 0.0 && __builtin_isfinite(accf) && __builtin_isfinite(margin) &&
-                          fabs(accf - t_lo) > margin && fabs(accf - t_hi) > margin;
-        double acc = accf;
-        if (ballot(binary_fill && !fast)) {
-            double ex = 0.0;  // SPEC: sum of (rep/tot)*F over the present rows, in row order
-#pragma unroll
-            for (int i = 0; i < NR; i++) {
-                if (i < N) {
-                    const double t = (S.rep[i] / tot) * S.F[i * ES + (col ? l : 0)];
-                    ex = ((miss_j >> i) & 1) ? ex : ex + t;
-                }
-            }
-            if (!fast) acc = ex;
-        }
-        if (binary_fill) {
-            double g = catch_(acc, a.catch_tol);
-            if (a.int_dtype) g = trunc(g);
-            S.guess[l] = g;
-        }
-        if (col && miss_j) S.tot[l] = tot;  // the present-reputation total, for the median phase
-    }
-    wsync();
-    STAMP(13);
-    // scaled columns with missing reports: weighted median of the present values
-    {
-        uint64_t todo = ballot(col && scj && miss_j != 0);
-        // the (x, w) pairs of interpolation median j: present reports, rep / tot (:292-303);
-        // Wsum = weightedstats' sum(weights), sequential in row order (absent rows add +0.0,
-        // which leaves a sum from +0.0 unchanged)
-        auto pair_of = [&](int j, double& x, double& w, bool& present, double& Wsum) {
-            const uint64_t mj = S.miss[j];
-            present = row && !((mj >> l) & 1);
-            const double tot = S.tot[j];
-            x = row ? S.F[l * ES + j] : 0.0;
-            w = present ? S.rep[l] / tot : 0.0;
-            Wsum = 0.0;  // (formed inside the median only where a decision needs it: wlazy)
-        };
-        auto finish = [&](int j, double g) {
-            if (a.int_dtype) g = trunc(g);
-            if (l == 0) S.guess[j] = g;
-        };
-        // one median at a time: the scratch lives in M, dead until the covariance.  Each lane's
-        // rank among the present keys is kept (one byte per column) for the outcome median of the
-        // same column, whose keys are these plus the fill's (a8 below: no second rank loop)
-        while (todo) {
-            const int j = __builtin_ctzll(todo);
-            todo &= todo - 1;
-            double x0, w0, W0;
-            bool p0;
-            pair_of(j, x0, w0, p0, W0);
-            int rk = -1;
-            finish(j, wave_wmedian_rank<(NT > 0 ? NT : 64)>(x0, w0, p0, W0, N, S.M, a.stamps ? mprof : nullptr,
-                                                            false, 0, &rk, true));
-            if (ballot(rk >= 0)) {  // the rank loop ran (no dominant weight, no NaN)
-                rk_valid |= 1u << j;
-                const int sh = 8 * (j & 3);
-                rkq[j >> 2] = (rkq[j >> 2] & ~(0xffu << sh)) | ((uint32_t)(rk & 0xff) << sh);
-            }
-            wsync();
-        }
-    }
-    wsync();
-    STAMP(14);
-    // fill (row phase; the next column's masks and fill loaded ahead of this column's store)
-    if (row) {
-        uint64_t mn = S.miss[0];
-        double gn = S.guess[0];
-        for (int j = 0; j < E; j++) {
-            const uint64_t mj = mn;
-            const double g = gn;
-            if (j + 1 < E) {
-                mn = S.miss[j + 1];
-                gn = S.guess[j + 1];
-            }
-            if ((mj >> l) & 1) S.F[l * ES + j] = g;
-        }
-    }
-    wsync();
-    if (double* const fg = out_args()->filled) round_to_global(fg + b * (int64_t)N * E, S.F, N, E, ES, NT, ET);
-
-    STAMP(3);
-    // ---- old = rep . F (np.dot) -------------------------------------------
-    double oldj = col ? ob_vecmat(S.rep, S.F + l, ES, N, E, l) : 0.0;  // np.dot(rep, F) (:490)
-
-    double sc_i = 0.0, nc_i = 0.0, ld_j = 0.0;
-    int branch = 5, flags = 0, iters = 0, comps = -1;
-    const int alg = a.algorithm;
-    const bool clus = CLUS && alg >= 5;  // k-means / hierarchical / clusterfeck call wpca too (:393, :408, :422)
-    if (alg == 0 || alg == 2 || alg == 3 || clus) {  // wpca (:315-339): PCA, big-five, fixed-variance
-        // ---- a5: weighted mean, np.ma.average (:317-319) -------------------
-        const double den = wave_pw_sum(rep, row);
-        double muj = 0.0;
-        if (E == 1) {
-            const double p = row ? S.F[l * ES] * rep : 0.0;
-            const double acc = wave_pw_sum(p, row);
-            muj = acc / den;
-        } else if (col) {
-            double acc = S.F[l] * S.rep[0];
-            for (int i = 1; i < N; i++) acc = acc + S.F[i * ES + l] * S.rep[i];
-            muj = acc / den;
-        }
-        if constexpr (!PK) {  // (the clusterings and big-five read it from LDS)
-            wsync();
-            if (col) S.mu[l] = muj;
-            wsync();
-        }
-
-        STAMP(4);
-        // ---- a6: token-weighted covariance (:326), lower triangle ----------
-        // fp64 MFMA, lower tiles of the 2 x 2 grid: entry (j, k), j >= k, accumulates
-        // fma((F_ij - mu_j) * tok_i, F_ik - mu_k, acc) over i ascending -- the SPEC's
-        // chain bit for bit (rows past N and events past E are exact zero padding)
-        bool nonzero = false, finite = true;
-        {
-            constexpr int NR = NT > 0 ? NT : 64;
-            const int ml = l & 15, kq = l >> 4;
-            const bool two = E > 16;
-            const double m0 = __shfl(muj, ml), m1 = __shfl(muj, 16 + ml);  // column ml's / 16 + ml's mean
-            const double mu0 = ml < E ? m0 : 0.0, mu1 = 16 + ml < E ? m1 : 0.0;
-            d4v c00 = {0, 0, 0, 0}, c10 = {0, 0, 0, 0}, c11 = {0, 0, 0, 0};
-#pragma unroll
-            for (int i0 = 0; i0 < NR; i0 += 4) {
-                if (i0 < N) {
-                    const int i = i0 + kq;
-                    const bool ok = i < N;
-                    const double tk = ok ? trunc(S.rep[i] * 1e6) : 0.0;  // the integer tokens (a1)
-                    const bool v0 = ok && ml < E, v1 = ok && 16 + ml < E;
-                    const double d0 = v0 ? S.F[i * ES + ml] - mu0 : 0.0;
-                    const double d1 = v1 ? S.F[i * ES + 16 + ml] - mu1 : 0.0;
-                    const double a0 = v0 ? d0 * tk : 0.0, a1 = v1 ? d1 * tk : 0.0;
-                    c00 = mfma_f64(a0, d0, c00);
-                    if (two) {
-                        c10 = mfma_f64(a1, d0, c10);
-                        c11 = mfma_f64(a1, d1, c11);
-                    }
-                }
-            }
-            auto put = [&](int j, int k, double acc) {  // j >= k
-                const double c = acc / denom;
-                S.C[sym_at<PK>(j, k, ES)] = c;
-                if (!PK) {
-                    S.M[sym_at<PK>(j, k, ES)] = c;
-                    S.C[k * ES + j] = c;
-                    S.M[k * ES + j] = c;
-                }
-                nonzero |= c != 0.0;
-                finite &= __builtin_isfinite(c) != 0;
-            };
-            if constexpr (PK) wsync();  // packed C lies over rep, which the loop above read
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int j0 = kq + 4 * r, j1 = 16 + kq + 4 * r, k0 = ml, k1 = 16 + ml;
-                if (j0 < E && k0 <= j0) put(j0, k0, c00[r]);
-                if (j1 < E && k0 < E) put(j1, k0, c10[r]);
-                if (j1 < E && k1 <= j1) put(j1, k1, c11[r]);
-            }
-        }
-        const bool any_nz = ballot(nonzero) != 0;
-        const bool all_fin = ballot(!finite) == 0;
-        wsync();
-
-        STAMP(5);
-        // ---- a7: leading eigenvector by power iteration (:330-336) -------
-        double xv = 0.0;
-        if (!all_fin) {
-            xv = col ? 1.0 : 0.0;
-            flags |= 2;
-        } else if (!any_nz) {
-            xv = l == 0 ? 1.0 : 0.0;
-            flags |= 1;
-        } else {
-            // start: the column with the largest diagonal entry (first max; C is finite here)
-            const double dg = col ? S.C[sym_at<PK>(l, l, ES)] : -__builtin_inf();
-            const int kd = __builtin_ctzll(ballot(col && dg == wave_max(dg)));
-            double x0 = col ? S.C[sym_at<PK>(l, kd, ES)] : 0.0;
-            const double n0 = sqrt(tree_sum(x0 * x0));
-            xv = col ? x0 / n0 : 0.0;
-            // packed: M starts as C's operands and is squared in registers (the covariance
-            // accumulators cannot seed it: (d_j tok) d_k and (d_k tok) d_j round differently, and C
-            // is its lower triangle mirrored); the matrix-vector steps read M's triangle from C's
-            // place in LDS, and C's operands (creg) are written back for the polish steps
-            constexpr int NS = !PK ? 1 : ET > 0 ? (ET + 3) / 4 : EMAX / 4;
-            constexpr bool MVM = PK && PCX_BATCHED_MV_MFMA, MVL = PK && !PCX_BATCHED_MV_MFMA;
-            SymOps<NS> mreg, creg;
-            if constexpr (PK) load_sym_ops<NS>(S.C, E, mreg);
-            if constexpr (MVL) creg = mreg;
-            auto square = [&](bool in_loop) {
-                if constexpr (MVM) {
-                    square_scaled_reg<NS>(mreg, E);
-                } else if constexpr (MVL) {  // (M's triangle lies over C in LDS between the squarings)
-                    if (in_loop) load_sym_ops<NS>(S.C, E, mreg);
-                    square_scaled_reg<NS>(mreg, E);
-                    if (in_loop) store_sym_ops<NS>(S.C, E, mreg);
-                } else {
-                    square_scaled<PK>(S.M, ES, E);
-                }
-            };
-            auto step = [&](const double* Mlds, double x) {
-                if constexpr (MVM)
-                    return matvec_unit_reg<NS>(mreg, x, E);
-                else
-                    return matvec_unit<PK>(Mlds, ES, x, E);
-            };
-            int sqn = 0;
-            for (; sqn < PI_PRESQUARE; sqn++) square(false);
-            if constexpr (MVL) store_sym_ops<NS>(S.C, E, mreg);
-            int it = 0, since = 0;
-            for (;;) {
-                const double y = step(PK ? S.C : S.M, xv);
-                const double d = wave_max(col ? fabs(y - xv) : 0.0);
-                xv = y;
-                it++;
-                since++;
-                if (d <= PI_TOL) break;
-                if (it >= PI_MAXIT) {
-                    flags |= 4;
-                    break;
-                }
-                if (since >= PI_SQUARE_EVERY && sqn < PI_MAX_SQUARINGS) {
-                    square(true);
-                    sqn++;
-                    since = 0;
-                }
-            }
-            // the polish steps run on C itself
-            if constexpr (MVM) load_sym_ops<NS>(S.C, E, mreg);
-            if constexpr (MVL) store_sym_ops<NS>(S.C, E, creg);
-            for (int p = 0; p < PI_POLISH; p++) xv = step(S.C, xv);
-            // SPEC sign: first nonzero component negative; a unit vector e_k is +e_k
-            const uint64_t nzm = ballot(col && xv != 0.0);
-            if (nzm) {
-                const double xf = bcast(xv, __builtin_ctzll(nzm));
-                const bool neg = popc(nzm) == 1 ? xf < 0.0 : xf > 0.0;
-                if (neg) xv = -xv;
-            }
-            iters = it + PI_POLISH + sqn;
-        }
-        // loading = v / sqrt(sum(v**2)) with numpy's pairwise sum (:336)
-        const double nv = sqrt(wave_pw_sum(xv * xv, col));
-        ld_j = col ? xv / nv : 0.0;
-        wsync();
-        if (clus) {
-            // the loading only: scores stay zeros (:357)
-        } else if (alg == 0) {
-            // scores s = wcd . loading (:337), row phase (column j's mean and loading from lane j)
-            const int r = row ? l : 0;
-            double acc = 0.0;
-            for (int j = 0; j < E; j++) acc = fma(S.F[r * ES + j] - lane_value(muj, j), lane_value(ld_j, j), acc);
-            if (row) sc_i = acc;
-        } else if (flags & 2) {
-            sc_i = __builtin_nan("");  // the reference's second svd raises (:375, :431)
-        } else if constexpr (!PK) {  // (the packed layout is never launched for these)
-            // ---- big-five (:373-390) / fixed-variance (:429-451): net score =
-            // sum_c Sigma_c * (wcd . loading_c); Sigma, loadings from Jacobi (SPEC)
-            const double trace = wave_pw_sum(col ? S.C[l * ES + l] : 0.0, col);  // np.trace
-            wsync();
-            for (int o = l; o < E * E; o += W) {
-                const int j = o / E, k = o - j * E;
-                S.M[j * ES + k] = S.C[j * ES + k];
-            }
-            wsync();
-            jacobi_eig_wave(S.M, S.C, ES, E, S.x, S.ld);  // A in M; V overwrites C; x, ld are dead
-            const double sig = col ? fabs(S.M[l * ES + l]) : 0.0;
-            if (col) S.nv1[l] = sig;
-            wsync();
-            if (col) {  // order: descending Sigma, ties by index
-                int rk = 0;
-                for (int k = 0; k < E; k++) rk += (S.nv1[k] > sig) | ((S.nv1[k] == sig) & (k < l));
-                S.nv2[rk] = (double)l;
-            }
-            wsync();
-            const int kmax = alg == 2 ? a.max_components : E;
-            double net = 0.0, ve = 0.0;
-            int used = kmax;
-            for (int c = 0; c < kmax; c++) {
-                const int idx = (int)S.nv2[c];
-                const double sg = S.nv1[idx];
-                const double fl = S.C[idx] < 0.0 ? -1.0 : 1.0;  // loading *= -1 if loading[0] < 0
-                if (row) {
-                    double d = 0.0;
-                    for (int j = 0; j < E; j++) d = fma(S.F[l * ES + j] - S.mu[j], fl * S.C[j * ES + idx], d);
-                    net = net + sg * d;
-                }
-                if (alg == 3) {  // cumsum(Sigma / trace) >= threshold -> stop (:432, :448)
-                    ve = ve + sg / trace;
-                    if (ve >= a.variance_threshold) {
-                        used = c + 1;
-                        break;
-                    }
-                }
-            }
-            comps = alg == 3 ? used : -1;
-            sc_i = net;
-            wsync();
-        }
-    } else if (alg == 4) {  // cokurtosis: caller-supplied scores (:455-457)
-        sc_i = row ? a.aux_scores[b * N + l] : 0.0;
-    }
-    STAMP(6);
-    if constexpr (CLUS) {
-        if (clus) {
-            double* X = smem + smem_doubles(N, E, ES, NRM, PK);
-            if (alg == 6)
-                nc_i = hier_nc(S.F, S.mu, ES, N, E, a.hierarchy_threshold, reinterpret_cast<uint64_t*>(X));
-            else if (alg == 5)
-                nc_i = kmeans_nc(a, b, S.F, S.mu, ES, N, E, X);
-            else
-                nc_i = feck_nc(a, S.F, ES, N, E, rep, X);
-            wsync();
-        }
-    }
-    if (alg != 1 && !clus) {
-        // ---- a8/a9: nonconformity_rank (:487-500) / nonconformity (:475-485); the
-        // non-PCA algorithms call nonconformity directly (:389, :450, :456)
-        const bool any_nan = ballot(row && __builtin_isnan(sc_i)) != 0;
-        double mn = wave_max(row ? -sc_i : -__builtin_inf());
-        mn = -mn;
-        double mx = wave_max(row ? sc_i : -__builtin_inf());
-        if (any_nan) {
-            mn = __builtin_nan("");
-            mx = __builtin_nan("");
-        }
-        const double set1 = sc_i + fabs(mn);
-        const double set2 = sc_i - mx;
-        double a1 = fabs(set1), a2 = fabs(set2);
-        double S1 = wave_pw_sum(a1, row);
-        if (S1 == 0) {
-            a1 += 1.0;
-            S1 = wave_pw_sum(a1, row);
-        }
-        double S2 = wave_pw_sum(a2, row);
-        if (S2 == 0) {
-            a2 += 1.0;
-            S2 = wave_pw_sum(a2, row);
-        }
-        if (row) {
-            S.n1[l] = a1 / S1;
-            S.n2[l] = a2 / S2;
-        }
-        if (col) S.old[l] = oldj;
-        wsync();
-        double d1 = 0.0, d2 = 0.0;
-#if PCX_BATCHED_D12_ONE_PASS
-        {
-            // both products in one pass over the rows: lane j < E runs column j on n1, lane 32 + j
-            // the same column on n2 (E <= 32) -- one instruction stream, each lane its own vector
-            // and its column's own order (block, tail or ddot), then d2 moves down to lane j
-            const int jc = l & 31;
-            double d = 0.0;
-            if (jc < E) d = ob_vecmat(l < 32 ? S.n1 : S.n2, S.F + jc, ES, N, E, jc);  // np.dot(normalize(set), F) (:492)
-            const uint64_t du = (uint64_t)__double_as_longlong(d);
-            const int up = ((l + 32) & 63) << 2;
-            const uint32_t ulo = (uint32_t)__builtin_amdgcn_ds_bpermute(up, (int)(uint32_t)du);
-            const uint32_t uhi = (uint32_t)__builtin_amdgcn_ds_bpermute(up, (int)(uint32_t)(du >> 32));
-            if (col) {
-                d1 = d;
-                d2 = __longlong_as_double((long long)(((uint64_t)uhi << 32) | ulo));
-            }
-        }
-#endif
-        if (col) {
-#if !PCX_BATCHED_D12_ONE_PASS
-            d1 = ob_vecmat(S.n1, S.F + l, ES, N, E, l);  // np.dot(normalize(set1), F) (:492)
-            d2 = ob_vecmat(S.n2, S.F + l, ES, N, E, l);
-#endif
-            const double t = 0.01 * oldj;
-            S.nv1[l] = d1 + t;
-            S.nv2[l] = d2 + t;
-        }
-        wsync();
-        double ref = 0.0;  // non-PCA: straight to the continuous rule
-        if (alg == 0) {
-            const double r0 = rank_avg(S.old, E);
-            const double r1 = rank_avg(S.nv1, E);
-            const double r2 = rank_avg(S.nv2, E);
-            const double e1 = fabs(r1 - r0), e2 = fabs(r2 - r0);
-            ref = wave_pw_sum(e1, col) - wave_pw_sum(e2, col);
-        }
-        bool pick1;
-        if (ref == 0) {
-            const double q1 = d1 - oldj, q2 = d2 - oldj;
-            const double ref2 = wave_pw_sum(q1 * q1, col) - wave_pw_sum(q2 * q2, col);
-            pick1 = ref2 <= 0;
-            branch = pick1 ? 3 : 4;
-        } else {
-            pick1 = ref < 0;
-            branch = pick1 ? 1 : 2;
-        }
-        nc_i = pick1 ? set1 : set2;
-    }
-
-    STAMP(7);
-    // ---- a10: reputation update (:460-472) --------------------------------
-    const double meanrep = wave_pw_sum(rep, row) / (double)N;
-    double u = fabs(nc_i * (rep / meanrep));
-    double Su = wave_pw_sum(u, row);
-    // PCA: a NaN total leaves the reference's this_rep / smooth_rep fully MASKED (SPEC
-    // rep_masked: participation_columns, reporter_bonus and author_bonus are numpy.ma's data)
-    const bool rep_masked = alg == 0 && __builtin_isnan(Su);
-    if (Su == 0) {
-        u += 1.0;
-        Su = wave_pw_sum(u, row);
-    }
-    const double this_i = u / Su;
-    const double smooth_i = a.alpha * this_i + (1.0 - a.alpha) * rep;
-    wsync();
-    if (row) S.smooth[l] = smooth_i;
-    wsync();
-
-    STAMP(8);
-    // ---- a12/a13: outcomes (:510-538) -------------------------------------
-    // The compiled shapes load the scaled columns' bounds again here (L2 hits, in flight over the
-    // np.dot and the medians) instead of holding four registers since the rescale: under the
-    // 128-register budget the allocator otherwise spills them and reloads them per rescaled column.
-    double lo2 = NT > 0 ? 0.0 : loj, hi2 = NT > 0 ? 0.0 : hij;  // (read by scaled columns only)
-    if constexpr (NT > 0) {
-        if (col && scj) {
-            lo2 = a.lo[bo + l];
-            hi2 = a.hi[bo + l];
-        }
-    }
-    double rawj = col ? ob_vecmat(S.smooth, S.F + l, ES, N, E, l) : 0.0;  // np.dot(smooth_rep, F) (:510)
-    STAMP(15);
-    if (scaled_mask) {
-        const double Wsm = [&] {  // builtin sequential sum of smooth_rep (weightedstats)
-            double w = 0.0;
-            if (l == 0)
-                for (int i = 0; i < N; i++) w += S.smooth[i];
-            return bcast(w, 0);
-        }();
-        uint64_t todo = scaled_mask;
-        while (todo) {  // scratch in M, dead after the scores
-            const int j = __builtin_ctzll(todo);
-            todo &= todo - 1;
-            const double x0 = row ? S.F[l * ES + j] : 0.0;
-            // the filled column's keys are the interpolation median's (present rows) plus the
-            // fill's (missing rows, all equal): a present row's count of smaller keys is its
-            // recorded one plus the missing rows when the fill's key is below its own, a missing
-            // row's is the present keys below the fill's -- the same counts the loop would make
-            const bool reuse = (rk_valid >> j) & 1;
-            int rk = 0;
-            if (reuse) {
-                const uint64_t mj = S.miss[j];
-                const bool ms = (mj >> l) & 1;
-                const uint32_t key = key_hi32(x0);
-                const uint32_t kg = (uint32_t)__builtin_amdgcn_readlane((int)key, __builtin_ctzll(mj));
-                const int below = popc(ballot(row && !ms && key < kg));
-                const int own = (int)((rkq[j >> 2] >> (8 * (j & 3))) & 0xffu);
-                rk = ms ? below : own + (kg < key ? popc(mj) : 0);
-            }
-            const double m = wave_wmedian_rank<(NT > 0 ? NT : 64)>(x0, smooth_i, row, Wsm, N, S.M,
-                                                                   a.stamps ? mprof : nullptr, reuse, rk);
-            if (l == j) rawj = m;
-            wsync();
-        }
-    }
-    STAMP(16);
-    double adjj = 0.0, finj = 0.0;
-    if (col) {
-        if (scj) {
-            adjj = rawj;
-            finj = adjj * (hi2 - lo2);
-            finj = finj + lo2;
-        } else {
-            adjj = catch_(rawj, a.catch_tol);
-            finj = adjj;
-        }
-        S.adj[l] = adjj;
-    }
-    wsync();
-
-    STAMP(9);
-    // ---- a14: certainty (:540-546): pairwise sum of the matching smooth_rep --
-    // every column at once, one lane per column: the hit masks first (F is read for the
-    // last time), then each row lane scatters its smooth_rep into the compacted hit list of
-    // every column it matches (into F, dead from here on), then lane j runs numpy's pairwise
-    // add.reduce (n <= 128: eight strided accumulators, fixed tree, sequential tail) on
-    // its column's list
-    double certj = 0.0;
-    {
-        uint64_t* hitm = reinterpret_cast<uint64_t*>(S.M);  // [E]; M is dead after the medians
-        double fn = row ? S.F[l * ES] : 0.0, an = S.adj[0];  // (next column's loads ahead of this column's store)
-        for (int j = 0; j < E; j++) {
-            const double f = fn, av = an;
-            if (j + 1 < E) {
-                fn = row ? S.F[l * ES + j + 1] : 0.0;
-                an = S.adj[j + 1];
-            }
-            const uint64_t hm = ballot(row && f == av);
-            if (l == 0) hitm[j] = hm;
-        }
-        wsync();
-        const int NS = cert_stride(N, ES);  // odd stride: lane-per-column reads spread over the banks
-        double* comp = S.F;    // [E][NS]
-        for (int j = 0; j < E; j++) {
-            const uint64_t hm = hitm[j];
-            if ((hm >> l) & 1) comp[j * NS + mbcnt64(hm)] = smooth_i;
-        }
-        wsync();
-        if (col) {
-            constexpr int TMAX = (NT > 0 ? NT : 64) / 8;
-            const uint64_t hm = hitm[l];
-            const int n = popc(hm), T = n >> 3;
-            const double* c = comp + l * NS;
-            double res = 0.0;
-            if (T) {
-                double r[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) r[k] = c[k];
-#pragma unroll
-                for (int t = 1; t < TMAX; t++)
-                    if (t < T) {
-#pragma unroll
-                        for (int k = 0; k < 8; k++) r[k] = r[k] + c[8 * t + k];
-                    }
-                res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-            }
-            for (int q = 8 * T; q < n; q++) res = res + c[q];  // the tail (everything when n < 8)
-            certj = n ? res : (a.algorithm == 0 ? __builtin_nan("") : 0.0);
-        }
-    }
-    // normalize(certainty), mean(certainty)
-    double ac = fabs(certj);
-    double Sc = wave_pw_sum(ac, col);
-    if (Sc == 0) {
-        ac += 1.0;
-        Sc = wave_pw_sum(ac, col);
-    }
-    const double reward = ac / Sc;
-    const double avg_cert = wave_pw_sum(certj, col) / (double)E;
-
-    STAMP(10);
-    // ---- a15: participation and bonuses (:549-581) -------------------------
-    double pcj = 0.0, nzj = 0.0;
-    // every smooth_rep finite: a row with na = 0 adds p = x * 0 = +-0 and pe = +-0, which leave
-    // (s, c) bit for bit as they were (neither is ever -0.0), so only the missing rows are visited
-    const bool smooth_finite = !ballot(row && !__builtin_isfinite(smooth_i));
-    if (col) {
-        const uint64_t nam = S.miss[l];
-        // dot2(smooth, na) with na in {0,1}
-        double s = 0.0, c = 0.0;
-        auto step = [&](double x, double y) {
-            const double p = x * y;
-            const double pe = fma(x, y, -p);
-            const double t = s + p;
-            const double z = t - s;
-            const double se = (s - (t - z)) + (p - z);
-            s = t;
-            c = c + (pe + se);
-        };
-        if (smooth_finite) {
-            for (uint64_t mm = nam; mm; mm &= mm - 1) step(S.smooth[__builtin_ctzll(mm)], 1.0);
-        } else {
-            for (int i = 0; i < N; i++) step(S.smooth[i], ((nam >> i) & 1) ? 1.0 : 0.0);
-        }
-        pcj = 1.0 - (s + c);
-        nzj = (double)((nacnt >> 16) & 0xffu);
-    }
-    double narow = 0.0;
-    int nnan = 0;
-    if (row) {
-        narow = (double)(nacnt & 0xffu);
-        nnan = (int)((nacnt >> 8) & 0xffu);
-    }
-    const bool rowmasked = row && nnan == E;
-    const double pr = 1.0 - narow / (double)E;
-    const double pna = 1.0 - wave_pw_sum(pcj, col) / (double)E;
-    double ar = rowmasked ? 0.0 : fabs(pr);
-    double Sr = wave_pw_sum(ar, row);
-    if (Sr == 0) {
-        ar = rowmasked ? 0.0 : fabs(pr) + 1.0;
-        Sr = wave_pw_sum(ar, row);
-    }
-    const double rel = rowmasked ? fabs(pr) : ar / Sr;
-    double apc = fabs(pcj);
-    double Spc = wave_pw_sum(apc, col);
-    if (Spc == 0) {
-        apc += 1.0;
-        Spc = wave_pw_sum(apc, col);
-    }
-    const double relc = apc / Spc;
-
-    STAMP(11);
-    // ---- write the round ---------------------------------------------------
-    const auto oa = out_args();
-    if (row) {
-        const int64_t o = b * N + l;
-        if (oa->old_rep) oa->old_rep[o] = rep;
-        if (oa->this_rep) oa->this_rep[o] = this_i;
-        if (oa->smooth_rep) oa->smooth_rep[o] = smooth_i;
-        if (oa->scores) oa->scores[o] = sc_i;
-        if (oa->na_row) oa->na_row[o] = narow;
-        if (oa->participation_rows) oa->participation_rows[o] = pr;
-        if (oa->relative_part) oa->relative_part[o] = rel;
-        if (oa->reporter_bonus) oa->reporter_bonus[o] = (rowmasked || rep_masked) ? rel : rel * pna + smooth_i * (1.0 - pna);
-    }
-    if (col) {
-        const int64_t o = b * E + l;
-        if (oa->adj_first_loadings) oa->adj_first_loadings[o] = ld_j;
-        if (oa->outcomes_raw) oa->outcomes_raw[o] = rawj;
-        if (oa->outcomes_adjusted) oa->outcomes_adjusted[o] = adjj;
-        if (oa->outcomes_final) oa->outcomes_final[o] = finj;
-        if (oa->certainty) oa->certainty[o] = certj;
-        if (oa->consensus_reward) oa->consensus_reward[o] = reward;
-        if (oa->nas_filled) oa->nas_filled[o] = nzj;
-        if (oa->participation_columns) oa->participation_columns[o] = rep_masked ? 1.0 : pcj;
-        if (oa->author_bonus) oa->author_bonus[o] = rep_masked ? 1.0 : relc * pna + reward * (1.0 - pna);
-    }
-    if (l == 0) {
-        if (oa->participation) oa->participation[b] = 1.0 - pna;
-        if (oa->avg_certainty) oa->avg_certainty[b] = avg_cert;
-        if (oa->branch) oa->branch[b] = branch;
-        if (oa->flags) oa->flags[b] = flags;
-        if (oa->pi_iters) oa->pi_iters[b] = iters;
-        if (oa->components) oa->components[b] = comps;
-    }
-    STAMP(12);
-    if (a.stamps && threadIdx.x == 0) {
-        a.stamps[b * 32 + 20] = mprof[0];
-        a.stamps[b * 32 + 21] = mprof[1];
-    }
+// wave-uniform 64-bit value into scalar registers
+__device__ __forceinline__ int64_t uniform64(int64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
 }
+
+// the round kernel, under its two names (see pcx_batched_round.inc)
+#define PCX_ROUND_RAGGED 0
+#include "pcx_batched_round.inc"
+#undef PCX_ROUND_RAGGED
+#define PCX_ROUND_RAGGED 1
+#include "pcx_batched_round.inc"
+#undef PCX_ROUND_RAGGED
 
 // the launch's instantiation: <50, 20> for the C3 shape, else the dynamic one; packed
 // C / M unless the algorithm needs the Jacobi eigenpairs (big-five, fixed-variance) or
@@ -2322,6 +1522,32 @@ hipError_t launch_batched(const BatchArgs& a, hipStream_t stream) {
         hipLaunchKernelGGL((batched_round_kernel<0, 0, false, true>), grid, block, lds, stream, a);
     } else {
         hipLaunchKernelGGL((batched_round_kernel<0, 0, false, false>), grid, block, lds, stream, a);
+    }
+    return hipGetLastError();
+}
+
+// one N x E round on the generic instantiation (odd pitch, 64 median rows), with the clusterings' region
+size_t ragged_lds_bytes(int N, int E, int alg) {
+    const int ES = E | 1;
+    size_t d = smem_doubles(N, E, ES, 64, packed_alg(alg));
+    if (alg >= 5) d += (size_t)cluster_lds_doubles(N, E, ES);
+    return d * sizeof(double);
+}
+
+hipError_t launch_ragged(const BatchArgs& a, const RaggedDesc* desc, size_t lds, hipStream_t stream) {
+    if (a.B <= 0) return hipSuccess;
+    const dim3 grid((unsigned)a.B), block(64);
+    if (a.algorithm >= 5) {
+        static bool attr = [] {
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(&ragged_round_kernel<0, 0, true, false>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
+        }();
+        (void)attr;
+        hipLaunchKernelGGL((ragged_round_kernel<0, 0, true, false>), grid, block, lds, stream, a, desc);
+    } else if (packed_alg(a.algorithm)) {
+        hipLaunchKernelGGL((ragged_round_kernel<0, 0, false, true>), grid, block, lds, stream, a, desc);
+    } else {
+        hipLaunchKernelGGL((ragged_round_kernel<0, 0, false, false>), grid, block, lds, stream, a, desc);
     }
     return hipGetLastError();
 }

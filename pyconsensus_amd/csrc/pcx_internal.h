@@ -208,8 +208,24 @@ struct BatchArgs {
     long long* stamps;  // diagnostic phase clocks [B][16] (PCX_STAMPS), normally NULL
 };
 
+// One round of a ragged launch (rounds of different shapes in one launch of the one-wave round
+// kernel): where the round's cells, reporters and events start in the flat inputs and outputs, and
+// its shape.  The wave of round b reads entry b of a device table (wave-uniform, kept scalar).
+struct RaggedDesc {
+    int64_t cell;  // sum over earlier rounds of N * E: reports, original, filled
+    int64_t row;   // sum of N: reputation, aux_scores, the per-reporter outputs
+    int64_t ev;    // sum of E: scaled / lo / hi, the per-event outputs
+    int32_t N, E;
+};
+static_assert(sizeof(RaggedDesc) == 32, "ragged descriptor");
+
 size_t batched_lds_bytes(int N, int E, int algorithm);
 hipError_t launch_batched(const BatchArgs& a, hipStream_t stream);
+// ragged launch: BatchArgs.N / E / ES are ignored, round b's shape and offsets are desc[b]; the
+// generic instantiation's LDS of one N x E round (the clusterings' region included), and the launch
+// with `lds` = its maximum over the rounds.  k-means is not supported (the caller refuses it).
+size_t ragged_lds_bytes(int N, int E, int algorithm);
+hipError_t launch_ragged(const BatchArgs& a, const RaggedDesc* desc, size_t lds, hipStream_t stream);
 // rounds above one wavefront (N <= 256, E <= 64; every algorithm, k-means up to 16 codes): one
 // workgroup each.  Xscr: the clusterings' per-round N x E scratch (unused by the other algorithms).
 bool medium_fits(int N, int E, int algorithm, int kmeans_k);
@@ -387,6 +403,19 @@ struct pcx_ctx {
     // the simulator's work buffers (pcx_simulate_f64): one allocation, kept between calls
     void* sim_buf = nullptr;
     size_t sim_bytes = 0;
+    // ragged batches (pcx_consensus_ragged_f64): two slots, taken in turn, of a descriptor table on the
+    // device and the pinned staging it is uploaded from (both grown on demand, freed with the
+    // workspace).  copy_ev is recorded after the slot's upload: the host waits for it before it
+    // rewrites the staging.  kern_ev is recorded after the slot's launch: the next upload into the
+    // slot's device table waits for it on its stream (the caller may have changed streams).
+    struct RaggedSlot {
+        void* pin = nullptr;
+        void* dev = nullptr;
+        size_t bytes = 0;
+        hipEvent_t copy_ev = nullptr, kern_ev = nullptr;
+        bool used = false;
+    } rag[2];
+    int rag_next = 0;
 };
 
 namespace pcx {
@@ -406,4 +435,5 @@ void rounds_free(pcx_ctx* c);
 void ctx_host_free(pcx_ctx* c);
 void io_bufs_free(pcx_ctx* c);  // the host path's cached device copies (pcx_ctx.io_bufs)
 void sim_free(pcx_ctx* c);      // the simulator's work buffers (pcx_ctx.sim_buf)
+void ragged_free(pcx_ctx* c);   // the ragged batches' descriptor slots (pcx_ctx.rag)
 }  // namespace pcx

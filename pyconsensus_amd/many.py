@@ -1,0 +1,71 @@
+"""Many independent consensus problems of different shapes, in a few ragged launches.
+
+``consensus_many(problems)`` returns what ``[Oracle(**p).consensus() for p in problems]`` returns,
+but the problems of at most 64 reporters x 32 events run together on the one-wave round kernel
+(:func:`pyconsensus_amd.batched.consensus_ragged`): one launch and one copy back per group of
+problems that share the integer dtype, bounds given or not, and reputation given or not.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _abi
+from .batched import MAX_EVENTS, MAX_REPORTERS, consensus_ragged, ragged_round, ragged_to_host
+from .oracle import Oracle
+
+_SHARED = ("catch_tolerance", "alpha", "algorithm", "variance_threshold", "hierarchy_threshold", "device")
+
+
+def consensus_many(problems, **oracle_kwargs):
+    """Run every problem's ``Oracle(**problem, **oracle_kwargs).consensus()``.
+
+    problems: a sequence of dicts of Oracle constructor arguments (``reports``, ``event_bounds``,
+              ``reputation``, ``aux`` for cokurtosis, ...)
+    Returns the list of result dicts, in order; each equals that problem's own
+    ``Oracle(...).consensus()`` in values and container types (the dicts are built by the same code).
+    A problem above 64 x 32, and every problem under ``algorithm="k-means"`` (whose restarts draw from
+    numpy's global RandomState call by call), goes through ``Oracle`` itself, in list order."""
+    oracles = [Oracle(**p, **oracle_kwargs) for p in problems]
+    results = [None] * len(oracles)
+    groups, alone = {}, []
+    for i, (p, o) in enumerate(zip(problems, oracles)):
+        if o.algorithm not in _abi.ALGORITHMS:
+            raise NotImplementedError("algorithm %r is not on the GPU path (supported: %s)"
+                                      % (o.algorithm, ", ".join(sorted(_abi.ALGORITHMS))))
+        if (o.num_reports > MAX_REPORTERS or o.num_events > MAX_EVENTS or o.algorithm == "k-means"
+                or o.num_reports < 1 or o.num_events < 1 or o.devices is not None):
+            alone.append(i)
+            continue
+        # (the problems' own max_components: each Oracle holds it capped at its E already)
+        mc = p.get("max_components", oracle_kwargs.get("max_components", 5))
+        key = (o._int_dtype, o.event_bounds is not None, o._rep_raw is not None, mc) + tuple(
+            getattr(o, k) for k in _SHARED)
+        groups.setdefault(key, []).append(i)
+    for key, idx in groups.items():
+        first = oracles[idx[0]]
+        kw = {}
+        if first.event_bounds is not None:
+            bounds = [oracles[i]._bounds_arrays() for i in idx]
+            kw.update(scaled=[b[0] for b in bounds], lo=[b[1] for b in bounds], hi=[b[2] for b in bounds])
+        if first._rep_raw is not None:
+            kw["reputation"] = [oracles[i]._rep_raw for i in idx]
+        if first.algorithm == "cokurtosis":
+            aux = [np.asarray(oracles[i].aux["cokurt"], dtype=np.float64).ravel() for i in idx]  # :456
+            if any(a.size != oracles[i].num_reports for a, i in zip(aux, idx)):
+                raise ValueError("aux['cokurt'] must hold one score per reporter")
+            kw["aux_scores"] = aux
+        out = consensus_ragged([oracles[i]._data for i in idx], filled=True, original=True,
+                               int_dtype=first._int_dtype, algorithm=first.algorithm,
+                               catch_tolerance=first.catch_tolerance, alpha=first.alpha, max_components=key[3],
+                               variance_threshold=first.variance_threshold,
+                               hierarchy_threshold=first.hierarchy_threshold, device=first.device, **kw)
+        host = ragged_to_host(out)  # the group's one copy back
+        for b, i in enumerate(idx):
+            g = ragged_round(host, b)
+            o = oracles[i]
+            o.last_info = {"branch": int(g["branch"]), "flags": int(g["flags"]), "pi_iters": int(g["pi_iters"]),
+                           "path": "ragged"}
+            results[i] = o._finish(g, float(g["participation"]), float(g["avg_certainty"]), int(g["components"]))
+    for i in alone:
+        results[i] = oracles[i].consensus()
+    return results

@@ -267,15 +267,7 @@ class Oracle(object):
                               "grid_events": meta["grid_events"], "mixed_int8": meta["mixed_int8"],
                               "cov_guard": meta["cov_guard"], "cov_guard_cols": meta["cov_guard_cols"],
                               "cov_err_bound": meta["cov_err_bound"]}
-        if self.algorithm in ("big-five", "fixed-variance") and self.last_info["flags"] & _abi.FLAG_SVD_FAIL:
-            # the reference's second svd (:375, :431) is outside the try of :329-333
-            raise np.linalg.LinAlgError("SVD did not converge (non-finite covariance)")
-        if self.algorithm == "fixed-variance":
-            self.num_components = comps  # :449
-        self.convergence = self.algorithm != "absolute"  # nonconformity(_rank) / the clusterings set it
-        if self.algorithm == "clusterfeck":  # cluster() rewrites zero tokens in the caller's list (:202-204)
-            self.reptokens = [0.00001 if t == 0 else t for t in self.reptokens]
-        res = self._result(g, participation, avg_certainty)
+        res = self._finish(g, participation, avg_certainty, comps)
         t4 = time.perf_counter()
         # per-call host timing (bench.py's c1 / c2 entries): argument preparation, the GPU call
         # (batched: inputs to the device, launch, kernel; matrix: the whole synchronous libpcx call),
@@ -285,6 +277,19 @@ class Oracle(object):
         if self.verbose:
             self._print_verbose(res)
         return res
+
+    def _finish(self, g, participation, avg_certainty, comps):
+        """The steps after the GPU call (``last_info`` is set): the attributes consensus() leaves on the
+        Oracle and the result dict.  Shared with :func:`pyconsensus_amd.consensus_many`."""
+        if self.algorithm in ("big-five", "fixed-variance") and self.last_info["flags"] & _abi.FLAG_SVD_FAIL:
+            # the reference's second svd (:375, :431) is outside the try of :329-333
+            raise np.linalg.LinAlgError("SVD did not converge (non-finite covariance)")
+        if self.algorithm == "fixed-variance":
+            self.num_components = comps  # :449
+        self.convergence = self.algorithm != "absolute"  # nonconformity(_rank) / the clusterings set it
+        if self.algorithm == "clusterfeck":  # cluster() rewrites zero tokens in the caller's list (:202-204)
+            self.reptokens = [0.00001 if t == 0 else t for t in self.reptokens]
+        return self._result(g, participation, avg_certainty)
 
     def _print_verbose(self, res):
         """The reference's verbose=True trace (:349-357, :363-365, :463-466, :552-572),
