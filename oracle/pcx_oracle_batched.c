@@ -196,12 +196,16 @@ static double wmedian(const double* x, const double* w, int n) {
     for (int i = 0; i < n; i++) pos |= w[i] > 0;
     if (!pos) return NAN;
     double xs[NMAX], ws[NMAX];
-    for (int i = 0; i < n; i++) {  /* stable rank by (x, w) */
+    /* stable rank by (x, w) in numpy's sort order (the restatement's np.lexsort((w, x))): a NaN
+     * after every number, NaNs equal among themselves -- a total order, so every slot is written */
+    for (int i = 0; i < n; i++) {
         int r = 0;
+        const int xin = isnan(x[i]), win = isnan(w[i]);
         for (int m = 0; m < n; m++) {
-            int lt = (x[m] < x[i]) || (x[m] == x[i] && w[m] < w[i]);
-            int eq = (x[m] == x[i]) && (w[m] == w[i]);
-            r += lt || (eq && m < i);
+            const int xmn = isnan(x[m]), wmn = isnan(w[m]);
+            int xlt = (x[m] < x[i]) || (xin && !xmn), xeq = (x[m] == x[i]) || (xin && xmn);
+            int wlt = (w[m] < w[i]) || (win && !wmn), weq = (w[m] == w[i]) || (win && wmn);
+            r += xlt || (xeq && (wlt || (weq && m < i)));
         }
         xs[r] = x[i];
         ws[r] = w[i];

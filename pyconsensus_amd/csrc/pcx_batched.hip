@@ -322,15 +322,18 @@ __device__ __noinline__ double wave_wmedian(double x, double w, bool sel, double
     }
     wsync();
     int r = 0;
-    if (sel) {  // stable rank by (x, w)
+    if (sel) {  // stable rank by (x, w) in numpy's sort order (the SPEC's): a NaN after every number,
+        // NaNs equal among themselves -- a total order, so the ranks fill slots 0 .. n - 1
+        const bool xin = __builtin_isnan(x), win = __builtin_isnan(w);
         uint64_t rest = selm;
         while (rest) {
             const int mrow = __builtin_ctzll(rest);
             rest &= rest - 1;
             const double xm = sx[mrow], wm = sw[mrow];
-            const bool lt = (xm < x) || (xm == x && wm < w);
-            const bool eq = (xm == x) && (wm == w);
-            r += (lt || (eq && mrow < l)) ? 1 : 0;
+            const bool xmn = __builtin_isnan(xm), wmn = __builtin_isnan(wm);
+            const bool xlt = (xm < x) || (xin && !xmn), xeq = (xm == x) || (xin && xmn);
+            const bool wlt = (wm < w) || (win && !wmn), weq = (wm == w) || (win && wmn);
+            r += (xlt || (xeq && (wlt || (weq && mrow < l)))) ? 1 : 0;
         }
     }
     wsync();

@@ -377,13 +377,17 @@ __device__ double wv_wmedian(const double* x, const double* w, int n, double* sb
             wi[q] = i < n ? w[i] : 0.0;
             rk[q] = 0;
         }
+        // (numpy's sort order, the SPEC's: a NaN after every number, NaNs equal among themselves;
+        // a total order, so the ranks are a permutation and every slot below n is written)
         auto cmp = [&](double xm, double wm, int m) {
+            const bool xmn = __builtin_isnan(xm), wmn = __builtin_isnan(wm);
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 if (q >= nq) break;  // wave-uniform
-                const bool lt = (xm < xi[q]) || (xm == xi[q] && wm < wi[q]);
-                const bool eq = (xm == xi[q]) && (wm == wi[q]);
-                rk[q] += (lt || (eq && m < lane + 64 * q)) ? 1 : 0;
+                const bool xin = __builtin_isnan(xi[q]), win = __builtin_isnan(wi[q]);
+                const bool xlt = (xm < xi[q]) || (xin && !xmn), xeq = (xm == xi[q]) || (xin && xmn);
+                const bool wlt = (wm < wi[q]) || (win && !wmn), weq = (wm == wi[q]) || (win && wmn);
+                rk[q] += (xlt || (xeq && (wlt || (weq && m < lane + 64 * q)))) ? 1 : 0;
             }
         };
         int m0 = 0;

@@ -44,15 +44,17 @@ def _dyadic_reputation(nb, N):
     return raw
 
 
-def side_rounds(N, E, seed=11):
-    """B hand-made rounds of one shape: inputs and the round indices of each kind."""
+def side_rounds(N, E, seed=11, nb=B):
+    """nb hand-made rounds of one shape (32 identical-reporter, 32 overflowing-bounds, the rest
+    degenerate-eigenvalue): inputs and the round indices of each kind."""
     rng = np.random.default_rng(seed)
     n_id, n_wide = 32, 32
-    n_deg = B - n_id - n_wide
-    sc = np.zeros((B, E), bool)
-    lo, hi = np.ones((B, E)), 2.0 * np.ones((B, E))
-    R = np.empty((B, N, E))
-    rep = np.empty((B, N))
+    n_deg = nb - n_id - n_wide
+    assert n_deg >= 2
+    sc = np.zeros((nb, E), bool)
+    lo, hi = np.ones((nb, E)), 2.0 * np.ones((nb, E))
+    R = np.empty((nb, N, E))
+    rep = np.empty((nb, N))
     # every reporter files the same row: each centred report is exactly zero
     ident = np.arange(0, n_id)
     R[ident] = np.repeat(rng.integers(1, 3, (n_id, 1, E)).astype(np.float64), N, axis=1)
@@ -67,7 +69,7 @@ def side_rounds(N, E, seed=11):
     rep[wide] = rng.integers(1, 100, (n_wide, N))
     # two pairs of identical columns, the pairs' patterns orthogonal: the covariance has two
     # leading eigenvalues that differ only through the reputations' imbalance
-    degen = np.arange(n_id + n_wide, B)
+    degen = np.arange(n_id + n_wide, nb)
     i = np.arange(N)
     R[degen] = 1.0
     R[degen, :, 0] = R[degen, :, 1] = 1.0 + (i % 2)
@@ -77,8 +79,9 @@ def side_rounds(N, E, seed=11):
     return R, dict(reputation=rep, scaled=sc, lo=lo, hi=hi), dict(ident=ident, wide=wide, degen=degen)
 
 
-def check_side_branches(c, kinds):
-    """The oracle itself took the branches the rounds were made for."""
+def check_side_branches(c, kinds, nb=B):
+    """The oracle itself took the branches the nb rounds were made for."""
+    assert len(c["flags"]) == nb == sum(len(v) for v in kinds.values())
     assert np.all(c["flags"][kinds["ident"]] & 1), "identical reporters: zero covariance expected"
     assert np.all(c["pi_iters"][kinds["ident"]] == 0)
     assert np.all(c["flags"][kinds["wide"]] & 2), "overflowing bounds: non-finite covariance expected"
@@ -117,6 +120,18 @@ def test_side_branches_bitexact(gpu_lib, shape):
     check_side_branches(c, kinds)
     g = _np(consensus_batched(R, filled=True, original=True, **kw))
     _assert_bitexact(g, c, shape)
+
+
+def test_side_batch_64x32_reaches_the_iteration_cap():
+    """The packed kernel's PI_MAXIT exit is compared by test_side_branches_bitexact[64x32]; this shows
+    that the batch reaches it: the SPEC stops some degenerate-eigenvalue rounds at the cap (24 of 256)."""
+    from oracle import pcx_oracle_c as OC
+    from pyconsensus_amd._abi import FLAG_PI_MAXIT
+
+    R, kw, kinds = side_rounds(64, 32)
+    c = OC.batched(R, **kw, threads=8)
+    capped = np.flatnonzero(c["flags"] & FLAG_PI_MAXIT)
+    assert len(capped) >= 1 and set(capped) <= set(kinds["degen"]), capped
 
 
 def _lds_bytes_lds_resident_m(N, E):
