@@ -50,6 +50,23 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x; }
 // slower (24.4 M vs 34.4 M rounds/s).
 #define PCX_OUTLINE __forceinline__
 
+// Build parameters of the live-lane steps (0 builds the form before each):
+#ifndef PCX_BATCHED_PI_BALLOT  // the power iteration's convergence test is a ballot, not a max reduction
+#define PCX_BATCHED_PI_BALLOT 1
+#endif
+#ifndef PCX_BATCHED_LIVE_ROWS  // column-phase tree_sum / wave_max of a compiled shape read E's 16-lane rows only
+#define PCX_BATCHED_LIVE_ROWS 1
+#endif
+#ifndef PCX_BATCHED_PW_PREFIX  // wave_pw_sum over the prefixes l < N, l < E: no ballot, no lane counts
+#define PCX_BATCHED_PW_PREFIX 1
+#endif
+#ifndef PCX_BATCHED_REPSUM_ONCE  // the pairwise sum of rep is formed once for a5 (den) and a10 (meanrep)
+#define PCX_BATCHED_REPSUM_ONCE 1
+#endif
+#ifndef PCX_BATCHED_RANK3  // 3 E <= 64: the rankings of old, nv1 and nv2 in one pass on three lane groups
+#define PCX_BATCHED_RANK3 1
+#endif
+
 // diagnostic phase stamps (PCX_STAMPS=1): shader-clock reads at phase boundaries
 #define STAMP(k)                                                                  \
     do {                                                                          \
@@ -114,13 +131,22 @@ __device__ __forceinline__ double lane_value(double v, int k) {  // lane k's v (
 
 // SPEC tree64: a butterfly inside each 16-lane row (xor 1, 2, 4, 8: every lane of a row
 // ends with the same row sum R_r), then (R0 + R1) + (R2 + R3) from lanes 0, 16, 32, 48
+// ROWS < 4: the caller's lanes from 16 * ROWS on hold +0.0 and no row sum is -0.0 (squares, say),
+// so the dead rows' sums are +0.0 and adding them changes no bit: R0 + 0 = R0 unless R0 is -0.0.
+// The dead rows' readlanes and adds are left out.
+template <int ROWS = 4>
 __device__ __forceinline__ double tree_sum(double v) {
+    static_assert(ROWS == 1 || ROWS == 2 || ROWS == 4, "live 16-lane rows");
     v = v + xor_lane<1>(v);
     v = v + xor_lane<2>(v);
     v = v + xor_lane<4>(v);
     v = v + xor_lane<8>(v);
+    if constexpr (ROWS == 1) return lane_value(v, 0);
+    if constexpr (ROWS == 2) return lane_value(v, 0) + lane_value(v, 16);
     return (lane_value(v, 0) + lane_value(v, 16)) + (lane_value(v, 32) + lane_value(v, 48));
 }
+// the live rows of a column-phase value (lanes >= E are padding) of a compiled shape
+constexpr int live_rows(int ET) { return PCX_BATCHED_LIVE_ROWS && ET > 0 ? (ET <= 16 ? 1 : ET <= 32 ? 2 : 4) : 4; }
 
 // inclusive prefix sum over the lanes in lane order (row_shr DPP inside each 16-lane row, then the
 // rows' totals by readlane): a fixed tree order, deterministic, within ~6 u of the exact sums
@@ -142,11 +168,17 @@ __device__ __forceinline__ double wave_scan_d(double v) {
     return row == 0 ? v : v + (row == 1 ? r0 : row == 2 ? r01 : r01 + r2);
 }
 
+// ROWS < 4: the lanes from 16 * ROWS on hold the caller's pad (-inf, or 0.0 under values >= 0), which
+// a live row's maximum already includes or exceeds: leaving the dead rows out is exact.
+template <int ROWS = 4>
 __device__ __forceinline__ double wave_max(double v) {
+    static_assert(ROWS == 1 || ROWS == 2 || ROWS == 4, "live 16-lane rows");
     v = fmax(v, xor_lane<1>(v));
     v = fmax(v, xor_lane<2>(v));
     v = fmax(v, xor_lane<4>(v));
     v = fmax(v, xor_lane<8>(v));
+    if constexpr (ROWS == 1) return lane_value(v, 0);
+    if constexpr (ROWS == 2) return fmax(lane_value(v, 0), lane_value(v, 16));
     return fmax(fmax(lane_value(v, 0), lane_value(v, 16)), fmax(lane_value(v, 32), lane_value(v, 48)));
 }
 
@@ -174,6 +206,13 @@ __device__ __forceinline__ double permute_d(int dst_lane, double v) {  // forwar
     const uint64_t u = (uint64_t)__double_as_longlong(v);
     const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_permute(dst_lane * 4, (int)(uint32_t)u);
     const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_permute(dst_lane * 4, (int)(uint32_t)(u >> 32));
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
+__device__ __forceinline__ double bpermute_d(int src_lane, double v) {  // lane l <- lane src_lane's v
+    const uint64_t u = (uint64_t)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane * 4, (int)(uint32_t)u);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane * 4, (int)(uint32_t)(u >> 32));
     return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
 
@@ -205,6 +244,37 @@ __device__ PCX_OUTLINE double wave_pw_sum(double v, bool sel) {
     const int p = sel ? mbcnt64(m) : n + mbcnt64(~m);
     const double a = permute_d((p & 7) * 8 + (p >> 3), v);
     const int T = n >> 3;  // full rounds of 8: positions < 8T feed the accumulators
+    double c = a;
+    for (int t = 1; t < T; t++) {
+        const double prev = shr1_d(c);
+        c = (l & 7) == 0 ? a : prev + a;
+    }
+    const double r0 = readlane_d(c, 0 * 8 + T - 1), r1 = readlane_d(c, 1 * 8 + T - 1);
+    const double r2 = readlane_d(c, 2 * 8 + T - 1), r3 = readlane_d(c, 3 * 8 + T - 1);
+    const double r4 = readlane_d(c, 4 * 8 + T - 1), r5 = readlane_d(c, 5 * 8 + T - 1);
+    const double r6 = readlane_d(c, 6 * 8 + T - 1), r7 = readlane_d(c, 7 * 8 + T - 1);
+    double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
+    for (int q = 8 * T; q < n; q++) res += readlane_d(a, (q & 7) * 8 + (q >> 3));
+    return res;
+}
+
+// wave_pw_sum(v, l < n): the selected lanes are a prefix, so the p-th selected lane is lane p and
+// an unselected lane's place n + (l - n) is its own too -- the permute address is an expression of
+// the lane alone, with no ballot and no lane counts.  NC > 0: n = NC at compile time, so the n < 8
+// branch is decided, the accumulator chain unrolls (T - 1 steps) and the accumulators' and the
+// tail's lanes are constants.  NC = 0: n = nrt, wave-uniform.  The additions and their order are
+// wave_pw_sum's: eight strided accumulators, the fixed tree, the sequential tail.
+template <int NC>
+__device__ PCX_OUTLINE double wave_pw_sum_prefix(double v, int nrt) {
+    const int l = lane_id();
+    const int n = NC > 0 ? NC : nrt;
+    if (n < 8) {
+        double res = 0.0;
+        for (int k = 0; k < n; k++) res += readlane_d(v, k);
+        return res;
+    }
+    const double a = permute_d((l & 7) * 8 + (l >> 3), v);
+    const int T = n >> 3;
     double c = a;
     for (int t = 1; t < T; t++) {
         const double prev = shr1_d(c);
@@ -623,6 +693,32 @@ __device__ PCX_OUTLINE double rank_avg(const double* v, int E) {
     return r;
 }
 
+// rank_avg of three vectors in one pass, 3 E <= 64: lane g * E + j ranks entry j of vector g with
+// rank_avg's loop and NaN rule, every lane on its own base pointer; r0 is left on lanes [0, E) and
+// r1, r2 come down to them by ds_bpermute (lane j + 2 E < 64).  The lanes from E on return values
+// nobody reads.
+__device__ PCX_OUTLINE void rank_avg3(const double* v0, const double* v1, const double* v2, int E, double& r0,
+                                      double& r1, double& r2) {
+    const int l = lane_id();
+    const int g = (l >= E) + (l >= 2 * E);
+    const double* v = g == 0 ? v0 : g == 1 ? v1 : v2;
+    double r = 0.0;
+    if (l < 3 * E) {
+        const double x = v[l - g * E];
+        int lt = 0, eq = 0;
+        for (int k = 0; k < E; k++) {
+            const double y = v[k];
+            lt += y < x;
+            eq += y == x;
+        }
+        r = (double)lt + (double)(eq + 1) * 0.5;
+        if (__builtin_isnan(x)) r = __builtin_nan("");
+    }
+    r0 = r;
+    r1 = bpermute_d(l + E, r);
+    r2 = bpermute_d(l + 2 * E, r);
+}
+
 struct Smem {
     double* F;      // [N][ES] rescaled, then filled reports
     double* C;      // [E][ES] covariance (phase aliases: see carve; packed: runs on into M's region)
@@ -753,13 +849,13 @@ __device__ Smem carve(double* base, int N, int E, int ES, int NR, bool pk) {
 }
 
 // y = normalize(M x) for lane j < E, x_k on lane k; returns y_j (0 on other lanes)
-template <bool PK>
+template <bool PK, int ROWS = 4>
 __device__ PCX_OUTLINE double matvec_unit(const double* M, int ES, double xv, int E) {
     const int l = lane_id(), r = l < E ? l : 0;  // (every lane runs the chain: readlane is wave-wide)
     double acc = 0.0;
     for (int k = 0; k < E; k++) acc = fma(M[sym_at<PK>(r, k, ES)], lane_value(xv, k), acc);
     const double y = l < E ? acc : 0.0;
-    const double nrm = sqrt(tree_sum(l < E ? y * y : 0.0));
+    const double nrm = sqrt(tree_sum<ROWS>(l < E ? y * y : 0.0));  // squares: no row sum is -0.0
     return l < E ? y / nrm : 0.0;
 }
 
@@ -839,13 +935,6 @@ struct SymOps {
 #ifndef PCX_BATCHED_MV_MFMA  // 1: the matrix-vector steps by MFMA from the operand registers; 0: matvec_unit
 #define PCX_BATCHED_MV_MFMA 0  // on the packed triangle written over C (C's operands wait in registers)
 #endif
-
-__device__ __forceinline__ double bpermute_d(int src_lane, double v) {  // lane l <- lane src_lane's v
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane * 4, (int)(uint32_t)u);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane * 4, (int)(uint32_t)(u >> 32));
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
 
 // the operands of the packed lower triangle C in LDS (the reads square_scaled<true> makes)
 template <int NS>
@@ -950,7 +1039,7 @@ __device__ PCX_OUTLINE void square_scaled_reg(SymOps<NS>& m, int E) {
 // leaves y_j = fma(x_k, M[j][k], acc) over k ascending from +0 -- matvec_unit's chain, the
 // product commuted -- in every accumulator of lane (ml = j, any kq): lane l < 16 reads its y
 // from row tile 0, lane 16 + ml (kq = 1) from row tile 1.  x_{4s + kq} comes by ds_bpermute.
-template <int NS>
+template <int NS, int ROWS = 4>
 __device__ PCX_OUTLINE double matvec_unit_reg(const SymOps<NS>& m, double xv, int E) {
     const int l = lane_id(), kq = l >> 4;
     const bool two = E > 16;
@@ -965,7 +1054,7 @@ __device__ PCX_OUTLINE double matvec_unit_reg(const SymOps<NS>& m, double xv, in
     }
     const double acc = l < 16 ? y0[0] : y1[0];
     const double y = l < E ? acc : 0.0;
-    const double nrm = sqrt(tree_sum(l < E ? y * y : 0.0));
+    const double nrm = sqrt(tree_sum<ROWS>(l < E ? y * y : 0.0));  // squares: no row sum is -0.0
     return l < E ? y / nrm : 0.0;
 }
 

@@ -42,6 +42,23 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
     const bool row = l < N, col = l < E;
     const int64_t bo = a.bounds_shared ? 0 : PCX_ROUND_EV0;
     const bool has_bounds = a.scaled != nullptr;
+    // numpy's pairwise sum over the reporters' / the events' lanes: both are prefixes of the wave
+    // (of compile-time length in a compiled shape), see wave_pw_sum_prefix
+    auto pw_rows = [&](double v) {
+#if PCX_BATCHED_PW_PREFIX
+        return wave_pw_sum_prefix<NT>(v, N);
+#else
+        return wave_pw_sum(v, row);
+#endif
+    };
+    auto pw_cols = [&](double v) {
+#if PCX_BATCHED_PW_PREFIX
+        return wave_pw_sum_prefix<ET>(v, E);
+#else
+        return wave_pw_sum(v, col);
+#endif
+    };
+    constexpr int CR = live_rows(ET);  // 16-lane rows that hold events (a compiled shape's; else all four)
 
     // The output pointers are read from the kernel-argument segment where they are used (scalar
     // loads, the segment's address made opaque at each use): as fields of `a` all of them are
@@ -97,7 +114,7 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
     // ---- a1: reputation (__init__.py:138-146) -----------------------------
     double rep;
     if (a.reputation) {
-        const double tot = wave_pw_sum(raw, row);
+        const double tot = pw_rows(raw);
         rep = raw / tot;
     } else {
         rep = 1.0 / (double)N;
@@ -307,13 +324,22 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
     int branch = 5, flags = 0, iters = 0, comps = -1;
     const int alg = a.algorithm;
     const bool clus = CLUS && alg >= 5;  // k-means / hierarchical / clusterfeck call wpca too (:393, :408, :422)
+#if PCX_BATCHED_REPSUM_ONCE
+    // sum(rep), numpy's pairwise: the weighted mean's denominator (a5) and mean(rep) (a10) are the
+    // same sum of the same operands, formed here once for both
+    const double rep_sum = pw_rows(rep);
+#endif
     if (alg == 0 || alg == 2 || alg == 3 || clus) {  // wpca (:315-339): PCA, big-five, fixed-variance
         // ---- a5: weighted mean, np.ma.average (:317-319) -------------------
-        const double den = wave_pw_sum(rep, row);
+#if PCX_BATCHED_REPSUM_ONCE
+        const double den = rep_sum;
+#else
+        const double den = pw_rows(rep);
+#endif
         double muj = 0.0;
         if (E == 1) {
             const double p = row ? S.F[l * ES] * rep : 0.0;
-            const double acc = wave_pw_sum(p, row);
+            const double acc = pw_rows(p);
             muj = acc / den;
         } else if (col) {
             double acc = S.F[l] * S.rep[0];
@@ -392,9 +418,10 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
         } else {
             // start: the column with the largest diagonal entry (first max; C is finite here)
             const double dg = col ? S.C[sym_at<PK>(l, l, ES)] : -__builtin_inf();
-            const int kd = __builtin_ctzll(ballot(col && dg == wave_max(dg)));
+            // (the lanes from E on hold -inf, below every finite entry: live rows only)
+            const int kd = __builtin_ctzll(ballot(col && dg == wave_max<CR>(dg)));
             double x0 = col ? S.C[sym_at<PK>(l, kd, ES)] : 0.0;
-            const double n0 = sqrt(tree_sum(x0 * x0));
+            const double n0 = sqrt(tree_sum<CR>(x0 * x0));  // squares, +0.0 from lane E on: no row sum is -0.0
             xv = col ? x0 / n0 : 0.0;
             // packed: M starts as C's operands and is squared in registers (the covariance
             // accumulators cannot seed it: (d_j tok) d_k and (d_k tok) d_j round differently, and C
@@ -418,9 +445,9 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
             };
             auto step = [&](const double* Mlds, double x) {
                 if constexpr (MVM)
-                    return matvec_unit_reg<NS>(mreg, x, E);
+                    return matvec_unit_reg<NS, CR>(mreg, x, E);
                 else
-                    return matvec_unit<PK>(Mlds, ES, x, E);
+                    return matvec_unit<PK, CR>(Mlds, ES, x, E);
             };
             int sqn = 0;
             for (; sqn < PI_PRESQUARE; sqn++) square(false);
@@ -428,11 +455,21 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
             int it = 0, since = 0;
             for (;;) {
                 const double y = step(PK ? S.C : S.M, xv);
-                const double d = wave_max(col ? fabs(y - xv) : 0.0);
+#if PCX_BATCHED_PI_BALLOT
+                // SPEC: d = max over the events of |y - x|, stop when d <= PI_TOL.  Only the compare
+                // is used, and d <= PI_TOL holds exactly when no event lane has |y - x| > PI_TOL:
+                // the maximum (v_max_f64) drops a NaN operand and the lanes from E on feed 0.0, so a
+                // NaN difference never reaches d, just as `NaN > PI_TOL` is false for it (all of
+                // them NaN: d = 0.0, the loop stops, and so does this); an infinite difference makes
+                // d infinite and the compare true, and the loop goes on in both forms.
+                const bool moved = ballot(col && fabs(y - xv) > PI_TOL) != 0;
+#else
+                const bool moved = !(wave_max(col ? fabs(y - xv) : 0.0) <= PI_TOL);
+#endif
                 xv = y;
                 it++;
                 since++;
-                if (d <= PI_TOL) break;
+                if (!moved) break;
                 if (it >= PI_MAXIT) {
                     flags |= 4;
                     break;
@@ -457,7 +494,7 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
             iters = it + PI_POLISH + sqn;
         }
         // loading = v / sqrt(sum(v**2)) with numpy's pairwise sum (:336)
-        const double nv = sqrt(wave_pw_sum(xv * xv, col));
+        const double nv = sqrt(pw_cols(xv * xv));
         ld_j = col ? xv / nv : 0.0;
         wsync();
         if (clus) {
@@ -473,7 +510,7 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
         } else if constexpr (!PK) {  // (the packed layout is never launched for these)
             // ---- big-five (:373-390) / fixed-variance (:429-451): net score =
             // sum_c Sigma_c * (wcd . loading_c); Sigma, loadings from Jacobi (SPEC)
-            const double trace = wave_pw_sum(col ? S.C[l * ES + l] : 0.0, col);  // np.trace
+            const double trace = pw_cols(col ? S.C[l * ES + l] : 0.0);  // np.trace
             wsync();
             for (int o = l; o < E * E; o += W) {
                 const int j = o / E, k = o - j * E;
@@ -550,15 +587,15 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
         const double set1 = sc_i + fabs(mn);
         const double set2 = sc_i - mx;
         double a1 = fabs(set1), a2 = fabs(set2);
-        double S1 = wave_pw_sum(a1, row);
+        double S1 = pw_rows(a1);
         if (S1 == 0) {
             a1 += 1.0;
-            S1 = wave_pw_sum(a1, row);
+            S1 = pw_rows(a1);
         }
-        double S2 = wave_pw_sum(a2, row);
+        double S2 = pw_rows(a2);
         if (S2 == 0) {
             a2 += 1.0;
-            S2 = wave_pw_sum(a2, row);
+            S2 = pw_rows(a2);
         }
         if (row) {
             S.n1[l] = a1 / S1;
@@ -597,16 +634,21 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
         wsync();
         double ref = 0.0;  // non-PCA: straight to the continuous rule
         if (alg == 0) {
-            const double r0 = rank_avg(S.old, E);
-            const double r1 = rank_avg(S.nv1, E);
-            const double r2 = rank_avg(S.nv2, E);
+            double r0, r1, r2;
+            if (PCX_BATCHED_RANK3 && 3 * E <= W) {  // (wave-uniform)
+                rank_avg3(S.old, S.nv1, S.nv2, E, r0, r1, r2);
+            } else {
+                r0 = rank_avg(S.old, E);
+                r1 = rank_avg(S.nv1, E);
+                r2 = rank_avg(S.nv2, E);
+            }
             const double e1 = fabs(r1 - r0), e2 = fabs(r2 - r0);
-            ref = wave_pw_sum(e1, col) - wave_pw_sum(e2, col);
+            ref = pw_cols(e1) - pw_cols(e2);
         }
         bool pick1;
         if (ref == 0) {
             const double q1 = d1 - oldj, q2 = d2 - oldj;
-            const double ref2 = wave_pw_sum(q1 * q1, col) - wave_pw_sum(q2 * q2, col);
+            const double ref2 = pw_cols(q1 * q1) - pw_cols(q2 * q2);
             pick1 = ref2 <= 0;
             branch = pick1 ? 3 : 4;
         } else {
@@ -618,15 +660,19 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
 
     STAMP(7);
     // ---- a10: reputation update (:460-472) --------------------------------
-    const double meanrep = wave_pw_sum(rep, row) / (double)N;
+#if PCX_BATCHED_REPSUM_ONCE
+    const double meanrep = rep_sum / (double)N;
+#else
+    const double meanrep = pw_rows(rep) / (double)N;
+#endif
     double u = fabs(nc_i * (rep / meanrep));
-    double Su = wave_pw_sum(u, row);
+    double Su = pw_rows(u);
     // PCA: a NaN total leaves the reference's this_rep / smooth_rep fully MASKED (SPEC
     // rep_masked: participation_columns, reporter_bonus and author_bonus are numpy.ma's data)
     const bool rep_masked = alg == 0 && __builtin_isnan(Su);
     if (Su == 0) {
         u += 1.0;
-        Su = wave_pw_sum(u, row);
+        Su = pw_rows(u);
     }
     const double this_i = u / Su;
     const double smooth_i = a.alpha * this_i + (1.0 - a.alpha) * rep;
@@ -748,13 +794,13 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
     }
     // normalize(certainty), mean(certainty)
     double ac = fabs(certj);
-    double Sc = wave_pw_sum(ac, col);
+    double Sc = pw_cols(ac);
     if (Sc == 0) {
         ac += 1.0;
-        Sc = wave_pw_sum(ac, col);
+        Sc = pw_cols(ac);
     }
     const double reward = ac / Sc;
-    const double avg_cert = wave_pw_sum(certj, col) / (double)E;
+    const double avg_cert = pw_cols(certj) / (double)E;
 
     STAMP(10);
     // ---- a15: participation and bonuses (:549-581) -------------------------
@@ -791,19 +837,19 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
     }
     const bool rowmasked = row && nnan == E;
     const double pr = 1.0 - narow / (double)E;
-    const double pna = 1.0 - wave_pw_sum(pcj, col) / (double)E;
+    const double pna = 1.0 - pw_cols(pcj) / (double)E;
     double ar = rowmasked ? 0.0 : fabs(pr);
-    double Sr = wave_pw_sum(ar, row);
+    double Sr = pw_rows(ar);
     if (Sr == 0) {
         ar = rowmasked ? 0.0 : fabs(pr) + 1.0;
-        Sr = wave_pw_sum(ar, row);
+        Sr = pw_rows(ar);
     }
     const double rel = rowmasked ? fabs(pr) : ar / Sr;
     double apc = fabs(pcj);
-    double Spc = wave_pw_sum(apc, col);
+    double Spc = pw_cols(apc);
     if (Spc == 0) {
         apc += 1.0;
-        Spc = wave_pw_sum(apc, col);
+        Spc = pw_cols(apc);
     }
     const double relc = apc / Spc;
 
