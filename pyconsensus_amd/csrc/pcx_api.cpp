@@ -30,6 +30,97 @@ int fail(int code, const std::string& msg) {
 int hip_fail(hipError_t e, const char* what) {
     return fail(PCX_EHIP, std::string(what) + ": " + hipGetErrorString(e));
 }
+
+// The option checks that pcx_consensus_batched_f64 ("batched") and pcx_consensus_ragged_f64
+// ("ragged") share, in the order both make them.  `own` is what the entry's own checks found (the
+// algorithm's range, k-means, big-five; NULL: nothing): they follow reports / scaled and precede
+// catch_tolerance / alpha, and each of them, like each check here that names an algorithm, can
+// only fire alone, so one place among those serves both entries.
+template <class In>
+int check_options(const char* who, const In* in, const char* own) {
+    auto refuse = [who](const char* why) { return fail(PCX_EINVAL, std::string(who) + ": " + why); };
+    if (!in->reports) return refuse("reports is NULL");
+    if (in->scaled && (!in->lo || !in->hi)) return refuse("scaled given without lo/hi");
+    if (own) return refuse(own);
+    if (in->algorithm == PCX_ALG_HIERARCHICAL && std::isnan(in->hierarchy_threshold))
+        return refuse("hierarchy_threshold is NaN");
+    if (in->algorithm == PCX_ALG_FIXED_VARIANCE && !std::isfinite(in->variance_threshold))
+        return refuse("variance_threshold must be finite");
+    if (in->algorithm == PCX_ALG_COKURTOSIS && !in->aux_scores)
+        return refuse("cokurtosis needs aux_scores (aux[\"cokurt\"])");
+    if (!std::isfinite(in->catch_tolerance) || !std::isfinite(in->alpha))
+        return refuse("catch_tolerance/alpha must be finite");
+    return PCX_OK;
+}
+
+// what pcx_batch and pcx_ragged both carry: the inputs, the algorithm's options and every output
+template <class In>
+pcx::BatchArgs shared_args(const In* in, const pcx_batch_result* out) {
+    pcx::BatchArgs a{};
+    a.reports = in->reports;
+    a.reputation = in->reputation;
+    a.scaled = in->scaled;
+    a.lo = in->lo;
+    a.hi = in->hi;
+    a.int_dtype = in->int_dtype;
+    a.algorithm = in->algorithm;
+    a.max_components = in->max_components;
+    a.variance_threshold = in->variance_threshold;
+    a.aux_scores = in->aux_scores;
+    a.hierarchy_threshold = in->hierarchy_threshold;
+    a.cluster_threshold = in->cluster_threshold;
+    a.catch_tol = in->catch_tolerance;
+    a.alpha = in->alpha;
+    a.old_rep = out->old_rep;
+    a.this_rep = out->this_rep;
+    a.smooth_rep = out->smooth_rep;
+    a.scores = out->scores;
+    a.na_row = out->na_row;
+    a.participation_rows = out->participation_rows;
+    a.relative_part = out->relative_part;
+    a.reporter_bonus = out->reporter_bonus;
+    a.adj_first_loadings = out->adj_first_loadings;
+    a.outcomes_raw = out->outcomes_raw;
+    a.outcomes_adjusted = out->outcomes_adjusted;
+    a.outcomes_final = out->outcomes_final;
+    a.certainty = out->certainty;
+    a.consensus_reward = out->consensus_reward;
+    a.nas_filled = out->nas_filled;
+    a.participation_columns = out->participation_columns;
+    a.author_bonus = out->author_bonus;
+    a.participation = out->participation;
+    a.avg_certainty = out->avg_certainty;
+    a.branch = out->branch;
+    a.flags = out->flags;
+    a.pi_iters = out->pi_iters;
+    a.components = out->components;
+    a.original = out->original;
+    a.filled = out->filled;
+    return a;
+}
+
+// The PCX_STAMPS diagnostic's buffer (per-phase shader clocks, [B][32]): allocated and zeroed on
+// the stream when the variable is "1" -- a.stamps stays NULL otherwise, and when there are no rounds
+// or no memory -- then, after the launches, read back (the stream is synchronised) and freed.
+void stamps_begin(pcx::BatchArgs& a, hipStream_t stream) {
+    const char* env = getenv("PCX_STAMPS");
+    if (!env || env[0] != '1' || a.B <= 0) return;
+    const size_t bytes = (size_t)a.B * 32 * sizeof(long long);
+    long long* d = nullptr;
+    if (hipMalloc(&d, bytes) != hipSuccess) return;
+    (void)hipMemsetAsync(d, 0, bytes, stream);
+    a.stamps = d;
+}
+
+std::vector<long long> stamps_end(pcx::BatchArgs& a, hipStream_t stream) {
+    std::vector<long long> h(a.stamps ? a.B * 32 : 0);
+    if (!a.stamps) return h;
+    (void)hipMemcpyAsync(h.data(), a.stamps, h.size() * sizeof(long long), hipMemcpyDeviceToHost, stream);
+    (void)hipStreamSynchronize(stream);
+    (void)hipFree(a.stamps);
+    a.stamps = nullptr;
+    return h;
+}
 }  // namespace
 
 extern "C" {
@@ -271,6 +362,86 @@ int pcx_batched_route(int n_reporters, int n_events, int algorithm, int kmeans_k
     return batched_route(n_reporters, n_events, algorithm, kmeans_k);
 }
 
+// PCX_STAMPS, one-wave kernel: h = the stamps read back, [B][32]
+static void print_wave_stamps(const std::vector<long long>& h, int64_t B) {
+    // stamp ids in program order (pcx_batched.hip STAMP(k)); a phase is named by its closing stamp
+    static const int order[] = {0, 1, 2, 13, 14, 3, 4, 5, 6, 7, 8, 15, 16, 9, 10, 11, 12};
+    const int no = (int)(sizeof(order) / sizeof(order[0]));
+    double acc[32] = {0};
+    for (int64_t b = 0; b < B; b++)
+        for (int k = 1; k < no; k++) {
+            const long long t1 = h[b * 32 + order[k]], t0 = h[b * 32 + order[k - 1]];
+            if (t1 && t0) acc[order[k]] += (double)(t1 - t0);
+        }
+    fprintf(stderr, "PCX_STAMPS mean cycles per phase:");
+    for (int k = 1; k < no; k++) fprintf(stderr, " %d:%.0f", order[k], acc[order[k]] / (double)B);
+    double sort = 0, walk = 0;
+    for (int64_t b = 0; b < B; b++) {
+        sort += (double)h[b * 32 + 20];
+        walk += (double)h[b * 32 + 21];
+    }
+    fprintf(stderr, " median_sort:%.0f median_walk:%.0f\n", sort / (double)B, walk / (double)B);
+}
+
+// PCX_STAMPS, workgroup kernel: stamps 0..15 in program order (pcx_medium.hip MSTAMP(k))
+static void print_medium_stamps(const std::vector<long long>& h, int64_t B) {
+    double acc[16] = {0};
+    for (int64_t b = 0; b < B; b++)
+        for (int k = 1, prev = 0; k < 16; k++) {
+            const long long t1 = h[b * 32 + k], t0 = h[b * 32 + prev];
+            if (t1 && t0) {
+                acc[k] += (double)(t1 - t0);
+                prev = k;
+            }
+        }
+    fprintf(stderr, "PCX_STAMPS medium mean cycles per phase:");
+    for (int k = 1; k < 16; k++) fprintf(stderr, " %d:%.0f", k, acc[k] / (double)B);
+    double mp[3] = {0, 0, 0};  // wave 0's outcome medians: total+dom, rank, walk
+    for (int64_t b = 0; b < B; b++)
+        for (int k = 0; k < 3; k++) mp[k] += (double)h[b * 32 + 20 + k];
+    fprintf(stderr, " wave0 medians total:%.0f rank:%.0f walk:%.0f", mp[0] / (double)B, mp[1] / (double)B,
+            mp[2] / (double)B);
+    double sub[4] = {0, 0, 0, 0};  // the nonconformity phase's steps (stamps 24-27 after 8)
+    for (int64_t b = 0; b < B; b++)
+        for (int k = 0; k < 4; k++) {
+            const long long t1 = h[b * 32 + 24 + k], t0 = h[b * 32 + (k ? 23 + k : 8)];
+            if (t1 && t0) sub[k] += (double)(t1 - t0);
+        }
+    fprintf(stderr, " nc: minmax+norm:%.0f n12:%.0f dots:%.0f ranks:%.0f", sub[0] / (double)B, sub[1] / (double)B,
+            sub[2] / (double)B, sub[3] / (double)B);
+    double pw[2] = {0, 0};  // power iteration: presquares (6 -> 28), steps (28 -> 29)
+    for (int64_t b = 0; b < B; b++) {
+        const long long* hb = &h[b * 32];
+        if (hb[28] && hb[6]) pw[0] += (double)(hb[28] - hb[6]);
+        if (hb[29] && hb[28]) pw[1] += (double)(hb[29] - hb[28]);
+    }
+    fprintf(stderr, " pi: presq:%.0f steps:%.0f\n", pw[0] / (double)B, pw[1] / (double)B);
+}
+
+// one workgroup per round (pcx_medium.hip), in chunks of bounded scratch
+static int run_workgroup_route(pcx_ctx* ctx, pcx::BatchArgs& a) {
+    const size_t cap = (size_t)2 << 30;
+    const int64_t chunk = pcx::medium_chunk(a, cap);
+    const size_t need = pcx::medium_scratch_per_round(a) * (size_t)chunk;
+    hipError_t e = hipSuccess;
+    if (ctx->mscr_bytes < need) {
+        if (ctx->mscr) (void)hipFree(ctx->mscr);
+        ctx->mscr = nullptr;
+        ctx->mscr_bytes = 0;
+        e = hipMalloc(&ctx->mscr, need);
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc(medium scratch)");
+        ctx->mscr_bytes = need;
+    }
+    double* Fscr = (double*)ctx->mscr;
+    double* Cscr = Fscr + (a.filled ? 0 : (size_t)chunk * a.N * a.E);
+    double* Xscr = Cscr + (size_t)chunk * a.E * a.E;  // the clusterings' cluster sums / observations
+    stamps_begin(a, ctx->stream);
+    for (int64_t b0 = 0; b0 < a.B && e == hipSuccess; b0 += chunk)
+        e = pcx::launch_medium(a, b0, std::min<int64_t>(chunk, a.B - b0), Fscr, Cscr, Xscr, ctx->stream);
+    if (a.stamps) print_medium_stamps(stamps_end(a, ctx->stream), a.B);
+    return e == hipSuccess ? PCX_OK : hip_fail(e, "medium_round_kernel launch");
+}
+
 int pcx_consensus_batched_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_result* out) {
     if (!ctx || !in || !out) return fail(PCX_EINVAL, "pcx_consensus_batched_f64: null argument");
     if (in->n_rounds < 0 || in->n_rounds > 0x7fffffff)
@@ -279,182 +450,39 @@ int pcx_consensus_batched_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_resul
         return fail(PCX_EINVAL, "batched: n_reporters must be in [1, 2^31)");
     if (in->n_events < 1 || in->n_events > 65536) return fail(PCX_EINVAL, "batched: n_events must be in [1, 65536]");
     const bool large = in->n_reporters > 64 || in->n_events > 32;  // beyond one wavefront per round
-    if (!in->reports) return fail(PCX_EINVAL, "batched: reports is NULL");
-    if (in->scaled && (!in->lo || !in->hi)) return fail(PCX_EINVAL, "batched: scaled given without lo/hi");
+    const char* own = nullptr;  // this entry's own option checks (check_options reports them in their place)
     if (in->algorithm < PCX_ALG_PCA || in->algorithm > PCX_ALG_CLUSTERFECK)
-        return fail(PCX_EINVAL, "batched: algorithm must be an enum pcx_algorithm value (0..7)");
-    if (in->algorithm == PCX_ALG_KMEANS &&
-        (!in->kmeans_init || in->kmeans_k < 1 || in->kmeans_k > (large ? 1024 : 8) || in->kmeans_k > in->n_reporters ||
-         in->kmeans_restarts < 1))
-        return fail(PCX_EINVAL, "batched: k-means needs kmeans_init and 1 <= kmeans_k <= min(N, 8; 1024 above 64 x 32), "
-                                "restarts >= 1");
-    if (in->algorithm == PCX_ALG_HIERARCHICAL && std::isnan(in->hierarchy_threshold))
-        return fail(PCX_EINVAL, "batched: hierarchy_threshold is NaN");
-    if (in->algorithm == PCX_ALG_BIG_FIVE && (in->max_components < 1 || in->max_components > in->n_events))
-        return fail(PCX_EINVAL, "batched: big-five needs 1 <= max_components <= n_events");
-    if (in->algorithm == PCX_ALG_FIXED_VARIANCE && !std::isfinite(in->variance_threshold))
-        return fail(PCX_EINVAL, "batched: variance_threshold must be finite");
-    if (in->algorithm == PCX_ALG_COKURTOSIS && !in->aux_scores)
-        return fail(PCX_EINVAL, "batched: cokurtosis needs aux_scores (aux[\"cokurt\"])");
-    if (!std::isfinite(in->catch_tolerance) || !std::isfinite(in->alpha))
-        return fail(PCX_EINVAL, "batched: catch_tolerance/alpha must be finite");
+        own = "algorithm must be an enum pcx_algorithm value (0..7)";
+    else if (in->algorithm == PCX_ALG_KMEANS &&
+             (!in->kmeans_init || in->kmeans_k < 1 || in->kmeans_k > (large ? 1024 : 8) ||
+              in->kmeans_k > in->n_reporters || in->kmeans_restarts < 1))
+        own = "k-means needs kmeans_init and 1 <= kmeans_k <= min(N, 8; 1024 above 64 x 32), restarts >= 1";
+    else if (in->algorithm == PCX_ALG_BIG_FIVE && (in->max_components < 1 || in->max_components > in->n_events))
+        own = "big-five needs 1 <= max_components <= n_events";
+    if (const int rc = check_options("batched", in, own)) return rc;
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    pcx::BatchArgs a{};
+    pcx::BatchArgs a = shared_args(in, out);
     a.B = in->n_rounds;
     a.N = (int)in->n_reporters;
     a.E = (int)in->n_events;
     a.ES = a.E | 1;
-    a.reports = in->reports;
-    a.reputation = in->reputation;
-    a.scaled = in->scaled;
-    a.lo = in->lo;
-    a.hi = in->hi;
     a.bounds_shared = in->bounds_shared;
-    a.int_dtype = in->int_dtype;
-    a.algorithm = in->algorithm;
-    a.max_components = in->max_components;
-    a.variance_threshold = in->variance_threshold;
-    a.aux_scores = in->aux_scores;
-    a.hierarchy_threshold = in->hierarchy_threshold;
-    a.cluster_threshold = in->cluster_threshold;
     a.kmeans_k = in->kmeans_k;
     a.kmeans_restarts = in->kmeans_restarts;
     a.kmeans_init = in->kmeans_init;
-    a.catch_tol = in->catch_tolerance;
-    a.alpha = in->alpha;
-    a.old_rep = out->old_rep;
-    a.this_rep = out->this_rep;
-    a.smooth_rep = out->smooth_rep;
-    a.scores = out->scores;
-    a.na_row = out->na_row;
-    a.participation_rows = out->participation_rows;
-    a.relative_part = out->relative_part;
-    a.reporter_bonus = out->reporter_bonus;
-    a.adj_first_loadings = out->adj_first_loadings;
-    a.outcomes_raw = out->outcomes_raw;
-    a.outcomes_adjusted = out->outcomes_adjusted;
-    a.outcomes_final = out->outcomes_final;
-    a.certainty = out->certainty;
-    a.consensus_reward = out->consensus_reward;
-    a.nas_filled = out->nas_filled;
-    a.participation_columns = out->participation_columns;
-    a.author_bonus = out->author_bonus;
-    a.participation = out->participation;
-    a.avg_certainty = out->avg_certainty;
-    a.branch = out->branch;
-    a.flags = out->flags;
-    a.pi_iters = out->pi_iters;
-    a.components = out->components;
-    a.original = out->original;
-    a.filled = out->filled;
     const int route = batched_route(in->n_reporters, in->n_events, in->algorithm, in->kmeans_k);
     if (route < 0) return fail(PCX_EINVAL, "batched: invalid shape or algorithm");  // (refused above)
+    if (route == PCX_ROUTE_WORKGROUP && !getenv("PCX_NO_MEDIUM")) return run_workgroup_route(ctx, a);
     if (route != PCX_ROUTE_WAVE) {
-        if (route == PCX_ROUTE_WORKGROUP && !getenv("PCX_NO_MEDIUM")) {
-            // one workgroup per round (pcx_medium.hip), in chunks of bounded scratch
-            const size_t cap = (size_t)2 << 30;
-            const int64_t chunk = pcx::medium_chunk(a, cap);
-            const size_t per = pcx::medium_scratch_per_round(a);
-            const size_t need = per * (size_t)chunk;
-            if (ctx->mscr_bytes < need) {
-                if (ctx->mscr) (void)hipFree(ctx->mscr);
-                ctx->mscr = nullptr;
-                ctx->mscr_bytes = 0;
-                e = hipMalloc(&ctx->mscr, need);
-                if (e != hipSuccess) return hip_fail(e, "hipMalloc(medium scratch)");
-                ctx->mscr_bytes = need;
-            }
-            double* Fscr = (double*)ctx->mscr;
-            double* Cscr = Fscr + (a.filled ? 0 : (size_t)chunk * a.N * a.E);
-            double* Xscr = Cscr + (size_t)chunk * a.E * a.E;  // the clusterings' cluster sums / observations
-            const char* mst = getenv("PCX_STAMPS");
-            if (mst && mst[0] == '1') {  // diagnostic: per-phase clock breakdown
-                long long* d = nullptr;
-                if (hipMalloc(&d, a.B * 32 * sizeof(long long)) == hipSuccess) {
-                    (void)hipMemsetAsync(d, 0, a.B * 32 * sizeof(long long), ctx->stream);
-                    a.stamps = d;
-                }
-            }
-            for (int64_t b0 = 0; b0 < a.B && e == hipSuccess; b0 += chunk)
-                e = pcx::launch_medium(a, b0, std::min<int64_t>(chunk, a.B - b0), Fscr, Cscr, Xscr, ctx->stream);
-            if (a.stamps) {  // stamps 0..15 in program order (pcx_medium.hip MSTAMP(k))
-                std::vector<long long> h(a.B * 32);
-                (void)hipMemcpyAsync(h.data(), a.stamps, h.size() * sizeof(long long), hipMemcpyDeviceToHost,
-                                     ctx->stream);
-                (void)hipStreamSynchronize(ctx->stream);
-                (void)hipFree(a.stamps);
-                double acc[16] = {0};
-                for (int64_t b = 0; b < a.B; b++)
-                    for (int k = 1, prev = 0; k < 16; k++) {
-                        const long long t1 = h[b * 32 + k], t0 = h[b * 32 + prev];
-                        if (t1 && t0) {
-                            acc[k] += (double)(t1 - t0);
-                            prev = k;
-                        }
-                    }
-                fprintf(stderr, "PCX_STAMPS medium mean cycles per phase:");
-                for (int k = 1; k < 16; k++) fprintf(stderr, " %d:%.0f", k, acc[k] / (double)a.B);
-                double mp[3] = {0, 0, 0};  // wave 0's outcome medians: total+dom, rank, walk
-                for (int64_t b = 0; b < a.B; b++)
-                    for (int k = 0; k < 3; k++) mp[k] += (double)h[b * 32 + 20 + k];
-                fprintf(stderr, " wave0 medians total:%.0f rank:%.0f walk:%.0f", mp[0] / (double)a.B,
-                        mp[1] / (double)a.B, mp[2] / (double)a.B);
-                double sub[4] = {0, 0, 0, 0};  // the nonconformity phase's steps (stamps 24-27 after 8)
-                for (int64_t b = 0; b < a.B; b++)
-                    for (int k = 0; k < 4; k++) {
-                        const long long t1 = h[b * 32 + 24 + k], t0 = h[b * 32 + (k ? 23 + k : 8)];
-                        if (t1 && t0) sub[k] += (double)(t1 - t0);
-                    }
-                fprintf(stderr, " nc: minmax+norm:%.0f n12:%.0f dots:%.0f ranks:%.0f", sub[0] / (double)a.B,
-                        sub[1] / (double)a.B, sub[2] / (double)a.B, sub[3] / (double)a.B);
-                double pw[2] = {0, 0};  // power iteration: presquares (6 -> 28), steps (28 -> 29)
-                for (int64_t b = 0; b < a.B; b++) {
-                    const long long* hb = &h[b * 32];
-                    if (hb[28] && hb[6]) pw[0] += (double)(hb[28] - hb[6]);
-                    if (hb[29] && hb[28]) pw[1] += (double)(hb[29] - hb[28]);
-                }
-                fprintf(stderr, " pi: presq:%.0f steps:%.0f\n", pw[0] / (double)a.B, pw[1] / (double)a.B);
-            }
-            return e == hipSuccess ? PCX_OK : hip_fail(e, "medium_round_kernel launch");
-        }
         // one single-matrix consensus per round, many rounds in flight (pcx_rounds.cpp)
         std::string err;
         const int rc = pcx::run_rounds(ctx, in, out, err);
         return rc ? fail(rc, "pcx_consensus_batched_f64: " + err) : PCX_OK;
     }
-    const char* st_env = getenv("PCX_STAMPS");
-    if (st_env && st_env[0] == '1' && a.B > 0) {  // diagnostic: per-phase clock breakdown
-        long long* d = nullptr;
-        if (hipMalloc(&d, a.B * 32 * sizeof(long long)) == hipSuccess) {
-            (void)hipMemsetAsync(d, 0, a.B * 32 * sizeof(long long), ctx->stream);
-            a.stamps = d;
-        }
-    }
+    stamps_begin(a, ctx->stream);
     e = pcx::launch_batched(a, ctx->stream);
-    if (a.stamps) {
-        // stamp ids in program order (pcx_batched.hip STAMP(k)); a phase is named by its closing stamp
-        static const int order[] = {0, 1, 2, 13, 14, 3, 4, 5, 6, 7, 8, 15, 16, 9, 10, 11, 12};
-        const int no = (int)(sizeof(order) / sizeof(order[0]));
-        std::vector<long long> h(a.B * 32);
-        (void)hipMemcpyAsync(h.data(), a.stamps, h.size() * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream);
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(a.stamps);
-        double acc[32] = {0};
-        for (int64_t b = 0; b < a.B; b++)
-            for (int k = 1; k < no; k++) {
-                const long long t1 = h[b * 32 + order[k]], t0 = h[b * 32 + order[k - 1]];
-                if (t1 && t0) acc[order[k]] += (double)(t1 - t0);
-            }
-        fprintf(stderr, "PCX_STAMPS mean cycles per phase:");
-        for (int k = 1; k < no; k++) fprintf(stderr, " %d:%.0f", order[k], acc[order[k]] / (double)a.B);
-        double sort = 0, walk = 0;
-        for (int64_t b = 0; b < a.B; b++) {
-            sort += (double)h[b * 32 + 20];
-            walk += (double)h[b * 32 + 21];
-        }
-        fprintf(stderr, " median_sort:%.0f median_walk:%.0f\n", sort / (double)a.B, walk / (double)a.B);
-    }
+    if (a.stamps) print_wave_stamps(stamps_end(a, ctx->stream), a.B);
     return e == hipSuccess ? PCX_OK : hip_fail(e, "batched_round_kernel launch");
 }
 
@@ -498,18 +526,10 @@ int pcx_consensus_ragged_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_resul
                                        nullptr))
         return rc;
     if (in->n_rounds == 0) return PCX_OK;
-    if (!in->reports) return fail(PCX_EINVAL, "ragged: reports is NULL");
-    if (in->scaled && (!in->lo || !in->hi)) return fail(PCX_EINVAL, "ragged: scaled given without lo/hi");
-    if (in->algorithm == PCX_ALG_HIERARCHICAL && std::isnan(in->hierarchy_threshold))
-        return fail(PCX_EINVAL, "ragged: hierarchy_threshold is NaN");
-    if (in->algorithm == PCX_ALG_BIG_FIVE && in->max_components < 1)  // (capped at E_b per round on the device)
-        return fail(PCX_EINVAL, "ragged: big-five needs max_components >= 1");
-    if (in->algorithm == PCX_ALG_FIXED_VARIANCE && !std::isfinite(in->variance_threshold))
-        return fail(PCX_EINVAL, "ragged: variance_threshold must be finite");
-    if (in->algorithm == PCX_ALG_COKURTOSIS && !in->aux_scores)
-        return fail(PCX_EINVAL, "ragged: cokurtosis needs aux_scores (aux[\"cokurt\"])");
-    if (!std::isfinite(in->catch_tolerance) || !std::isfinite(in->alpha))
-        return fail(PCX_EINVAL, "ragged: catch_tolerance/alpha must be finite");
+    // (max_components is capped at E_b per round on the device)
+    const bool bad_five = in->algorithm == PCX_ALG_BIG_FIVE && in->max_components < 1;
+    if (const int rc = check_options("ragged", in, bad_five ? "big-five needs max_components >= 1" : nullptr))
+        return rc;
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     // the descriptor table: built in this call's staging slot, uploaded on the stream
@@ -562,47 +582,8 @@ int pcx_consensus_ragged_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_resul
     if (e == hipSuccess) e = hipEventRecord(s.copy_ev, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "ragged: descriptor upload");
     s.used = true;
-    pcx::BatchArgs a{};
+    pcx::BatchArgs a = shared_args(in, out);
     a.B = B;
-    a.reports = in->reports;
-    a.reputation = in->reputation;
-    a.scaled = in->scaled;
-    a.lo = in->lo;
-    a.hi = in->hi;
-    a.int_dtype = in->int_dtype;
-    a.algorithm = in->algorithm;
-    a.max_components = in->max_components;
-    a.variance_threshold = in->variance_threshold;
-    a.aux_scores = in->aux_scores;
-    a.hierarchy_threshold = in->hierarchy_threshold;
-    a.cluster_threshold = in->cluster_threshold;
-    a.catch_tol = in->catch_tolerance;
-    a.alpha = in->alpha;
-    a.old_rep = out->old_rep;
-    a.this_rep = out->this_rep;
-    a.smooth_rep = out->smooth_rep;
-    a.scores = out->scores;
-    a.na_row = out->na_row;
-    a.participation_rows = out->participation_rows;
-    a.relative_part = out->relative_part;
-    a.reporter_bonus = out->reporter_bonus;
-    a.adj_first_loadings = out->adj_first_loadings;
-    a.outcomes_raw = out->outcomes_raw;
-    a.outcomes_adjusted = out->outcomes_adjusted;
-    a.outcomes_final = out->outcomes_final;
-    a.certainty = out->certainty;
-    a.consensus_reward = out->consensus_reward;
-    a.nas_filled = out->nas_filled;
-    a.participation_columns = out->participation_columns;
-    a.author_bonus = out->author_bonus;
-    a.participation = out->participation;
-    a.avg_certainty = out->avg_certainty;
-    a.branch = out->branch;
-    a.flags = out->flags;
-    a.pi_iters = out->pi_iters;
-    a.components = out->components;
-    a.original = out->original;
-    a.filled = out->filled;
     e = pcx::launch_ragged(a, static_cast<const pcx::RaggedDesc*>(s.dev), (size_t)lds, ctx->stream);
     if (e == hipSuccess) e = hipEventRecord(s.kern_ev, ctx->stream);
     return e == hipSuccess ? PCX_OK : hip_fail(e, "ragged_round_kernel launch");

@@ -31,6 +31,7 @@ constexpr int NMAX = 64;  // reporters per round (one lane each)
 constexpr int EMAX = 32;  // events per round (MFMA tiles 2 x 16; pcx_api.cpp validates)
 static_assert(EMAX <= 2 * 16, "2 x 2 grid of 16 x 16 MFMA tiles");
 static_assert(NMAX == W, "one reporter per lane");
+constexpr int PACKED_WAVES = 4;  // waves per SIMD the compiled packed shapes' VGPR budget is sized for (128 VGPRs)
 
 // power iteration constants (SPEC; equal to oracle/pcx_oracle_batched.c)
 constexpr double PI_TOL = 1e-14;
@@ -49,23 +50,6 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x; }
 // __noinline__, 49 KB + shared helpers) the call ABI spills and the kernel ran 29 %
 // slower (24.4 M vs 34.4 M rounds/s).
 #define PCX_OUTLINE __forceinline__
-
-// Build parameters of the live-lane steps (0 builds the form before each):
-#ifndef PCX_BATCHED_PI_BALLOT  // the power iteration's convergence test is a ballot, not a max reduction
-#define PCX_BATCHED_PI_BALLOT 1
-#endif
-#ifndef PCX_BATCHED_LIVE_ROWS  // column-phase tree_sum / wave_max of a compiled shape read E's 16-lane rows only
-#define PCX_BATCHED_LIVE_ROWS 1
-#endif
-#ifndef PCX_BATCHED_PW_PREFIX  // wave_pw_sum over the prefixes l < N, l < E: no ballot, no lane counts
-#define PCX_BATCHED_PW_PREFIX 1
-#endif
-#ifndef PCX_BATCHED_REPSUM_ONCE  // the pairwise sum of rep is formed once for a5 (den) and a10 (meanrep)
-#define PCX_BATCHED_REPSUM_ONCE 1
-#endif
-#ifndef PCX_BATCHED_RANK3  // 3 E <= 64: the rankings of old, nv1 and nv2 in one pass on three lane groups
-#define PCX_BATCHED_RANK3 1
-#endif
 
 // diagnostic phase stamps (PCX_STAMPS=1): shader-clock reads at phase boundaries
 #define STAMP(k)                                                                  \
@@ -146,7 +130,7 @@ __device__ __forceinline__ double tree_sum(double v) {
     return (lane_value(v, 0) + lane_value(v, 16)) + (lane_value(v, 32) + lane_value(v, 48));
 }
 // the live rows of a column-phase value (lanes >= E are padding) of a compiled shape
-constexpr int live_rows(int ET) { return PCX_BATCHED_LIVE_ROWS && ET > 0 ? (ET <= 16 ? 1 : ET <= 32 ? 2 : 4) : 4; }
+constexpr int live_rows(int ET) { return ET > 0 ? (ET <= 16 ? 1 : ET <= 32 ? 2 : 4) : 4; }
 
 // inclusive prefix sum over the lanes in lane order (row_shr DPP inside each 16-lane row, then the
 // rows' totals by readlane): a fixed tree order, deterministic, within ~6 u of the exact sums
@@ -766,7 +750,7 @@ struct Smem {
 // 12,800 bytes ran twelve to a CU, one of 13,192 eleven).
 __host__ __device__ inline int smem_rows(int N) { return (N + 1) & ~1; }
 // F also holds the certainty phase's compacted hit lists, [E][cert_stride] (an odd stride with
-// the odd row pitch; the even pitch of PCX_BATCHED_ES_EVEN keeps N)
+// the odd row pitch; the compiled shapes' even pitch keeps N)
 __host__ __device__ inline int cert_stride(int N, int ES) { return (ES & 1) ? (N | 1) : N; }
 __host__ __device__ inline int smem_f_size(int N, int E, int ES) {
     return N * ES > E * cert_stride(N, ES) ? N * ES : E * cert_stride(N, ES);
@@ -928,13 +912,6 @@ template <int NS>
 struct SymOps {
     double a0[NS], a1[NS];
 };
-// (Build parameters for A/B runs; the defaults are what measured fastest)
-#ifndef PCX_BATCHED_T01_MOVES  // 1: E <= 20 takes t01 from t10 by cross-lane moves; 0: always a fourth MFMA chain
-#define PCX_BATCHED_T01_MOVES 1
-#endif
-#ifndef PCX_BATCHED_MV_MFMA  // 1: the matrix-vector steps by MFMA from the operand registers; 0: matvec_unit
-#define PCX_BATCHED_MV_MFMA 0  // on the packed triangle written over C (C's operands wait in registers)
-#endif
 
 // the operands of the packed lower triangle C in LDS (the reads square_scaled<true> makes)
 template <int NS>
@@ -983,7 +960,7 @@ __device__ PCX_OUTLINE void square_scaled_reg(SymOps<NS>& m, int E) {
     const bool two = E > 16;
     // E <= 20: t01's live entries (kq + 4r, 16 + ml), ml < 4, are t10's accumulator 0 of lane
     // (4r + kq, kq' = ml) -- four cross-lane moves instead of a fourth MFMA chain
-    const bool t01_moves = PCX_BATCHED_T01_MOVES && E <= 20;
+    const bool t01_moves = E <= 20;
     d4v t00 = {0, 0, 0, 0}, t01 = {0, 0, 0, 0}, t10 = {0, 0, 0, 0}, t11 = {0, 0, 0, 0};
 #pragma unroll
     for (int s = 0; s < NS; s++) {
@@ -1033,29 +1010,6 @@ __device__ PCX_OUTLINE void square_scaled_reg(SymOps<NS>& m, int E) {
         keep([&](double t) { return t * sc; });
     else
         keep([&](double t) { return mx > 0.0 ? t / mx : t; });
-}
-
-// matvec_unit on those operands.  With A[i][k] = x_k (every row) and B[k][j] = M[j][k] the MFMA
-// leaves y_j = fma(x_k, M[j][k], acc) over k ascending from +0 -- matvec_unit's chain, the
-// product commuted -- in every accumulator of lane (ml = j, any kq): lane l < 16 reads its y
-// from row tile 0, lane 16 + ml (kq = 1) from row tile 1.  x_{4s + kq} comes by ds_bpermute.
-template <int NS, int ROWS = 4>
-__device__ PCX_OUTLINE double matvec_unit_reg(const SymOps<NS>& m, double xv, int E) {
-    const int l = lane_id(), kq = l >> 4;
-    const bool two = E > 16;
-    d4v y0 = {0, 0, 0, 0}, y1 = {0, 0, 0, 0};
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        if (4 * s < E) {
-            const double xk = bpermute_d(4 * s + kq, xv);  // (xv is 0.0 on lanes >= E)
-            y0 = mfma_f64(xk, m.a0[s], y0);
-            if (two) y1 = mfma_f64(xk, m.a1[s], y1);
-        }
-    }
-    const double acc = l < 16 ? y0[0] : y1[0];
-    const double y = l < E ? acc : 0.0;
-    const double nrm = sqrt(tree_sum<ROWS>(l < E ? y * y : 0.0));  // squares: no row sum is -0.0
-    return l < E ? y / nrm : 0.0;
 }
 
 // ---- "big-five" / "fixed-variance" eigenpairs: SPEC jacobi_eig of
@@ -1532,31 +1486,12 @@ __device__ __noinline__ double feck_nc(const BatchArgs& a, const double* F, int 
 
 }  // namespace
 
-// The compiled shapes' row pitch: E (1) or E | 1 (0).  The odd pitch spreads a row-phase column
-// read over the banks, but 50 x 20 rounds at the even one fit nine LDS units instead of ten -- 14
-// rounds a CU instead of 12 with the 128-VGPR budget below (C3: 1.53 -> 1.46 ms, 42.5 -> 44.6 M
+// The compiled shapes' row pitch: E, not the dynamic shapes' E | 1.  The odd pitch spreads a row-phase
+// column read over the banks, but 50 x 20 rounds at the even one fit nine LDS units instead of ten -- 14
+// rounds a CU instead of 12 with the 128-VGPR budget of PACKED_WAVES (C3: 1.53 -> 1.46 ms, 42.5 -> 44.6 M
 // rounds/s; the even pitch under the three-wave budget, 12 a CU, ran 1.534-1.546 ms against the odd
-// pitch's 1.530-1.540: its bank conflicts cost little).  (Build parameters for A/B runs.)
-#ifndef PCX_BATCHED_ES_EVEN
-#define PCX_BATCHED_ES_EVEN 1
-#endif
-__host__ __device__ constexpr int compiled_es(int E) { return PCX_BATCHED_ES_EVEN ? E : (E | 1); }
-#ifndef PCX_BATCHED_WAVES  // waves per SIMD the compiled packed shapes' VGPR budget is sized for (4: 128 VGPRs)
-#define PCX_BATCHED_WAVES 4
-#endif
-// Build parameters of the instruction-count steps (0 builds the form before each):
-#ifndef PCX_BATCHED_ROWMASKS  // the rescale loop keeps per-row NaN / zero bit masks, no live ballots
-#define PCX_BATCHED_ROWMASKS 1
-#endif
-#ifndef PCX_BATCHED_RESCALE_WALK  // (with ROWMASKS) only scaled columns fetch bounds; no row mask on the ballots
-#define PCX_BATCHED_RESCALE_WALK 1
-#endif
-#ifndef PCX_BATCHED_KERNARG_OUT  // the output pointers are read from the kernel arguments where they are used
-#define PCX_BATCHED_KERNARG_OUT 1
-#endif
-#ifndef PCX_BATCHED_D12_ONE_PASS  // np.dot(n1, F) on lanes 0.., np.dot(n2, F) on lanes 32.. in one pass
-#define PCX_BATCHED_D12_ONE_PASS 1
-#endif
+// pitch's 1.530-1.540: its bank conflicts cost little).
+__host__ __device__ constexpr int compiled_es(int E) { return E; }
 
 // wave-uniform 64-bit value into scalar registers
 __device__ __forceinline__ int64_t uniform64(int64_t v) {

@@ -31,7 +31,7 @@ __global__ void __launch_bounds__(64, 3) ragged_round_kernel(BatchArgs a, const 
 #define PCX_ROUND_ROW0 (b * N)
 #define PCX_ROUND_EV0 (b * E)
 template <int NT, int ET, bool CLUS, bool PK>
-__global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) batched_round_kernel(BatchArgs a) {
+__global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched_round_kernel(BatchArgs a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int N = NT > 0 ? NT : a.N, E = ET > 0 ? ET : a.E, ES = ET > 0 ? compiled_es(ET) : a.ES;
 #endif
@@ -44,35 +44,19 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
     const bool has_bounds = a.scaled != nullptr;
     // numpy's pairwise sum over the reporters' / the events' lanes: both are prefixes of the wave
     // (of compile-time length in a compiled shape), see wave_pw_sum_prefix
-    auto pw_rows = [&](double v) {
-#if PCX_BATCHED_PW_PREFIX
-        return wave_pw_sum_prefix<NT>(v, N);
-#else
-        return wave_pw_sum(v, row);
-#endif
-    };
-    auto pw_cols = [&](double v) {
-#if PCX_BATCHED_PW_PREFIX
-        return wave_pw_sum_prefix<ET>(v, E);
-#else
-        return wave_pw_sum(v, col);
-#endif
-    };
+    auto pw_rows = [&](double v) { return wave_pw_sum_prefix<NT>(v, N); };
+    auto pw_cols = [&](double v) { return wave_pw_sum_prefix<ET>(v, E); };
     constexpr int CR = live_rows(ET);  // 16-lane rows that hold events (a compiled shape's; else all four)
 
     // The output pointers are read from the kernel-argument segment where they are used (scalar
     // loads, the segment's address made opaque at each use): as fields of `a` all of them are
     // fetched at kernel entry and held -- 60 scalar registers spilled to lanes until the epilogue.
-#if PCX_BATCHED_KERNARG_OUT
     typedef const __attribute__((address_space(4))) BatchArgs* KernArgs;
     auto out_args = [&]() -> KernArgs {
         uint64_t p = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();  // `a` is the first argument: offset 0
         asm volatile("" : "+s"(p));
         return (KernArgs)p;
     };
-#else
-    auto out_args = [&]() { return &a; };
-#endif
 
     long long mprof[3] = {0, 0, 0};  // diagnostic: median sort / walk cycles (PCX_STAMPS)
     STAMP(0);
@@ -130,17 +114,15 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
     // the same LDS array would otherwise wait for it)
     // per-lane counts, 7 bits each: row l's zeros (bits 0-7) and NaNs (8-15), column l's zeros (16-23)
     uint32_t nacnt = 0;
-#if PCX_BATCHED_ROWMASKS
     // Each row lane collects its own row's NaN / zero columns as bits of two 32-bit masks straight
     // from the compares (E <= 32), and lane j takes column j's zero count when column j is visited,
     // so a column's two ballots die with it.  (Summed from the ballots' bits instead, the whole
     // accumulation sank to its first use after the certainty, and forty ballots waited for it in
     // spilled scalar registers.)
-    // WALK: only a scaled column (a wave-uniform branch on scaled_mask) fetches its bounds and
-    // divides, and the lanes past the last row hold 1.0, neither NaN nor zero, so the compares are
-    // the ballots with no row mask applied.
-    constexpr bool WALK = PCX_BATCHED_RESCALE_WALK;
-    double xnext = row ? S.F[l * ES] : (WALK ? 1.0 : 0.0);
+    // Only a scaled column (a wave-uniform branch on scaled_mask) fetches its bounds and divides,
+    // and the lanes past the last row hold 1.0, neither NaN nor zero, so the compares are the
+    // ballots with no row mask applied.
+    double xnext = row ? S.F[l * ES] : 1.0;
     uint32_t nanb = 0, zerob = 0;
     int zcol = 0;  // column l's zero count (lanes < E)
     // (the compiled shapes' loop unrolled: left rolled, as the compiler leaves it with the
@@ -149,25 +131,16 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
     for (int j = 0; j < E; j++) {
         const bool sc = (scaled_mask >> j) & 1;
         double x = xnext;
-        if (j + 1 < E) xnext = row ? S.F[l * ES + j + 1] : (WALK ? 1.0 : 0.0);
-        if constexpr (WALK) {
-            if (sc) {  // wave-uniform
-                const double lo = bcast(loj, j), hi = bcast(hij, j);
-                if (row) {
-                    x = (x - lo) / (hi - lo);
-                    if (a.int_dtype) x = trunc(x);
-                    S.F[l * ES + j] = x;
-                }
-            }
-        } else {
+        if (j + 1 < E) xnext = row ? S.F[l * ES + j + 1] : 1.0;
+        if (sc) {  // wave-uniform
             const double lo = bcast(loj, j), hi = bcast(hij, j);
-            if (row && sc) {
+            if (row) {
                 x = (x - lo) / (hi - lo);
                 if (a.int_dtype) x = trunc(x);
                 S.F[l * ES + j] = x;
             }
         }
-        const bool xn = (WALK || row) && __builtin_isnan(x), xz = (WALK || row) && x == 0.0;
+        const bool xn = __builtin_isnan(x), xz = x == 0.0;
         nanb |= xn ? 1u << j : 0u;
         zerob |= xz ? 1u << j : 0u;
         const uint64_t zm = ballot(xz), mm = ballot(xn) | zm;
@@ -178,26 +151,6 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
         asm volatile("" : "+v"(nanb), "+v"(zerob), "+v"(zcol));
     }
     nacnt = (uint32_t)__popc(zerob) | ((uint32_t)__popc(nanb) << 8) | ((uint32_t)zcol << 16);
-#else
-    double xnext = row ? S.F[l * ES] : 0.0;
-    for (int j = 0; j < E; j++) {
-        const bool sc = (scaled_mask >> j) & 1;
-        const double lo = bcast(loj, j), hi = bcast(hij, j);
-        double x = xnext;
-        if (j + 1 < E) xnext = row ? S.F[l * ES + j + 1] : 0.0;
-        if (row) {
-            if (sc) {
-                x = (x - lo) / (hi - lo);
-                if (a.int_dtype) x = trunc(x);
-                S.F[l * ES + j] = x;
-            }
-        }
-        const uint64_t nm = ballot(row && __builtin_isnan(x));
-        const uint64_t zm = ballot(row && x == 0.0);
-        nacnt += (uint32_t)((zm >> l) & 1) + ((uint32_t)((nm >> l) & 1) << 8) + (l == j ? (uint32_t)popc(zm) << 16 : 0u);
-        if (l == 0) S.miss[j] = nm | zm;
-    }
-#endif
     wsync();
     // result["original"] (the rescaled reports), from LDS in row-major order: every store
     // instruction writes 64 consecutive doubles (whole lines), not one column's 50 strided ones
@@ -324,18 +277,12 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
     int branch = 5, flags = 0, iters = 0, comps = -1;
     const int alg = a.algorithm;
     const bool clus = CLUS && alg >= 5;  // k-means / hierarchical / clusterfeck call wpca too (:393, :408, :422)
-#if PCX_BATCHED_REPSUM_ONCE
     // sum(rep), numpy's pairwise: the weighted mean's denominator (a5) and mean(rep) (a10) are the
     // same sum of the same operands, formed here once for both
     const double rep_sum = pw_rows(rep);
-#endif
     if (alg == 0 || alg == 2 || alg == 3 || clus) {  // wpca (:315-339): PCA, big-five, fixed-variance
         // ---- a5: weighted mean, np.ma.average (:317-319) -------------------
-#if PCX_BATCHED_REPSUM_ONCE
         const double den = rep_sum;
-#else
-        const double den = pw_rows(rep);
-#endif
         double muj = 0.0;
         if (E == 1) {
             const double p = row ? S.F[l * ES] * rep : 0.0;
@@ -428,14 +375,13 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
             // is its lower triangle mirrored); the matrix-vector steps read M's triangle from C's
             // place in LDS, and C's operands (creg) are written back for the polish steps
             constexpr int NS = !PK ? 1 : ET > 0 ? (ET + 3) / 4 : EMAX / 4;
-            constexpr bool MVM = PK && PCX_BATCHED_MV_MFMA, MVL = PK && !PCX_BATCHED_MV_MFMA;
             SymOps<NS> mreg, creg;
-            if constexpr (PK) load_sym_ops<NS>(S.C, E, mreg);
-            if constexpr (MVL) creg = mreg;
+            if constexpr (PK) {
+                load_sym_ops<NS>(S.C, E, mreg);
+                creg = mreg;
+            }
             auto square = [&](bool in_loop) {
-                if constexpr (MVM) {
-                    square_scaled_reg<NS>(mreg, E);
-                } else if constexpr (MVL) {  // (M's triangle lies over C in LDS between the squarings)
+                if constexpr (PK) {  // (M's triangle lies over C in LDS between the squarings)
                     if (in_loop) load_sym_ops<NS>(S.C, E, mreg);
                     square_scaled_reg<NS>(mreg, E);
                     if (in_loop) store_sym_ops<NS>(S.C, E, mreg);
@@ -443,19 +389,12 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
                     square_scaled<PK>(S.M, ES, E);
                 }
             };
-            auto step = [&](const double* Mlds, double x) {
-                if constexpr (MVM)
-                    return matvec_unit_reg<NS, CR>(mreg, x, E);
-                else
-                    return matvec_unit<PK, CR>(Mlds, ES, x, E);
-            };
             int sqn = 0;
             for (; sqn < PI_PRESQUARE; sqn++) square(false);
-            if constexpr (MVL) store_sym_ops<NS>(S.C, E, mreg);
+            if constexpr (PK) store_sym_ops<NS>(S.C, E, mreg);
             int it = 0, since = 0;
             for (;;) {
-                const double y = step(PK ? S.C : S.M, xv);
-#if PCX_BATCHED_PI_BALLOT
+                const double y = matvec_unit<PK, CR>(PK ? S.C : S.M, ES, xv, E);
                 // SPEC: d = max over the events of |y - x|, stop when d <= PI_TOL.  Only the compare
                 // is used, and d <= PI_TOL holds exactly when no event lane has |y - x| > PI_TOL:
                 // the maximum (v_max_f64) drops a NaN operand and the lanes from E on feed 0.0, so a
@@ -463,9 +402,6 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
                 // them NaN: d = 0.0, the loop stops, and so does this); an infinite difference makes
                 // d infinite and the compare true, and the loop goes on in both forms.
                 const bool moved = ballot(col && fabs(y - xv) > PI_TOL) != 0;
-#else
-                const bool moved = !(wave_max(col ? fabs(y - xv) : 0.0) <= PI_TOL);
-#endif
                 xv = y;
                 it++;
                 since++;
@@ -481,9 +417,8 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
                 }
             }
             // the polish steps run on C itself
-            if constexpr (MVM) load_sym_ops<NS>(S.C, E, mreg);
-            if constexpr (MVL) store_sym_ops<NS>(S.C, E, creg);
-            for (int p = 0; p < PI_POLISH; p++) xv = step(S.C, xv);
+            if constexpr (PK) store_sym_ops<NS>(S.C, E, creg);
+            for (int p = 0; p < PI_POLISH; p++) xv = matvec_unit<PK, CR>(S.C, ES, xv, E);
             // SPEC sign: first nonzero component negative; a unit vector e_k is +e_k
             const uint64_t nzm = ballot(col && xv != 0.0);
             if (nzm) {
@@ -604,7 +539,6 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
         if (col) S.old[l] = oldj;
         wsync();
         double d1 = 0.0, d2 = 0.0;
-#if PCX_BATCHED_D12_ONE_PASS
         {
             // both products in one pass over the rows: lane j < E runs column j on n1, lane 32 + j
             // the same column on n2 (E <= 32) -- one instruction stream, each lane its own vector
@@ -621,12 +555,7 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
                 d2 = __longlong_as_double((long long)(((uint64_t)uhi << 32) | ulo));
             }
         }
-#endif
         if (col) {
-#if !PCX_BATCHED_D12_ONE_PASS
-            d1 = ob_vecmat(S.n1, S.F + l, ES, N, E, l);  // np.dot(normalize(set1), F) (:492)
-            d2 = ob_vecmat(S.n2, S.F + l, ES, N, E, l);
-#endif
             const double t = 0.01 * oldj;
             S.nv1[l] = d1 + t;
             S.nv2[l] = d2 + t;
@@ -635,7 +564,7 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
         double ref = 0.0;  // non-PCA: straight to the continuous rule
         if (alg == 0) {
             double r0, r1, r2;
-            if (PCX_BATCHED_RANK3 && 3 * E <= W) {  // (wave-uniform)
+            if (3 * E <= W) {  // (wave-uniform)
                 rank_avg3(S.old, S.nv1, S.nv2, E, r0, r1, r2);
             } else {
                 r0 = rank_avg(S.old, E);
@@ -660,11 +589,7 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PCX_BATCHED_WAVES : 3) ba
 
     STAMP(7);
     // ---- a10: reputation update (:460-472) --------------------------------
-#if PCX_BATCHED_REPSUM_ONCE
     const double meanrep = rep_sum / (double)N;
-#else
-    const double meanrep = pw_rows(rep) / (double)N;
-#endif
     double u = fabs(nc_i * (rep / meanrep));
     double Su = pw_rows(u);
     // PCA: a NaN total leaves the reference's this_rep / smooth_rep fully MASKED (SPEC

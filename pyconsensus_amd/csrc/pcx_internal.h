@@ -205,7 +205,7 @@ struct BatchArgs {
     double *participation, *avg_certainty;
     int32_t *branch, *flags, *pi_iters, *components;
     double *original, *filled;
-    long long* stamps;  // diagnostic phase clocks [B][16] (PCX_STAMPS), normally NULL
+    long long* stamps;  // diagnostic phase clocks [B][32] (PCX_STAMPS), normally NULL
 };
 
 // One round of a ragged launch (rounds of different shapes in one launch of the one-wave round

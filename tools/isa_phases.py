@@ -3,7 +3,7 @@
     python tools/isa_phases.py                       # compile pcx_batched.hip, the 50 x 20 packed kernel
     python tools/isa_phases.py --kernel Li0ELi0ELb0ELb1E
     python tools/isa_phases.py --asm FILE.s          # an assembly listing made before (another revision's)
-    python tools/isa_phases.py --flags=-DPCX_BATCHED_ROWMASKS=0
+    python tools/isa_phases.py --flags=-DNAME=VALUE
 
 Compiles pyconsensus_amd/csrc/pcx_batched.hip to gfx950 assembly with the Makefile's flags, takes
 the kernel whose mangled name contains --kernel, and splits its text at the phase-stamp markers
