@@ -169,8 +169,8 @@ int pcx_consensus_batched_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_resul
 /* ------------------------------------------------------------------------ */
 typedef struct {
     int64_t n_rounds;
-    const int32_t* n_reporters;   /* HOST [B]: N_b in [1, 64]                                 */
-    const int32_t* n_events;      /* HOST [B]: E_b in [1, 32]                                 */
+    const int32_t* n_reporters;   /* HOST [B]: N_b in [1, 64]  (the wide entry: [1, 256])     */
+    const int32_t* n_events;      /* HOST [B]: E_b in [1, 32]  (the wide entry: [1, 64])      */
     const double*  reports;       /* DEVICE, round after round, each N_b x E_b row-major      */
     const double*  reputation;    /* DEVICE [sum N_b] or NULL (uniform)                       */
     const uint8_t* scaled;        /* DEVICE [sum E_b] or NULL (event_bounds None), with lo/hi */
@@ -192,6 +192,27 @@ int pcx_ragged_plan(int64_t n_rounds, const int32_t* n_reporters, const int32_t*
  * original / filled [sum N_b * E_b], the rest [B]; all in round order.  n_rounds == 0 succeeds and
  * launches nothing.  On a pcx_create_devices context the call runs on device_ids[0]. */
 int pcx_consensus_ragged_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_result* out);
+
+/* Wide ragged batches (added under ABI 9; detect by symbol): the same structs and layouts, rounds
+ * up to 256 x 64.  The rounds of at most 64 x 32 run on the one-wave kernel as above; the others on
+ * the workgroup-per-round kernel, one launch per launch class: the rounds per CU that a round's LDS
+ * allows (its dynamic LDS plus the kernel's static LDS in 1,280-byte units of 160 KiB, at most the
+ * kernel's three per CU).  The two entries above keep their limits and refusals.
+ *
+ * pcx_ragged_plan_wide is pure like pcx_ragged_plan: a round must lie within [1, 256] x [1, 64],
+ * k-means is refused.  counts[0] / lds_bytes[0]: the one-wave rounds and their launch's dynamic LDS;
+ * counts[c] / lds_bytes[c], c = 1..3: the workgroup rounds of launch class c and that launch's
+ * dynamic LDS (the class's largest round; 0 for an empty class).  Any output may be NULL. */
+int pcx_ragged_plan_wide(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int algorithm,
+                         int64_t totals[3], int64_t counts[4], int64_t lds_bytes[4], int64_t* bad_round);
+/* Asynchronous on the context's stream, no host wait of its own; n_rounds == 0 succeeds and
+ * launches nothing.  A batch of one-wave rounds only is pcx_consensus_ragged_f64 itself.  Each
+ * round's results are those of pcx_consensus_batched_f64 on its shape (the batched SPEC's order).
+ * The workgroup rounds use the context's per-round scratch in chunks of at most 2 GB; calls on one
+ * context share it, so they belong on one stream (as the workgroup route of the batched call).
+ * PCX_RAGGED_ONE_CLASS=1 in the environment (a diagnostic, read per call) runs every workgroup round
+ * in one launch at the largest round's LDS. */
+int pcx_consensus_ragged_wide_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_result* out);
 
 /* ------------------------------------------------------------------------ */
 /* Monte Carlo simulator (ABI >= 9): the Simulator.jl-style driver of the       */
@@ -484,6 +505,10 @@ int pcx_selftest_chunked_copy(int64_t bytes, int64_t chunk, int slots, int threa
  * makes its worker `worker` report PCX_ENOMEM for its first round without running it (the
  * hand-back path); -1 clears it.  Consumed by that call.  For the tests only. */
 int pcx_test_inject_enomem(pcx_ctx* ctx, int worker);
+/* Test hook: pcx_consensus_ragged_wide_f64 on `ctx` sizes its chunks of workgroup rounds to `bytes`
+ * of scratch in place of 2 GB (a chunk holds at least one round); 0 restores the default.  Stays
+ * set until changed.  For the tests only. */
+int pcx_test_scratch_cap(pcx_ctx* ctx, int64_t bytes);
 /* Dynamic LDS bytes one round of pcx_consensus_batched_f64 asks for (n_reporters <= 64, n_events
  * <= 32, algorithm as in pcx_batch): what bounds the rounds resident per CU (LDS is handed out in
  * 1,280-byte units of the CU's 160 KiB).  No device needed.  For the tests and the tools. */

@@ -79,9 +79,14 @@ def _declare(lib):
         ("pcx_simulate_f64", i32, [vp, C.POINTER(_abi.Sim), C.POINTER(_abi.SimResult)]),
         ("pcx_ragged_plan", i32, [i64, vp, vp, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
         ("pcx_consensus_ragged_f64", i32, [vp, C.POINTER(_abi.Ragged), C.POINTER(_abi.BatchResult)]),
+        ("pcx_ragged_plan_wide", i32, [i64, vp, vp, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64),
+                                       C.POINTER(i64)]),
+        ("pcx_consensus_ragged_wide_f64", i32, [vp, C.POINTER(_abi.Ragged), C.POINTER(_abi.BatchResult)]),
+        ("pcx_test_scratch_cap", i32, [vp, i64]),
     ]:
         if (name in ("pcx_batched_lds_bytes", "pcx_medium_lds_bytes", "pcx_batched_route", "pcx_ragged_plan",
-                     "pcx_consensus_ragged_f64")
+                     "pcx_consensus_ragged_f64", "pcx_ragged_plan_wide", "pcx_consensus_ragged_wide_f64",
+                     "pcx_test_scratch_cap")
                 and os.environ.get("PCX_LIB") and not hasattr(lib, name)):
             continue  # an A/B build of a revision before these queries (tools/ab_build.sh)
         f = getattr(lib, name)

@@ -9,7 +9,8 @@ Rounds of at most 64 reporters x 32 events run in one wavefront each of
 larger rounds run as single-matrix consensuses, many in flight on a pool of worker streams
 (csrc/pcx_rounds.cpp).  :func:`route` tells which of the three a shape takes.
 Rounds of DIFFERENT shapes (each at most 64 x 32) run in one launch of the one-wave kernel through
-:func:`consensus_ragged`.
+:func:`consensus_ragged`; with ``wide=True`` rounds up to 256 x 64 join them, on the ragged form of
+the workgroup kernel.
 """
 from __future__ import annotations
 
@@ -21,6 +22,8 @@ from . import _abi, _device, _lib
 
 MAX_REPORTERS = 64  # one wavefront per round up to here (and MAX_EVENTS)
 MAX_EVENTS = 32
+WIDE_MAX_REPORTERS = 256  # one workgroup per round up to here (and WIDE_MAX_EVENTS)
+WIDE_MAX_EVENTS = 64
 
 
 def kmeans_k(N):
@@ -233,15 +236,25 @@ def _ragged_vectors(seq, counts, dtype, what):
     return np.concatenate(parts) if parts else np.zeros(0, dtype=dtype)
 
 
-def ragged_plan(shapes, algorithm="PCA"):
+def ragged_plan(shapes, algorithm="PCA", wide=False):
     """(totals, lds_bytes) of a ragged batch of ``shapes`` [(N_b, E_b), ...]: totals = (sum N_b,
     sum E_b, sum N_b * E_b), the flat arrays' lengths, and the launch's dynamic LDS.  Needs no GPU;
-    raises PcxError naming the first round the one-wave kernel does not take (or k-means)."""
+    raises PcxError naming the first round the one-wave kernel does not take (or k-means).
+
+    ``wide=True``: rounds up to 256 x 64 (pcx_ragged_plan_wide); returns (totals, counts, lds_bytes)
+    with 4-tuples counts / lds_bytes: index 0 the rounds of at most 64 x 32 (the one-wave kernel's
+    launch), index c = 1..3 the workgroup kernel's rounds of launch class c -- c rounds per CU by
+    their LDS -- and that launch's dynamic LDS."""
     alg = _abi.ALGORITHMS.get(algorithm)
     if alg is None:
         raise NotImplementedError("algorithm %r is not on the GPU path" % (algorithm,))
     sh = np.ascontiguousarray(np.asarray(shapes, dtype=np.int32).reshape(-1, 2))
     n, e = np.ascontiguousarray(sh[:, 0]), np.ascontiguousarray(sh[:, 1])
+    if wide:
+        totals, counts, lds4, bad = (C.c_int64 * 3)(), (C.c_int64 * 4)(), (C.c_int64 * 4)(), C.c_int64(-1)
+        _lib.check(_lib.lib().pcx_ragged_plan_wide(len(sh), n.ctypes.data, e.ctypes.data, alg, totals, counts, lds4,
+                                                   C.byref(bad)))
+        return tuple(int(x) for x in totals), tuple(int(x) for x in counts), tuple(int(x) for x in lds4)
     totals, lds, bad = (C.c_int64 * 3)(), C.c_int64(0), C.c_int64(-1)
     _lib.check(_lib.lib().pcx_ragged_plan(len(sh), n.ctypes.data, e.ctypes.data, alg, totals, C.byref(lds),
                                           C.byref(bad)))
@@ -251,10 +264,15 @@ def ragged_plan(shapes, algorithm="PCA"):
 def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *, catch_tolerance=0.1, alpha=0.1,
                      int_dtype=False, algorithm="PCA", outputs=None, device=None, filled=False, original=False,
                      max_components=5, variance_threshold=0.9, aux_scores=None, hierarchy_threshold=0.5,
-                     cluster_threshold=None):
+                     cluster_threshold=None, wide=False):
     """Run B rounds of DIFFERENT shapes in one launch of the one-wave round kernel.
 
     reports:    a sequence of B arrays, round b an (N_b, E_b) matrix with N_b <= 64, E_b <= 32
+    wide:       True: rounds up to 256 x 64 (pcx_consensus_ragged_wide_f64).  Those above 64 x 32
+                run one workgroup each on the ragged form of ``medium_round_kernel``, one launch per
+                launch class (:func:`ragged_plan`); the others on the one-wave kernel as before.
+                Every round equals its own ``consensus_batched`` run.  Calls share one per-context
+                scratch: keep them on one stream
     reputation: a sequence of B vectors (N_b,) or None (uniform in every round)
     scaled/lo/hi: sequences of B vectors (E_b,) or None (every event binary)
     aux_scores: cokurtosis: a sequence of B vectors (N_b,)
@@ -293,7 +311,7 @@ def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *,
         if aux_scores is None:
             raise ValueError("cokurtosis needs aux_scores (aux['cokurt'] of every round)")
         aux = _ragged_vectors(aux_scores, ns, np.float64, "aux_scores")
-    totals, _ = ragged_plan(shapes, algorithm)  # refuses k-means and rounds above one wave, by index
+    totals = ragged_plan(shapes, algorithm, wide=wide)[0]  # refuses k-means and rounds past the limits, by index
     t = _device.require_gpu()
     dev = t.device(device) if device is not None else t.device("cuda", t.cuda.current_device())
     flat = np.concatenate([m.reshape(-1) for m in mats]) if B else np.zeros(0)
@@ -321,7 +339,8 @@ def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *,
         outs[name] = x
         setattr(res, name, x.data_ptr())
     h = _lib.bind_stream(dev.index, _device.current_stream_handle(dev))
-    _lib.check(_lib.lib().pcx_consensus_ragged_f64(h, C.byref(inp), C.byref(res)))
+    entry = _lib.lib().pcx_consensus_ragged_wide_f64 if wide else _lib.lib().pcx_consensus_ragged_f64
+    _lib.check(entry(h, C.byref(inp), C.byref(res)))
     zero = np.zeros(1, dtype=np.int64)
     outs["_packed"] = buf
     outs["_layout"] = layout

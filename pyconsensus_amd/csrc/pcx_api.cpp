@@ -419,19 +419,24 @@ static void print_medium_stamps(const std::vector<long long>& h, int64_t B) {
 }
 
 // one workgroup per round (pcx_medium.hip), in chunks of bounded scratch
+constexpr size_t MEDIUM_SCRATCH_CAP = (size_t)2 << 30;
+
+// the context's workgroup scratch (pcx_ctx.mscr) grown to `need` bytes; 0 = ok
+static int medium_scratch_reserve(pcx_ctx* ctx, size_t need) {
+    if (ctx->mscr_bytes >= need) return PCX_OK;
+    if (ctx->mscr) (void)hipFree(ctx->mscr);
+    ctx->mscr = nullptr;
+    ctx->mscr_bytes = 0;
+    const hipError_t e = hipMalloc(&ctx->mscr, need);
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc(medium scratch)");
+    ctx->mscr_bytes = need;
+    return PCX_OK;
+}
+
 static int run_workgroup_route(pcx_ctx* ctx, pcx::BatchArgs& a) {
-    const size_t cap = (size_t)2 << 30;
-    const int64_t chunk = pcx::medium_chunk(a, cap);
-    const size_t need = pcx::medium_scratch_per_round(a) * (size_t)chunk;
+    const int64_t chunk = pcx::medium_chunk(a, MEDIUM_SCRATCH_CAP);
+    if (const int rc = medium_scratch_reserve(ctx, pcx::medium_scratch_per_round(a) * (size_t)chunk)) return rc;
     hipError_t e = hipSuccess;
-    if (ctx->mscr_bytes < need) {
-        if (ctx->mscr) (void)hipFree(ctx->mscr);
-        ctx->mscr = nullptr;
-        ctx->mscr_bytes = 0;
-        e = hipMalloc(&ctx->mscr, need);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc(medium scratch)");
-        ctx->mscr_bytes = need;
-    }
     double* Fscr = (double*)ctx->mscr;
     double* Cscr = Fscr + (a.filled ? 0 : (size_t)chunk * a.N * a.E);
     double* Xscr = Cscr + (size_t)chunk * a.E * a.E;  // the clusterings' cluster sums / observations
@@ -487,8 +492,9 @@ int pcx_consensus_batched_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_resul
 }
 
 // ---------------------------------------------------------------- ragged batches
-int pcx_ragged_plan(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int algorithm,
-                    int64_t totals[3], int64_t* lds_bytes, int64_t* bad_round) {
+// what pcx_ragged_plan and pcx_ragged_plan_wide refuse alike, before they look at a round
+static int ragged_plan_checks(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int algorithm,
+                              int64_t* bad_round) {
     if (bad_round) *bad_round = -1;
     if (n_rounds < 0 || n_rounds > 0x7fffffff) return fail(PCX_EINVAL, "ragged: n_rounds must be in [0, 2^31)");
     if (algorithm < PCX_ALG_PCA || algorithm > PCX_ALG_CLUSTERFECK)
@@ -496,15 +502,24 @@ int pcx_ragged_plan(int64_t n_rounds, const int32_t* n_reporters, const int32_t*
     if (algorithm == PCX_ALG_KMEANS)
         return fail(PCX_EINVAL, "ragged: k-means is not supported (its code-book size depends on each round's N)");
     if (n_rounds > 0 && (!n_reporters || !n_events)) return fail(PCX_EINVAL, "ragged: n_reporters / n_events is NULL");
+    return PCX_OK;
+}
+
+static int ragged_bad_round(int64_t b, int N, int E, int max_n, int max_e, int64_t* bad_round) {
+    if (bad_round) *bad_round = b;
+    return fail(PCX_EINVAL, "ragged: round " + std::to_string(b) + " is " + std::to_string(N) + " x " +
+                                std::to_string(E) + "; a round must be within [1, " + std::to_string(max_n) +
+                                "] x [1, " + std::to_string(max_e) + "]");
+}
+
+int pcx_ragged_plan(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int algorithm,
+                    int64_t totals[3], int64_t* lds_bytes, int64_t* bad_round) {
+    if (const int rc = ragged_plan_checks(n_rounds, n_reporters, n_events, algorithm, bad_round)) return rc;
     int64_t tn = 0, te = 0, tc = 0;
     size_t lds = 0;
     for (int64_t b = 0; b < n_rounds; b++) {
         const int32_t N = n_reporters[b], E = n_events[b];
-        if (N < 1 || N > 64 || E < 1 || E > 32) {
-            if (bad_round) *bad_round = b;
-            return fail(PCX_EINVAL, "ragged: round " + std::to_string(b) + " is " + std::to_string(N) + " x " +
-                                        std::to_string(E) + "; a round must be within [1, 64] x [1, 32]");
-        }
+        if (N < 1 || N > 64 || E < 1 || E > 32) return ragged_bad_round(b, N, E, 64, 32, bad_round);
         tn += N;
         te += E;
         tc += (int64_t)N * E;
@@ -519,24 +534,13 @@ int pcx_ragged_plan(int64_t n_rounds, const int32_t* n_reporters, const int32_t*
     return PCX_OK;
 }
 
-int pcx_consensus_ragged_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_result* out) {
-    if (!ctx || !in || !out) return fail(PCX_EINVAL, "pcx_consensus_ragged_f64: null argument");
-    int64_t lds = 0;
-    if (const int rc = pcx_ragged_plan(in->n_rounds, in->n_reporters, in->n_events, in->algorithm, nullptr, &lds,
-                                       nullptr))
-        return rc;
-    if (in->n_rounds == 0) return PCX_OK;
-    // (max_components is capped at E_b per round on the device)
-    const bool bad_five = in->algorithm == PCX_ALG_BIG_FIVE && in->max_components < 1;
-    if (const int rc = check_options("ragged", in, bad_five ? "big-five needs max_components >= 1" : nullptr))
-        return rc;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    // the descriptor table: built in this call's staging slot, uploaded on the stream
-    const int64_t B = in->n_rounds;
-    const size_t bytes = (size_t)B * sizeof(pcx::RaggedDesc);
+// This call's staging slot (the two are taken in turn), with room for `bytes` on both sides and the
+// host side free to be rewritten: the slot's last upload has read it.  0 = ok.
+static int ragged_slot_take(pcx_ctx* ctx, size_t bytes, pcx_ctx::RaggedSlot** slot) {
+    hipError_t e = hipSuccess;
     pcx_ctx::RaggedSlot& s = ctx->rag[ctx->rag_next];
     ctx->rag_next ^= 1;
+    *slot = &s;
     if (s.used) {  // the slot's last upload has read the staging
         e = hipEventSynchronize(s.copy_ev);
         if (e != hipSuccess) return hip_fail(e, "ragged: hipEventSynchronize");
@@ -567,6 +571,39 @@ int pcx_consensus_ragged_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_resul
         }
         s.bytes = cap;
     }
+    return PCX_OK;
+}
+
+// The slot's first `bytes` from the staging to the device table on the stream, after any launch
+// that still reads the table (another stream's, maybe); copy_ev marks the staging read.
+static hipError_t ragged_slot_upload(pcx_ctx* ctx, pcx_ctx::RaggedSlot& s, size_t bytes) {
+    hipError_t e = hipSuccess;
+    if (s.used) e = hipStreamWaitEvent(ctx->stream, s.kern_ev, 0);
+    if (e == hipSuccess) e = hipMemcpyAsync(s.dev, s.pin, bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(s.copy_ev, ctx->stream);
+    if (e == hipSuccess) s.used = true;
+    return e;
+}
+
+int pcx_consensus_ragged_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_result* out) {
+    if (!ctx || !in || !out) return fail(PCX_EINVAL, "pcx_consensus_ragged_f64: null argument");
+    int64_t lds = 0;
+    if (const int rc = pcx_ragged_plan(in->n_rounds, in->n_reporters, in->n_events, in->algorithm, nullptr, &lds,
+                                       nullptr))
+        return rc;
+    if (in->n_rounds == 0) return PCX_OK;
+    // (max_components is capped at E_b per round on the device)
+    const bool bad_five = in->algorithm == PCX_ALG_BIG_FIVE && in->max_components < 1;
+    if (const int rc = check_options("ragged", in, bad_five ? "big-five needs max_components >= 1" : nullptr))
+        return rc;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    // the descriptor table: built in this call's staging slot, uploaded on the stream
+    const int64_t B = in->n_rounds;
+    const size_t bytes = (size_t)B * sizeof(pcx::RaggedDesc);
+    pcx_ctx::RaggedSlot* sp = nullptr;
+    if (const int rc = ragged_slot_take(ctx, bytes, &sp)) return rc;
+    pcx_ctx::RaggedSlot& s = *sp;
     pcx::RaggedDesc* d = static_cast<pcx::RaggedDesc*>(s.pin);
     int64_t cell = 0, row = 0, ev = 0;
     for (int64_t b = 0; b < B; b++) {
@@ -576,17 +613,138 @@ int pcx_consensus_ragged_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_resul
         row += N;
         ev += E;
     }
-    // (another stream's launch may still read this slot's table: the upload waits for it)
-    if (s.used) e = hipStreamWaitEvent(ctx->stream, s.kern_ev, 0);
-    if (e == hipSuccess) e = hipMemcpyAsync(s.dev, s.pin, bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipEventRecord(s.copy_ev, ctx->stream);
+    e = ragged_slot_upload(ctx, s, bytes);
     if (e != hipSuccess) return hip_fail(e, "ragged: descriptor upload");
-    s.used = true;
     pcx::BatchArgs a = shared_args(in, out);
     a.B = B;
     e = pcx::launch_ragged(a, static_cast<const pcx::RaggedDesc*>(s.dev), (size_t)lds, ctx->stream);
     if (e == hipSuccess) e = hipEventRecord(s.kern_ev, ctx->stream);
     return e == hipSuccess ? PCX_OK : hip_fail(e, "ragged_round_kernel launch");
+}
+
+// where a round of a wide ragged batch runs: 0 = the one-wave kernel, else the workgroup kernel's
+// launch class (pcx::medium_launch_class), or the one class of PCX_RAGGED_ONE_CLASS
+static int wide_slot(int N, int E, int algorithm, bool one_class) {
+    if (N <= 64 && E <= 32) return 0;
+    return one_class ? 1 : pcx::medium_launch_class(pcx::medium_lds_bytes(N, E, algorithm));
+}
+
+static int ragged_plan_wide(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int algorithm,
+                            bool one_class, int64_t totals[3], int64_t counts[4], int64_t lds_bytes[4],
+                            int64_t* bad_round) {
+    if (const int rc = ragged_plan_checks(n_rounds, n_reporters, n_events, algorithm, bad_round)) return rc;
+    int64_t tot[3] = {0, 0, 0}, cnt[4] = {0, 0, 0, 0};
+    size_t lds[4] = {0, 0, 0, 0};
+    for (int64_t b = 0; b < n_rounds; b++) {
+        const int32_t N = n_reporters[b], E = n_events[b];
+        if (N < 1 || N > 256 || E < 1 || E > 64) return ragged_bad_round(b, N, E, 256, 64, bad_round);
+        tot[0] += N;
+        tot[1] += E;
+        tot[2] += (int64_t)N * E;
+        const int k = wide_slot(N, E, algorithm, one_class);
+        cnt[k]++;
+        lds[k] = std::max(lds[k], k ? pcx::medium_lds_bytes(N, E, algorithm) : pcx::ragged_lds_bytes(N, E, algorithm));
+    }
+    for (int k = 0; k < 3 && totals; k++) totals[k] = tot[k];
+    for (int k = 0; k < 4 && counts; k++) counts[k] = cnt[k];
+    for (int k = 0; k < 4 && lds_bytes; k++) lds_bytes[k] = (int64_t)lds[k];
+    return PCX_OK;
+}
+
+int pcx_ragged_plan_wide(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int algorithm,
+                         int64_t totals[3], int64_t counts[4], int64_t lds_bytes[4], int64_t* bad_round) {
+    return ragged_plan_wide(n_rounds, n_reporters, n_events, algorithm, false, totals, counts, lds_bytes, bad_round);
+}
+
+int pcx_test_scratch_cap(pcx_ctx* ctx, int64_t bytes) {
+    if (!ctx || bytes < 0) return fail(PCX_EINVAL, "pcx_test_scratch_cap: null context or negative bytes");
+    ctx->test_scratch_cap = bytes;
+    return PCX_OK;
+}
+
+int pcx_consensus_ragged_wide_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_result* out) {
+    if (!ctx || !in || !out) return fail(PCX_EINVAL, "pcx_consensus_ragged_wide_f64: null argument");
+    const char* env = getenv("PCX_RAGGED_ONE_CLASS");  // diagnostic: every workgroup round in one launch
+    const bool one_class = env && env[0] == '1';
+    int64_t cnt[4], lds[4];
+    if (const int rc = ragged_plan_wide(in->n_rounds, in->n_reporters, in->n_events, in->algorithm, one_class, nullptr,
+                                        cnt, lds, nullptr))
+        return rc;
+    if (in->n_rounds == 0) return PCX_OK;
+    const int64_t B = in->n_rounds, nw = cnt[0], nm = B - nw;
+    if (nm == 0) return pcx_consensus_ragged_f64(ctx, in, out);  // wave-sized rounds only: that call as it is
+    // (max_components is capped at E_b per round on the device)
+    const bool bad_five = in->algorithm == PCX_ALG_BIG_FIVE && in->max_components < 1;
+    if (const int rc = check_options("ragged", in, bad_five ? "big-five needs max_components >= 1" : nullptr))
+        return rc;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    // One staging slot, one upload: the wave rounds' descriptors, the workgroup rounds' descriptors
+    // class after class (3, 2, 1; a class's rounds in their order), the wave rounds' indices.  The
+    // device side holds, past what is uploaded, the wave rounds' six [B] outputs until their scatter.
+    const size_t off_m = (size_t)nw * sizeof(pcx::RaggedDesc), off_i = off_m + (size_t)nm * sizeof(pcx::MediumDesc),
+                 bytes = (off_i + (size_t)nw * sizeof(int32_t) + 7) / 8 * 8, off_t = bytes;
+    pcx_ctx::RaggedSlot* sp = nullptr;
+    if (const int rc = ragged_slot_take(ctx, off_t + (size_t)nw * 32, &sp)) return rc;
+    pcx_ctx::RaggedSlot& s = *sp;
+    char* pin = static_cast<char*>(s.pin);
+    char* dev = static_cast<char*>(s.dev);
+    pcx::RaggedDesc* dw = reinterpret_cast<pcx::RaggedDesc*>(pin);
+    pcx::MediumDesc* dm = reinterpret_cast<pcx::MediumDesc*>(pin + off_m);
+    int32_t* idx = reinterpret_cast<int32_t*>(pin + off_i);
+    int64_t at[4] = {0, 0, 0, 0};  // next entry of each class in dm: class 3 first
+    at[2] = cnt[3];
+    at[1] = cnt[3] + cnt[2];
+    const int64_t first[4] = {0, at[1], at[2], at[3]};
+    int64_t cell = 0, row = 0, ev = 0, w = 0, stride[3] = {0, 0, 0};
+    for (int64_t b = 0; b < B; b++) {
+        const int32_t N = in->n_reporters[b], E = in->n_events[b];
+        const int k = wide_slot(N, E, in->algorithm, one_class);
+        if (k == 0) {
+            dw[w] = pcx::RaggedDesc{cell, row, ev, N, E};
+            idx[w++] = (int32_t)b;
+        } else {
+            dm[at[k]++] = pcx::MediumDesc{cell, row, ev, N, E, (int32_t)b, 0};
+            pcx::medium_slot_strides(N, E, in->algorithm, stride);
+        }
+        cell += (int64_t)N * E;
+        row += N;
+        ev += E;
+    }
+    // the workgroup scratch: slot strides of the call's largest round, chunks that fit the cap
+    const size_t cap = ctx->test_scratch_cap > 0 ? (size_t)ctx->test_scratch_cap : MEDIUM_SCRATCH_CAP;
+    const size_t per = (size_t)((out->filled ? 0 : stride[0]) + stride[1] + stride[2]) * sizeof(double);
+    const int64_t chunk = std::min<int64_t>(std::max<int64_t>((int64_t)(cap / per), 1), nm);
+    if (const int rc = medium_scratch_reserve(ctx, per * (size_t)chunk)) return rc;
+    double* Fscr = (double*)ctx->mscr;
+    double* Cscr = Fscr + (out->filled ? 0 : (size_t)chunk * stride[0]);
+    double* Xscr = Cscr + (size_t)chunk * stride[1];
+    e = ragged_slot_upload(ctx, s, bytes);
+    if (e != hipSuccess) return hip_fail(e, "ragged: descriptor upload");
+    pcx::BatchArgs a = shared_args(in, out);
+    a.B = B;
+    if (nw > 0) {
+        pcx::BatchArgs aw = a;
+        aw.B = nw;
+        const pcx::WaveTmp t = pcx::ragged_wave_tmp(dev + off_t, nw);
+        aw.participation = t.participation;
+        aw.avg_certainty = t.avg_certainty;
+        aw.branch = t.branch;
+        aw.flags = t.flags;
+        aw.pi_iters = t.pi_iters;
+        aw.components = t.components;
+        e = pcx::launch_ragged(aw, reinterpret_cast<const pcx::RaggedDesc*>(dev), (size_t)lds[0], ctx->stream);
+        if (e == hipSuccess)
+            e = pcx::launch_ragged_scatter(a, reinterpret_cast<const int32_t*>(dev + off_i), nw, dev + off_t,
+                                           ctx->stream);
+    }
+    const pcx::MediumDesc* ddm = reinterpret_cast<const pcx::MediumDesc*>(dev + off_m);
+    for (int k = 3; k >= 1 && e == hipSuccess; k--)
+        for (int64_t b0 = 0; b0 < cnt[k] && e == hipSuccess; b0 += chunk)
+            e = pcx::launch_ragged_medium(a, ddm + first[k] + b0, std::min<int64_t>(chunk, cnt[k] - b0), (size_t)lds[k],
+                                          stride, Fscr, Cscr, Xscr, ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(s.kern_ev, ctx->stream);
+    return e == hipSuccess ? PCX_OK : hip_fail(e, "ragged wide launch");
 }
 
 namespace {

@@ -235,6 +235,46 @@ int64_t medium_chunk(const BatchArgs& a, size_t scratch_bytes);
 hipError_t launch_medium(const BatchArgs& a, int64_t b0, int64_t nb, double* Fscr, double* Cscr, double* Xscr,
                          hipStream_t st);
 
+// One round of a ragged launch of the workgroup-per-round kernel (pcx_consensus_ragged_wide_f64):
+// RaggedDesc's offsets and shape, and the round's index in the caller's [B] outputs -- a launch
+// holds the rounds of one launch class, so workgroup k is not round k.
+struct MediumDesc {
+    int64_t cell, row, ev;
+    int32_t N, E;
+    int32_t round;
+    int32_t pad_;
+};
+static_assert(sizeof(MediumDesc) == 40, "ragged workgroup descriptor");
+// static LDS of the workgroup kernel's four instantiations (sh, scal, the scaled-event list, the
+// Jacobi pair tables; profiles/ragged_wide/resources.txt), which a workgroup holds on top of its
+// dynamic LDS
+constexpr size_t MEDIUM_STATIC_LDS = 4288;
+// launch class of a round with `dyn_lds` bytes of dynamic LDS: the rounds per CU that LDS allows
+// (1,280-byte allocation units of 160 KiB) under the kernel's three-per-CU register budget: 3, 2 or 1
+int medium_launch_class(size_t dyn_lds);
+// s = max(s, {N E, E E, medium_xscratch}): the scratch slot strides (doubles) of a launch holding the round
+void medium_slot_strides(int N, int E, int algorithm, int64_t s[3]);
+// `nb` workgroups over desc[0 .. nb), dynamic LDS `lds` (the largest round's), slot strides s
+hipError_t launch_ragged_medium(const BatchArgs& a, const MediumDesc* desc, int64_t nb, size_t lds, const int64_t s[3],
+                                double* Fscr, double* Cscr, double* Xscr, hipStream_t st);
+// where the one-wave kernel writes the six [B] outputs of n wave-sized rounds that share a batch
+// with workgroup rounds (32 n bytes at `base`), and their scatter to the rounds' indices idx[k]
+struct WaveTmp {
+    double *participation, *avg_certainty;
+    int32_t *branch, *flags, *pi_iters, *components;
+};
+inline WaveTmp ragged_wave_tmp(void* base, int64_t n) {
+    WaveTmp t;
+    t.participation = static_cast<double*>(base);
+    t.avg_certainty = t.participation + n;
+    t.branch = reinterpret_cast<int32_t*>(t.avg_certainty + n);
+    t.flags = t.branch + n;
+    t.pi_iters = t.flags + n;
+    t.components = t.pi_iters + n;
+    return t;
+}
+hipError_t launch_ragged_scatter(const BatchArgs& a, const int32_t* idx, int64_t n, void* tmp, hipStream_t st);
+
 // ---------------------------------------------------------------- Monte Carlo simulator (pcx_sim.hip)
 // one timestep's rounds on the device / on the host (the same inline generator, pcx_sim.h)
 hipError_t launch_sim_generate(const sim::Gen& g, int64_t B, int64_t N, int64_t E, uint32_t t,
@@ -386,6 +426,9 @@ struct pcx_ctx {
     // test hook (pcx_test_inject_enomem): the round scheduler's worker k reports PCX_ENOMEM for
     // its first round of the NEXT batched call, without running it; -1 = off; consumed by that call
     int test_enomem_worker = -1;
+    // test hook (pcx_test_scratch_cap): bytes of workgroup scratch pcx_consensus_ragged_wide_f64
+    // chunks its rounds under, in place of 2 GB; 0 = the default
+    int64_t test_scratch_cap = 0;
     // pinned staging slots of the host-memory path's large output copies (pcx_runner.cpp)
     void* pinned = nullptr;
     size_t pinned_bytes = 0;

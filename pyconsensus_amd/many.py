@@ -10,13 +10,14 @@ from __future__ import annotations
 import numpy as np
 
 from . import _abi
-from .batched import MAX_EVENTS, MAX_REPORTERS, consensus_ragged, ragged_round, ragged_to_host
+from .batched import (MAX_EVENTS, MAX_REPORTERS, WIDE_MAX_EVENTS, WIDE_MAX_REPORTERS, consensus_ragged, ragged_round,
+                      ragged_to_host)
 from .oracle import Oracle
 
 _SHARED = ("catch_tolerance", "alpha", "algorithm", "variance_threshold", "hierarchy_threshold", "device")
 
 
-def consensus_many(problems, **oracle_kwargs):
+def consensus_many(problems, wide=False, **oracle_kwargs):
     """Run every problem's ``Oracle(**problem, **oracle_kwargs).consensus()``.
 
     problems: a sequence of dicts of Oracle constructor arguments (``reports``, ``event_bounds``,
@@ -24,7 +25,16 @@ def consensus_many(problems, **oracle_kwargs):
     Returns the list of result dicts, in order; each equals that problem's own
     ``Oracle(...).consensus()`` in values and container types (the dicts are built by the same code).
     A problem above 64 x 32, and every problem under ``algorithm="k-means"`` (whose restarts draw from
-    numpy's global RandomState call by call), goes through ``Oracle`` itself, in list order."""
+    numpy's global RandomState call by call), goes through ``Oracle`` itself, in list order.
+
+    wide=True: problems up to 256 x 64 join the ragged groups as well (``consensus_ragged(wide=True)``,
+    one workgroup per such problem; ``last_info["path"] == "ragged"``); k-means and larger problems
+    still go through ``Oracle``.  What changes for a problem above 64 x 32: it runs in the batched
+    SPEC's operation order -- what ``consensus_batched`` gives that shape -- where ``Oracle`` gives it
+    the single-matrix pipeline's order.  Its discrete outputs are equal; its continuous ones agree
+    within the parity tolerances of the test suite (tests/parity.py), not bit for bit -- which is why
+    the keyword is opt-in."""
+    max_n, max_e = (WIDE_MAX_REPORTERS, WIDE_MAX_EVENTS) if wide else (MAX_REPORTERS, MAX_EVENTS)
     oracles = [Oracle(**p, **oracle_kwargs) for p in problems]
     results = [None] * len(oracles)
     groups, alone = {}, []
@@ -32,7 +42,7 @@ def consensus_many(problems, **oracle_kwargs):
         if o.algorithm not in _abi.ALGORITHMS:
             raise NotImplementedError("algorithm %r is not on the GPU path (supported: %s)"
                                       % (o.algorithm, ", ".join(sorted(_abi.ALGORITHMS))))
-        if (o.num_reports > MAX_REPORTERS or o.num_events > MAX_EVENTS or o.algorithm == "k-means"
+        if (o.num_reports > max_n or o.num_events > max_e or o.algorithm == "k-means"
                 or o.num_reports < 1 or o.num_events < 1 or o.devices is not None):
             alone.append(i)
             continue
@@ -58,7 +68,7 @@ def consensus_many(problems, **oracle_kwargs):
                                int_dtype=first._int_dtype, algorithm=first.algorithm,
                                catch_tolerance=first.catch_tolerance, alpha=first.alpha, max_components=key[3],
                                variance_threshold=first.variance_threshold,
-                               hierarchy_threshold=first.hierarchy_threshold, device=first.device, **kw)
+                               hierarchy_threshold=first.hierarchy_threshold, device=first.device, wide=wide, **kw)
         host = ragged_to_host(out)  # the group's one copy back
         for b, i in enumerate(idx):
             g = ragged_round(host, b)
