@@ -375,12 +375,15 @@ static void print_wave_stamps(const std::vector<long long>& h, int64_t B) {
         }
     fprintf(stderr, "PCX_STAMPS mean cycles per phase:");
     for (int k = 1; k < no; k++) fprintf(stderr, " %d:%.0f", order[k], acc[order[k]] / (double)B);
-    double sort = 0, walk = 0;
+    double sort = 0, walk = 0, fast = 0, slow = 0;  // 22, 23: outcome medians by the fill-group test / sorted
     for (int64_t b = 0; b < B; b++) {
         sort += (double)h[b * 32 + 20];
         walk += (double)h[b * 32 + 21];
+        fast += (double)h[b * 32 + 22];
+        slow += (double)h[b * 32 + 23];
     }
-    fprintf(stderr, " median_sort:%.0f median_walk:%.0f\n", sort / (double)B, walk / (double)B);
+    fprintf(stderr, " median_sort:%.0f median_walk:%.0f outcome_shortcut:%.4f outcome_sorted:%.4f\n", sort / (double)B,
+            walk / (double)B, fast / (double)B, slow / (double)B);
 }
 
 // PCX_STAMPS, workgroup kernel: stamps 0..15 in program order (pcx_medium.hip MSTAMP(k))

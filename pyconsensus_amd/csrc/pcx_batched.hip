@@ -452,16 +452,13 @@ __device__ __forceinline__ uint32_t key_hi32(double x) {
     return (uint32_t)(u >> 32);
 }
 
-// use_rank (wave-uniform): `rank` is already each selected lane's count of selected keys below
-// its own (the rank loop is skipped); rank_out: when the rank loop runs, each lane's count
-// wlazy: Wtot is not given; weightedstats' total (the selected weights summed in row order, an
-// absent row adding +0.0) is formed only where a decision needs it.  A tree-order total Wt differs
-// from it by < (N + 6) u Wt, so every comparison against mid = Wt / 2 that clears the slack
-// 2^-45 Wt is the one the exact total would make.
+// weightedstats' total (the selected weights summed in row order, an absent row adding +0.0) is
+// formed only where a decision needs it.  A tree-order total Wt differs from it by < (N + 6) u Wt,
+// so every comparison against mid = Wt / 2 that clears the slack 2^-45 Wt is the one the exact
+// total would make.
 template <int NR>
-__device__ PCX_OUTLINE double wave_wmedian_rank(double x, double w, bool sel, double Wtot, int N, double* scr,
-                                                    long long* prof = nullptr, bool use_rank = false, int rank = 0,
-                                                    int* rank_out = nullptr, bool wlazy = false) {
+__device__ PCX_OUTLINE double wave_wmedian_rank(double x, double w, bool sel, int N, double* scr,
+                                                    long long* prof = nullptr) {
     const int l = lane_id();
     double *ox = scr, *ow = scr + NR;
     int* cnt = reinterpret_cast<int*>(scr + NR + med_ow(NR));
@@ -476,11 +473,9 @@ __device__ PCX_OUTLINE double wave_wmedian_rank(double x, double w, bool sel, do
         slack = 0.0;
         return t;
     };
-    if (wlazy) {
-        Wtot = tree_sum(sel ? w : 0.0);
-        slack = 0x1p-45 * Wtot;
-        if (!(slack < __builtin_inf()) || ballot(sel && fabs(w - 0.5 * Wtot) <= slack)) Wtot = exact_total();
-    }
+    double Wtot = tree_sum(sel ? w : 0.0);
+    slack = 0x1p-45 * Wtot;
+    if (!(slack < __builtin_inf()) || ballot(sel && fabs(w - 0.5 * Wtot) <= slack)) Wtot = exact_total();
     double mid = 0.5 * Wtot;
     if (ballot(sel && w > mid)) {  // weightedstats: a weight above half the total wins outright
         const double mx = wave_max(sel ? w : -__builtin_inf());
@@ -506,15 +501,10 @@ __device__ PCX_OUTLINE double wave_wmedian_rank(double x, double w, bool sel, do
     for (int q = l; q < med_ow(NR); q += 64) ow[q] = 0.0;  // slots past n add +0.0 in the walk
     wsync();
     int r = 0;
-    if (use_rank) {
-        r = rank;
-    } else {
 #pragma unroll
-        for (int m = 0; m < NR; m++) {
-            if (NR == 64 && m >= N) break;
-            r += kx[m] < key ? 1 : 0;
-        }
-        if (rank_out) *rank_out = r;
+    for (int m = 0; m < NR; m++) {
+        if (NR == 64 && m >= N) break;
+        r += kx[m] < key ? 1 : 0;
     }
     if (sel) atomicAdd(&cnt[r], 1);
     wsync();
@@ -548,9 +538,7 @@ __device__ PCX_OUTLINE double wave_wmedian_rank(double x, double w, bool sel, do
     // the current group's dependent adds
     double cum = 0.0, before = 0.0;
     int k = 0;
-    double v[8];
-#pragma unroll
-    for (int q = 0; q < 8; q++) v[q] = ow[q];
+    double v[8];  // (the walk's first group: loaded by the branches that walk, the scan-decided case reads none)
     bool walked = false;
     if (!ballot(sel && !(w >= 0.0))) {
         // non-negative weights.  First the prefix sums of the sorted weights in a tree order
@@ -578,6 +566,10 @@ __device__ PCX_OUTLINE double wave_wmedian_rank(double x, double w, bool sel, do
     if (!walked && slack != 0.0) {  // a near tie: the walk needs the exact total
         Wtot = exact_total();
         mid = 0.5 * Wtot;
+    }
+    if (!walked) {
+#pragma unroll
+        for (int q = 0; q < 8; q++) v[q] = ow[q];
     }
     if (walked) {
     } else if (!ballot(sel && !(w >= 0.0))) {

@@ -160,11 +160,6 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
     // ---- a3: interpolation guesses (:284-313), column phase ----------------
     uint64_t miss_j = 0;
     if (col) miss_j = S.miss[l];
-    constexpr int RKW = (ET > 0 ? ET + 3 : EMAX) / 4;  // interpolation-median ranks, a byte per column
-    uint32_t rkq[RKW];
-#pragma unroll
-    for (int k = 0; k < RKW; k++) rkq[k] = 0;
-    uint32_t rk_valid = 0;
     {
         // tot: the SPEC's sequential sum of the present reputations (a missing row adds
         // +0.0, which leaves a sum that starts at +0.0 unchanged).  A binary column's
@@ -215,38 +210,28 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
     // scaled columns with missing reports: weighted median of the present values
     {
         uint64_t todo = ballot(col && scj && miss_j != 0);
-        // the (x, w) pairs of interpolation median j: present reports, rep / tot (:292-303);
-        // Wsum = weightedstats' sum(weights), sequential in row order (absent rows add +0.0,
-        // which leaves a sum from +0.0 unchanged)
-        auto pair_of = [&](int j, double& x, double& w, bool& present, double& Wsum) {
+        // the (x, w) pairs of interpolation median j: present reports, rep / tot (:292-303).
+        // weightedstats' sum(weights), sequential in row order (absent rows add +0.0, which leaves
+        // a sum from +0.0 unchanged), is formed inside the median only where a decision needs it
+        auto pair_of = [&](int j, double& x, double& w, bool& present) {
             const uint64_t mj = S.miss[j];
             present = row && !((mj >> l) & 1);
             const double tot = S.tot[j];
             x = row ? S.F[l * ES + j] : 0.0;
             w = present ? S.rep[l] / tot : 0.0;
-            Wsum = 0.0;  // (formed inside the median only where a decision needs it: wlazy)
         };
         auto finish = [&](int j, double g) {
             if (a.int_dtype) g = trunc(g);
             if (l == 0) S.guess[j] = g;
         };
-        // one median at a time: the scratch lives in M, dead until the covariance.  Each lane's
-        // rank among the present keys is kept (one byte per column) for the outcome median of the
-        // same column, whose keys are these plus the fill's (a8 below: no second rank loop)
+        // one median at a time: the scratch lives in M, dead until the covariance
         while (todo) {
             const int j = __builtin_ctzll(todo);
             todo &= todo - 1;
-            double x0, w0, W0;
+            double x0, w0;
             bool p0;
-            pair_of(j, x0, w0, p0, W0);
-            int rk = -1;
-            finish(j, wave_wmedian_rank<(NT > 0 ? NT : 64)>(x0, w0, p0, W0, N, S.M, a.stamps ? mprof : nullptr,
-                                                            false, 0, &rk, true));
-            if (ballot(rk >= 0)) {  // the rank loop ran (no dominant weight, no NaN)
-                rk_valid |= 1u << j;
-                const int sh = 8 * (j & 3);
-                rkq[j >> 2] = (rkq[j >> 2] & ~(0xffu << sh)) | ((uint32_t)(rk & 0xff) << sh);
-            }
+            pair_of(j, x0, w0, p0);
+            finish(j, wave_wmedian_rank<(NT > 0 ? NT : 64)>(x0, w0, p0, N, S.M, a.stamps ? mprof : nullptr));
             wsync();
         }
     }
@@ -365,8 +350,12 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
         } else {
             // start: the column with the largest diagonal entry (first max; C is finite here)
             const double dg = col ? S.C[sym_at<PK>(l, l, ES)] : -__builtin_inf();
-            // (the lanes from E on hold -inf, below every finite entry: live rows only)
-            const int kd = __builtin_ctzll(ballot(col && dg == wave_max<CR>(dg)));
+            // (the lanes from E on hold -inf, below every finite entry: live rows only).  The maximum
+            // is formed by the whole wave, outside the `col &&`: on its right-hand side the DPP steps
+            // ran with the lanes from E on switched off and read 0.0 for them, above every entry
+            // when the whole diagonal is negative (a negative reputation), and no lane matched.
+            const double dgmax = wave_max<CR>(dg);
+            const int kd = __builtin_ctzll(ballot(col && dg == dgmax));
             double x0 = col ? S.C[sym_at<PK>(l, kd, ES)] : 0.0;
             const double n0 = sqrt(tree_sum<CR>(x0 * x0));  // squares, +0.0 from lane E on: no row sum is -0.0
             xv = col ? x0 / n0 : 0.0;
@@ -620,34 +609,51 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
     double rawj = col ? ob_vecmat(S.smooth, S.F + l, ES, N, E, l) : 0.0;  // np.dot(smooth_rep, F) (:510)
     STAMP(15);
     if (scaled_mask) {
-        const double Wsm = [&] {  // builtin sequential sum of smooth_rep (weightedstats)
-            double w = 0.0;
-            if (l == 0)
-                for (int i = 0; i < N; i++) w += S.smooth[i];
-            return bcast(w, 0);
-        }();
-        uint64_t todo = scaled_mask;
-        while (todo) {  // scratch in M, dead after the scores
+        // The fill-group test (DESIGN.md 5.2).  A scaled column with missing rows holds its fill g in
+        // every one of them, and smooth_rep stays close to rep, whose median of the present rows g is:
+        // the rows equal to g almost always straddle half the weight.  With the tree-order sums
+        //   Wt = sum w,  below = sum w [x < g],  group = sum w [x == g]
+        // (each within (N + 6) u Wt of the SPEC's sequential sum over the same rows) and the margin
+        // M of the scan-decided walk (wave_wmedian_rank), below <= Wt / 2 - M and below + group >
+        // Wt / 2 + M place the SPEC's crossing inside the group: the median is g bit for bit, with no
+        // sort.  The SPEC's earlier exits come first, in its order, wherever the data is near one: a
+        // weight within the slack of half the total or above it (the dominant exit compares against
+        // the exact total), no positive weight, a NaN or a negative weight (the sums are not monotone),
+        // a NaN value, and a fill that is NaN, zero (the group may mix -0.0 and +0.0) or so large that
+        // g + g overflows in the two-value mean.  Every such column takes wave_wmedian_rank.
+        const double Wt = tree_sum(row ? smooth_i : 0.0);
+        const double mid = 0.5 * Wt, slack = 0x1p-45 * Wt;
+        const double Mg = 0x1p-44 * Wt + slack + DBL_EPS;
+        // the weights' conditions hold for every column of the round (a NaN weight fails both compares)
+        const bool wok = Mg < __builtin_inf() && !ballot(row && !(smooth_i >= 0.0 && smooth_i < mid - slack)) &&
+                         ballot(row && smooth_i > 0.0) != 0;
+        uint64_t slow = 0;  // the columns the test does not decide
+        for (uint64_t todo = scaled_mask; todo; todo &= todo - 1) {  // (no LDS write, no wave barrier)
             const int j = __builtin_ctzll(todo);
-            todo &= todo - 1;
             const double x0 = row ? S.F[l * ES + j] : 0.0;
-            // the filled column's keys are the interpolation median's (present rows) plus the
-            // fill's (missing rows, all equal): a present row's count of smaller keys is its
-            // recorded one plus the missing rows when the fill's key is below its own, a missing
-            // row's is the present keys below the fill's -- the same counts the loop would make
-            const bool reuse = (rk_valid >> j) & 1;
-            int rk = 0;
-            if (reuse) {
-                const uint64_t mj = S.miss[j];
-                const bool ms = (mj >> l) & 1;
-                const uint32_t key = key_hi32(x0);
-                const uint32_t kg = (uint32_t)__builtin_amdgcn_readlane((int)key, __builtin_ctzll(mj));
-                const int below = popc(ballot(row && !ms && key < kg));
-                const int own = (int)((rkq[j >> 2] >> (8 * (j & 3))) & 0xffu);
-                rk = ms ? below : own + (kg < key ? popc(mj) : 0);
+            const uint64_t mj = (uint64_t)uniform64((int64_t)S.miss[j]);
+            bool decided = false;
+            if (wok && mj) {
+                const double g = bcast(x0, __builtin_ctzll(mj));  // the first missing row's: the fill
+                if (g != 0.0 && fabs(g) < 0x1p1023 && !ballot(row && x0 != x0)) {  // (a NaN g fails the second)
+                    const double below = tree_sum(row && x0 < g ? smooth_i : 0.0);
+                    const double group = tree_sum(row && x0 == g ? smooth_i : 0.0);
+                    decided = below <= mid - Mg && below + group > mid + Mg;
+                    if (decided && l == j) rawj = g;
+                }
             }
-            const double m = wave_wmedian_rank<(NT > 0 ? NT : 64)>(x0, smooth_i, row, Wsm, N, S.M,
-                                                                   a.stamps ? mprof : nullptr, reuse, rk);
+            if (!decided) slow |= 1ull << j;
+        }
+        if (a.stamps && l == 0) {  // diagnostic counters: plain stores, no clock read
+            a.stamps[b * 32 + 22] = popc(scaled_mask) - popc(slow);
+            a.stamps[b * 32 + 23] = popc(slow);
+        }
+        while (slow) {  // scratch in M, dead after the scores
+            const int j = __builtin_ctzll(slow);
+            slow &= slow - 1;
+            const double x0 = row ? S.F[l * ES + j] : 0.0;
+            // (weightedstats' sequential total of smooth_rep is formed inside only where a decision needs it)
+            const double m = wave_wmedian_rank<(NT > 0 ? NT : 64)>(x0, smooth_i, row, N, S.M, a.stamps ? mprof : nullptr);
             if (l == j) rawj = m;
             wsync();
         }
