@@ -111,7 +111,7 @@ struct limbs3 {
 // fit a uint64.  Outside it the limbs are wrong -- f0 = floor(w 2^35) reaches 2^52 at w = 2^17,
 // and a negative w has no limbs at all -- so k_sel_start sends any event whose weights leave
 // [0, 2^8) (a negative reputation, or one above 256 times the total) to the exact replay in the
-// reference's order instead (pcx_matrix.hip, the weight-range test; tests/test_matrix_gpu.py
+// reference's order instead (pcx_mat_select.hip, the weight-range test; tests/test_matrix_gpu.py
 // negative / large reputation cases).
 __device__ __forceinline__ uint64_t limb_bits(double f) {
     return (uint64_t)__double_as_longlong(f + 0x1p52) & 0xFFFFFFFFFFFFFull;

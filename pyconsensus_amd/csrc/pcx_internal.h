@@ -13,8 +13,8 @@
 
 // Kernel-side view of one single-matrix consensus on one rank: problem, scratch and
 // outputs as device pointers (built by pcx_runner.cpp, passed by value to every
-// kernel of pcx_matrix.hip).  Internal: the public boundary is pcx_problem /
-// pcx_result (include/pcx.h).
+// kernel of pcx_matrix.hip and pcx_mat_*.hip; the slots of its buffers: pcx_mat_layout.h).
+// Internal: the public boundary is pcx_problem / pcx_result (include/pcx.h).
 typedef struct {
     /* shape and parameters */
     int64_t n_rows;               /* rows held by this rank                       */
@@ -55,15 +55,15 @@ typedef struct {
     double*   cmax;               /* [world][E][4] per-rank max rep / argmax / min / max */
     double*   scal;               /* [world][16][2] per-rank scalar sums (dd)      */
     double*   spart;              /* [4096][4][2] row-pass block partials          */
-    double*   ev;                 /* [16][E] event vectors (guess, mu, old, ...)   */
+    double*   ev;                 /* [EV_NSLOT][E] event vectors (guess, mu, old, ...) */
     double*   cslab;              /* [cov_kslices][E][E] covariance partial tiles  */
     double*   C;                  /* [E][E] covariance                             */
     double*   Mw;                 /* [2][E][E] power-iteration working matrices    */
-    double*   pvec;               /* [4][E + 64] power-iteration scratch           */
-    double*   rowv;               /* [6][n_rows] scores, this, smooth, u, ...       */
+    double*   pvec;               /* [PV_NROW][pv_stride(E)] power-iteration scratch */
+    double*   rowv;               /* [RV_NSLOT][n_rows] scores, this, smooth, u, ... */
     uint32_t* rowstat;            /* [n_rows][2] NaN / zero counts per row         */
     uint64_t* skey;               /* [world][4] score min/max keys, flags          */
-    int64_t*  info;               /* [16] host-visible status (branch, iterations, counts) */
+    int64_t*  info;               /* [IN_NSLOT] host-visible status (branch, iterations, counts) */
     /* weighted-median selection: per scaled event (reduced over ranks by SUM / MIN / MAX) */
     uint64_t* sel_state;          /* [n_scaled][SELS] range, sums, mode, result    */
     uint64_t* sel_isum;           /* [n_scaled][4] total weight limbs, count       (SUM) */
@@ -302,7 +302,7 @@ const char* stage_name(int k);
 constexpr int SEL_NB = 256;         // selection buckets per pass
 constexpr int SEL_EXACT_MAX = 8192; // one-block exact replay of weightedstats (one rank)
 
-// launch one stage (pcx_matrix.hip)
+// launch one stage (pcx_matrix.hip; the M_SEL_* stages: pcx_mat_select.hip)
 hipError_t mat_stage(pcx_mat& m, int stage, hipStream_t stream, std::string& err);
 
 // hard replay of weightedstats / the interpolation mean in the reference's sequential float
@@ -358,14 +358,9 @@ enum cluster_step { CL_WTOK = 0, CL_MU, CL_X_WCD, CL_X_F, CL_WHITEN, CL_HIER, CL
 hipError_t cluster_stage(pcx_mat& m, const ClusterArgs& a, int step, hipStream_t st, std::string& err);
 hipError_t sel_hist(pcx_mat& m, int n_active, hipStream_t st);
 hipError_t sel_step(pcx_mat& m, int n_active, hipStream_t st);
-// info[] slots read by the runner
-enum info_slot_pub { INFO_BRANCH = 0, INFO_PI_ITERS = 1, INFO_FLAGS = 2, INFO_SEL_ACTIVE = 3, INFO_SEL_ARGMAX = 4,
-                     INFO_PICK1 = 5, INFO_HARD = 6, INFO_SEL_WACTIVE = 7, INFO_COV_GENERAL = 8,
-                     INFO_COV_MIXED = 9, INFO_COV_TOK1 = 10, INFO_COV_GUARD = 12, INFO_COV_GUARD_COLS = 13,
-                     INFO_COV_GUARD_BOUND = 14 };
 // the covariance guard's sums per general position (pcx_mat.gacc / gsum rows)
 enum cov_guard_stat { G_L1D = 0, G_L1E, G_SD, G_SD2, G_SE, G_SE2, G_NSTAT };
-// the covariance guard's outcome (info[INFO_COV_GUARD], pcx_result.cov_guard)
+// the covariance guard's outcome (info[IN_COV_GUARD], pcx_result.cov_guard)
 enum cov_guard_mode { COV_GUARD_PASS = 0, COV_GUARD_PAIRS = 1, COV_GUARD_FP64 = 2 };
 hipError_t tri_pack(const double* C, double* buf, int64_t E, int unpack, hipStream_t st);
 

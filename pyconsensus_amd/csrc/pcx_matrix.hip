@@ -21,6 +21,10 @@
 // Per-rank partial results are written into slot [rank] of [world][...] buffers;
 // the host all-reduces (SUM) them between stages and the next stage combines the
 // ranks in rank order, so results do not depend on the communication algorithm.
+//
+// The weighted-median selection and its hard replay have translation units of their own,
+// pcx_mat_select.hip and pcx_mat_hard.hip; pcx_mat_device.h holds what they share with this file and
+// pcx_mat_layout.h the slots of the shared buffers, for the kernels and the runner.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -39,95 +43,11 @@
 #include "pcx_device.h"
 #include "pcx_gemm_i8.h"
 #include "pcx_internal.h"
+#include "pcx_mat_device.h"
 #include "pcx_seqsum.h"
 
 namespace pcx {
 namespace {
-
-constexpr int CS = 16;           // dd slots per column in cstat
-constexpr int SS = 16;           // dd slots in scal
-constexpr int NB = SEL_NB;       // selection buckets
-// rows per load batch of the weight-mode column passes, and the minimum waves per SIMD their
-// registers are held to (build parameters for A/B runs).  Measured at C5 (round 6, the phase-2
-// first pass): 8 rows, 107 VGPRs, 3.85-3.98 ms; 12 rows (139 VGPRs, 3 waves) 7.44 ms; 16 rows
-// (171 VGPRs, 2 waves) 7.77 ms, or held to 4 waves (58 VGPRs spilled) 7.65 ms.
-#ifndef PCX_SEL_WUNROLL
-#define PCX_SEL_WUNROLL 8
-#endif
-constexpr int SEL_WUNROLL = PCX_SEL_WUNROLL;
-#ifndef PCX_SEL_WWAVES
-#define PCX_SEL_WWAVES 1
-#endif
-constexpr int SEL_HC = 2;  // copies of each k_sel_hist bucket (4: 12.3 vs 9.0 ms at C5; 1: 9.37 vs 8.66 ms, round 5)
-constexpr int SELS = 40;         // sel_state words per scaled event
-constexpr int BT = 256;          // threads per block for row/column passes
-constexpr int CM = 8;            // doubles per column in mpart / cmax
-
-enum ev_slot { EV_GUESS = 0, EV_MU, EV_OLD, EV_LD, EV_D1, EV_D2, EV_RAW, EV_ADJ, EV_FIN, EV_CERT, EV_PC,
-               EV_MINX, EV_MAXX, EV_MISS, EV_NZERO, EV_SPARE, EV_LDP, EV_K, EV_MUP };  // (pcx_runner.cpp: EV_SLOTS)
-enum row_slot { RV_S = 0, RV_U, RV_THIS, RV_SMOOTH, RV_N1, RV_N2 };
-enum scal_slot { SC_TOK = 0, SC_REP, SC_A1, SC_A1P, SC_A2, SC_A2P, SC_U, SC_UP, SC_AR, SC_ARP, SC_BIGTOK, SC_MAXTOK };
-enum info_slot { IN_BRANCH = 0, IN_PI_ITERS, IN_FLAGS, IN_SEL_ACTIVE, IN_SEL_ARGMAX, IN_PICK1, IN_HARD, IN_SEL_WACTIVE,
-                 IN_COV_GENERAL, IN_COV_MIXED, IN_COV_TOK1, IN_SEL_WLIMB, IN_COV_GUARD, IN_COV_GUARD_COLS,
-                 IN_COV_GUARD_BOUND };  // (word 15: M_POWER's squaring scratch)
-static_assert((int)IN_COV_GUARD == (int)INFO_COV_GUARD && (int)IN_COV_GUARD_COLS == (int)INFO_COV_GUARD_COLS &&
-                  (int)IN_COV_GUARD_BOUND == (int)INFO_COV_GUARD_BOUND,
-              "info slots");
-
-// ------------------------------------------------------------------ element transform
-struct ColParam {
-    bool scaled;
-    double lo, range, guess, mu;
-    double rr;  // RN(1 / range); NaN when range lies outside [2^-100, 2^100] (quotients then divide)
-};
-
-// d / b correctly rounded from y = RN(1 / b) (Markstein: q0 = RN(d y) is faithful, the residual
-// d - b q0 is exact in one fma, and RN(q0 + r y) = RN(d / b)), in 4 fp64 ops where the IEEE
-// division sequence (div_scale x2, rcp, 5 fma, div_fmas, div_fixup) takes 11 with a quarter-rate
-// rcp.  The theorem assumes no underflow or overflow: with |b| in [2^-100, 2^100] (else y is
-// NaN) and |q0| in [2^-860, 2^1000], |d| >= 2^-960 keeps the residual exact and q finite.  Other
-// cells -- zeros among them, whose sign the fast path can get wrong (-0 / b) -- divide (a branch,
-// skipped when no lane needs it).  NaN d passes: the fast path returns NaN as the division does.
-// tests/test_fastdiv.py checks the sequence and its guard against the division bit for bit.
-__device__ __forceinline__ double div_rn(double d, double b, double y) {
-    const double q0 = d * y;
-    const double r = __builtin_fma(-q0, b, d);
-    double q = __builtin_fma(r, y, q0);
-    const bool slow = __builtin_isnan(y) | (fabs(q0) < 0x1p-860) | (fabs(q0) > 0x1p1000);
-    if (__builtin_expect(slow, 0)) q = d / b;
-    return q;
-}
-
-__device__ __forceinline__ double range_rcp(double range) {
-    const double a = fabs(range);
-    return (a >= 0x1p-100 && a <= 0x1p100) ? 1.0 / range : __builtin_nan("");
-}
-
-__device__ __forceinline__ double rescale(double r, const ColParam& p, int int_dtype) {
-    if (!p.scaled) return r;
-    double x = div_rn(r - p.lo, p.range, p.rr);
-    if (int_dtype) x = trunc(x);
-    return x;
-}
-
-__device__ __forceinline__ bool missing(double x) { return __builtin_isnan(x) || x == 0.0; }
-
-__device__ __forceinline__ ColParam col_param(const pcx_mat& m, int c, bool with_fill) {
-    ColParam p;
-    p.scaled = m.scaled && m.scaled[c] && !m.rescaled;  // (in place already: the identity)
-    p.lo = p.scaled ? m.lo[c] : 0.0;
-    p.range = p.scaled ? (m.hi[c] - m.lo[c]) : 1.0;
-    p.guess = with_fill ? m.ev[EV_GUESS * m.n_events + c] : 0.0;
-    p.mu = with_fill ? m.ev[EV_MU * m.n_events + c] : 0.0;
-    p.rr = p.scaled ? range_rcp(p.range) : 1.0;
-    return p;
-}
-
-// filled value F_ic (:310-312)
-__device__ __forceinline__ double filled(double r, const ColParam& p, int int_dtype) {
-    const double x = rescale(r, p, int_dtype);
-    return missing(x) ? p.guess : x;
-}
 
 // ------------------------------------------------------------------ the reference's own order
 // For one rank with N*E < 9216 the reference's np.dot runs single-threaded OpenBLAS dgemv and
@@ -289,35 +209,6 @@ __device__ __forceinline__ dd rank_sum(const double* buf, int world, int64_t str
     return r;
 }
 
-// ------------------------------------------------------------------ limbs (exact sums)
-struct L3 {
-    uint64_t a, b, c;  // value = a*2^-35 + b*2^-78 + c*2^-121
-};
-
-__device__ __forceinline__ L3 l3_norm(L3 x) {  // carry so that b, c < 2^43
-    const uint64_t M = (1ull << 43) - 1;
-    x.b += x.c >> 43;
-    x.c &= M;
-    x.a += x.b >> 43;
-    x.b &= M;
-    return x;
-}
-__device__ __forceinline__ L3 l3_add(L3 x, L3 y) { return l3_norm({x.a + y.a, x.b + y.b, x.c + y.c}); }
-__device__ __forceinline__ L3 l3_twice(L3 x) { return l3_norm({x.a * 2, x.b * 2, x.c * 2}); }
-__device__ __forceinline__ int l3_cmp(L3 x, L3 y) {  // both normalised
-    if (x.a != y.a) return x.a < y.a ? -1 : 1;
-    if (x.b != y.b) return x.b < y.b ? -1 : 1;
-    if (x.c != y.c) return x.c < y.c ? -1 : 1;
-    return 0;
-}
-__device__ __forceinline__ L3 l3_of(double w) {
-    const limbs3 t = to_limbs(w);
-    return {t.l0, t.l1, t.l2};
-}
-__device__ __forceinline__ double l3_to_double(L3 x) {
-    return ldexp((double)x.a, -35) + (ldexp((double)x.b, -78) + ldexp((double)x.c, -121));
-}
-
 // ================================================================== PCX_M_REPUTATION
 __global__ void __launch_bounds__(1024) k_rep_total(pcx_mat m) {
     __shared__ dd lds[16];
@@ -463,24 +354,6 @@ __device__ __forceinline__ void rows_pipelined(int64_t r0, int64_t r1, LOAD load
     }
     for (; i < r1; i++) proc(i, load(i));
 }
-
-// the same over a strided row set i = first, first + stride, ... < n
-template <int U, class LOAD, class PROC>
-__device__ __forceinline__ void rows_strided(int64_t first, int64_t stride, int64_t n, LOAD load, PROC proc) {
-    int64_t i = first;
-    for (; i + (U - 1) * stride < n; i += U * stride) {
-        decltype(load(i)) v[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) v[u] = load(i + u * stride);
-#pragma unroll
-        for (int u = 0; u < U; u++) proc(i + u * stride, v[u]);
-    }
-    for (; i < n; i += stride) proc(i, load(i));
-}
-
-struct XW {
-    double x, w;
-};
 
 // min / max of two non-NaN doubles (fmin / fmax canonicalise both operands first: three more
 // fp64 VALU ops per element in k_colstats)
@@ -762,7 +635,6 @@ __global__ void __launch_bounds__(BT) k_mean(pcx_mat m) {
 
 // ================================================================== covariance (fp64 MFMA)
 typedef double d4 __attribute__((ext_vector_type(4)));
-constexpr int CT = 128;          // C tile edge
 constexpr int KB = 16;           // rows staged per step
 constexpr int LDP = CT + 16;     // padded LDS row (bank-conflict-free b64 fragment reads)
 
@@ -1925,10 +1797,10 @@ __global__ void __launch_bounds__(BT) k_wcd_rebuild(pcx_mat m, int general) {
 }
 
 // ================================================================== power iteration
-// pvec layout: [0..E) x, [E+64 .. 2E+64) y, scalars at pvec[3*(E+64) + k]
-__device__ __forceinline__ double* pv_x(const pcx_mat& m) { return m.pvec; }
-__device__ __forceinline__ double* pv_y(const pcx_mat& m) { return m.pvec + (m.n_events + 64); }
-__device__ __forceinline__ double* pv_s(const pcx_mat& m) { return m.pvec + 3 * (m.n_events + 64); }
+// pvec rows (pv_row, pcx_mat_layout.h): x, y and the scalars pv_s(m)[k]
+__device__ __forceinline__ double* pv_x(const pcx_mat& m) { return m.pvec + PV_X * pv_stride(m.n_events); }
+__device__ __forceinline__ double* pv_y(const pcx_mat& m) { return m.pvec + PV_Y * pv_stride(m.n_events); }
+__device__ __forceinline__ double* pv_s(const pcx_mat& m) { return m.pvec + PV_S * pv_stride(m.n_events); }
 
 __global__ void __launch_bounds__(BT) k_pi_check(pcx_mat m) {
     const int64_t E = m.n_events;
@@ -1952,9 +1824,9 @@ __global__ void __launch_bounds__(1024) k_pi_start(pcx_mat m) {
     const int E = (int)m.n_events;
     if (pi_mode_of(m.info[IN_FLAGS]) != 0) {  // no iteration: the host's first poll sees "converged"
         if (threadIdx.x == 0) {
-            pv_s(m)[0] = 0.0;
-            pv_s(m)[1] = 1.0;
-            pv_s(m)[2] = 0.0;
+            pv_s(m)[PS_DELTA] = 0.0;
+            pv_s(m)[PS_DONE] = 1.0;
+            pv_s(m)[PS_STEPS] = 0.0;
         }
         return;
     }
@@ -1993,9 +1865,9 @@ __global__ void __launch_bounds__(1024) k_pi_start(pcx_mat m) {
     __syncthreads();
     for (int j = threadIdx.x; j < E; j += 1024) pv_x(m)[j] = m.C[(int64_t)j * E + kd] / nrm;
     if (threadIdx.x == 0) {  // delta, converged, steps (k_pi_norm)
-        pv_s(m)[0] = 1.0;
-        pv_s(m)[1] = 0.0;
-        pv_s(m)[2] = 0.0;
+        pv_s(m)[PS_DELTA] = 1.0;
+        pv_s(m)[PS_DONE] = 0.0;
+        pv_s(m)[PS_STEPS] = 0.0;
     }
 }
 
@@ -2008,7 +1880,7 @@ __global__ void __launch_bounds__(BT) k_pi_gemv(pcx_mat m, const double* M, int 
     const int E = (int)m.n_events;
     const int row = blockIdx.x * (BT / WAVE) + threadIdx.x / WAVE;
     const int lane = threadIdx.x % WAVE;
-    if (row >= E || (honor_done && pv_s(m)[1] != 0.0) || pi_mode_of(m.info[IN_FLAGS]) != 0) return;
+    if (row >= E || (honor_done && pv_s(m)[PS_DONE] != 0.0) || pi_mode_of(m.info[IN_FLAGS]) != 0) return;
     const double* Cr = M + (int64_t)row * E;
     const double* x = pv_x(m);
     double acc = 0.0;
@@ -2024,7 +1896,7 @@ __global__ void __launch_bounds__(BT) k_pi_gemv4(pcx_mat m, const double* M, int
     const int E = (int)m.n_events;
     const int row = blockIdx.x * (BT / WAVE) + threadIdx.x / WAVE;
     const int lane = threadIdx.x % WAVE;
-    if (row >= E || (honor_done && pv_s(m)[1] != 0.0) || pi_mode_of(m.info[IN_FLAGS]) != 0) return;
+    if (row >= E || (honor_done && pv_s(m)[PS_DONE] != 0.0) || pi_mode_of(m.info[IN_FLAGS]) != 0) return;
     const double2* Cr = reinterpret_cast<const double2*>(M + (int64_t)row * E);
     const double2* x = reinterpret_cast<const double2*>(pv_x(m));
     const int h = E / 2;
@@ -2052,7 +1924,7 @@ __global__ void __launch_bounds__(1024) k_pi_norm(pcx_mat m, int honor_done) {
     __shared__ double red[1024];
     __shared__ double nrm;
     const int E = (int)m.n_events;
-    if (honor_done && pv_s(m)[1] != 0.0) return;  // (uniform: every thread reads the same flag)
+    if (honor_done && pv_s(m)[PS_DONE] != 0.0) return;  // (uniform: every thread reads the same flag)
     if (pi_mode_of(m.info[IN_FLAGS]) != 0) return;
     acc2 a;
     for (int j = threadIdx.x; j < E; j += 1024) {
@@ -2075,9 +1947,9 @@ __global__ void __launch_bounds__(1024) k_pi_norm(pcx_mat m, int honor_done) {
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        pv_s(m)[0] = red[0];
-        pv_s(m)[2] += 1.0;
-        if (honor_done && red[0] <= PI_TOL_M) pv_s(m)[1] = 1.0;
+        pv_s(m)[PS_DELTA] = red[0];
+        pv_s(m)[PS_STEPS] += 1.0;
+        if (honor_done && red[0] <= PI_TOL_M) pv_s(m)[PS_DONE] = 1.0;
     }
 }
 
@@ -2385,7 +2257,6 @@ __device__ __forceinline__ double nweight(double v, double S, double Sp) {
 // weighted counts' fixed-point scale: m.wdig's header word `slot` (zeroed once per call by the
 // runner; 0: normalize(set1), 1: normalize(set2), 2: smooth_rep), one atomic per wave.  Every lane
 // of the wave calls it.
-enum wdig_slot { WD_N1 = 0, WD_N2, WD_SMOOTH };
 __device__ __forceinline__ void wdig_note(const pcx_mat& m, int slot, uint64_t mx) {
 #pragma unroll
     for (int d = WAVE / 2; d >= 1; d >>= 1) {
@@ -2480,9 +2351,6 @@ __device__ __forceinline__ uint32_t sub4_stride4(uint32_t M, int j) {
     return (v | (v >> 6)) & 0x0Fu;
 }
 
-#ifndef PCX_MF_ZBG  // (a build parameter for A/B runs: bit 0 the outcome sums, bit 1 the GEMV2 sums take zbg)
-#define PCX_MF_ZBG 3
-#endif
 // m.wdig: a 256-byte header (the largest |w| bits of each weight vector, wdig_slot, written by the
 // kernels that write the weights), then vector v's digits at 256 + v wcd_rows 16 bytes
 __device__ __forceinline__ uint64_t* wdig_max(const pcx_mat& m) { return reinterpret_cast<uint64_t*>(m.wdig); }
@@ -2522,7 +2390,7 @@ __global__ void __launch_bounds__(BT) k_gemv2_c(pcx_mat m) {
     }
     // (every wave of a grid block stays to the end: the block builds the subset tables together)
     if (!GRID && (q >= E || q >= gb)) return;
-    if (!GRID && (PCX_MF_ZBG & 2) && q >= m.info[IN_COV_GENERAL] && m.zbg && wdig_ok(m, WD_N1, WD_N2)) return;  // (k_gemv2_mf: zbg)
+    if (!GRID && q >= m.info[IN_COV_GENERAL] && m.zbg && wdig_ok(m, WD_N1, WD_N2)) return;  // (k_gemv2_mf: zbg)
     const bool live = q < E;
     const int c = live ? m.cov_perm[q] : -1;
     if (!GRID && c < 0) return;  // (padding)
@@ -2670,10 +2538,10 @@ __global__ void __launch_bounds__(BT) k_decide_prep(pcx_mat m) {
     const double* old = m.ev + EV_OLD * E;
     double* n1 = m.ev + EV_D1 * E;   // new1 = normalize(set1) . F + 0.01 * old
     double* n2 = m.ev + EV_D2 * E;   // new2
-    double* raw1 = m.pvec + 2 * (m.n_events + 64);  // normalize(set1) . F (continuous rule)
+    double* raw1 = m.pvec + PV_RAW1 * pv_stride(m.n_events);  // normalize(set1) . F (continuous rule)
     double* raw2 = pv_y(m);                          // normalize(set2) . F
     const int c = blockIdx.x * BT + threadIdx.x;
-    if (c == 0) pv_s(m)[8] = 0.0;
+    if (c == 0) pv_s(m)[PS_RANKREF] = 0.0;
     if (c >= E) return;
     const double a = m.ob_order ? ob_col_dot(m, m.rowv + RV_N1 * m.n_rows, c) : dd_to_double(cst(m, c, 4));
     const double b = m.ob_order ? ob_col_dot(m, m.rowv + RV_N2 * m.n_rows, c) : dd_to_double(cst(m, c, 5));
@@ -2744,16 +2612,16 @@ __global__ void __launch_bounds__(BT) k_ranks(pcx_mat m, const int* cnt) {
         if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
         __syncthreads();
     }
-    if (threadIdx.x == 0) atomicAdd(&pv_s(m)[8], red[0]);
+    if (threadIdx.x == 0) atomicAdd(&pv_s(m)[PS_RANKREF], red[0]);
 }
 
 __global__ void __launch_bounds__(1024) k_decide(pcx_mat m) {
     __shared__ dd lds[16];
     const int E = (int)m.n_events;
     const double* old = m.ev + EV_OLD * E;
-    const double* raw1 = m.pvec + 2 * (m.n_events + 64);
+    const double* raw1 = m.pvec + PV_RAW1 * pv_stride(m.n_events);
     const double* raw2 = pv_y(m);
-    const double ref = m.rank_rule ? pv_s(m)[8] : 0.0;  // no rank rule: nonconformity directly
+    const double ref = m.rank_rule ? pv_s(m)[PS_RANKREF] : 0.0;  // no rank rule: nonconformity directly
     int branch, pick1;
     if (ref == 0 && m.ob_order) {  // np.sum((new - old)**2) pairwise (:480-481)
         __shared__ int pk;
@@ -2902,7 +2770,7 @@ __device__ __forceinline__ void outcomes_c_body(const pcx_mat& m, int q, int64_t
     const int64_t qn = live ? q : 0;  // (a lane past the positions reads a valid word, unused)
     const bool scl = general && (!live || (m.scaled && m.scaled[c]));
     // (k_outcomes_mf took the scaled positions' missing rows and the grid events of the general tiles)
-    if (mf && (scl || q >= ((PCX_MF_ZBG & 1) ? m.info[IN_COV_GENERAL] : gb))) return;
+    if (mf && (scl || q >= m.info[IN_COV_GENERAL])) return;
     if (general && __all(scl)) {  // (a wave of scaled events only: the subset tables need every lane)
         // a scaled event's raw is its weighted median (:520-523) and its certainty comes from
         // the selection (:540-546): only np.dot(smooth_rep, na_mat) (:559) is read here, from
@@ -3355,7 +3223,7 @@ __global__ void __launch_bounds__(BT) k_outcomes_mf(pcx_mat m) {
     const v4i* wd = reinterpret_cast<const v4i*>(wdig_vec(m, 0)) + lc;  // + 16 group: digit lc of 16 rows
     // positions [n_general, gb) of the general tiles hold grid events too (the general tiles end at a
     // multiple of 128): their codes come from zbg (k_wcd)
-    const int64_t ngen = (PCX_MF_ZBG & 1) ? m.info[IN_COV_GENERAL] : gb;
+    const int64_t ngen = m.info[IN_COV_GENERAL];
     const bool lbin = !grid && alive && qa >= ngen;
     const bool full = grid || q0 + 15 >= ngen;  // (wave-uniform: the code sums run)
     const uint32_t* zsrc = grid && alive ? zb_packed(m) + (qa - gb) : (lbin ? m.zbg + (qa - (gb - 128)) : nullptr);
@@ -3449,7 +3317,7 @@ __global__ void __launch_bounds__(BT) k_gemv2_mf(pcx_mat m) {
     const int64_t gb = (int64_t)m.cov_jb * CT;
     const int lane = threadIdx.x & (WAVE - 1), lc = lane & 15, lg = lane >> 4;
     // from the first 16 positions holding a grid event (the general tiles' tail [n_general, gb): zbg)
-    const int64_t ngen = (PCX_MF_ZBG & 2) ? m.info[IN_COV_GENERAL] : gb;
+    const int64_t ngen = m.info[IN_COV_GENERAL];
     const int q0 = (int)(gb > ngen ? ngen / 16 * 16 : gb) + (blockIdx.x * (BT / WAVE) + threadIdx.x / WAVE) * 16;
     if (q0 >= E) return;  // (wave-uniform)
     const int qa = q0 + lc;
@@ -3524,1481 +3392,6 @@ __global__ void __launch_bounds__(BT) k_events(pcx_mat m) {
     m.ev[EV_ADJ * E + c] = adj;
     m.ev[EV_FIN * E + c] = adj;
     m.ev[EV_CERT * E + c] = cnt > 0 ? dd_to_double(cst(m, c, slot)) : empty_certainty(m);
-}
-
-// ================================================================== weighted median selection
-// weightedstats.weighted_median (:303 over the present reports of a scaled event with
-// weights rep/sum(rep); :520-523 over the filled column with smooth_rep) in three tiers:
-//
-//  1. exact selection: an order-preserving u64 key per value, weights as exact fixed-point
-//     limbs; 8-bit histogram passes narrow the key range to the run of equal values where
-//     the exact prefix crosses half the total.  Every per-rank partial reduces with a plain
-//     SUM / MIN / MAX, so the result does not depend on the sharding.
-//  2. equal weights (reputation=None: every weight of the column is one double): the
-//     reference's float walk depends on the count alone, and pcx_seqsum.h replays it in
-//     O(log n) -- crossing index k* and the DBL_EPSILON half test -- after which an exact
-//     count selection fetches the k*-th value (and its predecessor for an exact half).
-//  3. the exact crossing is decisive unless the prefix at either end of the run lies
-//     within the sequential-sum error bound of half the total; such events (and dominant
-//     weights at the bound) are "hard" and are replayed in the reference's own float order
-//     (k_hard_*: gather in row order, sequential totals, (value, weight) sort, walk).
-enum sel_word {
-    SW_STATUS = 0,   // 0 done, 1 histogram pass pending, 2 dominant weight (first argmax row), 3 hard
-    SW_LO, SW_HI, SW_SHIFT,           // current key range and bucket shift
-    SW_BELOW0, SW_BELOW1, SW_BELOW2,  // exact weight before the range
-    SW_TOT0, SW_TOT1, SW_TOT2,        // exact total weight
-    SW_BELOW_MAX, SW_HAS_BELOW,       // largest key before the range
-    SW_RESULT,                        // result bits (status 0)
-    SW_WMAX,                          // max weight bits
-    SW_MODE,                          // 0 weight walk, 1 count rank (equal weights)
-    SW_NEED,                          // phase 1: the event has missing reports
-    SW_COUNT,                         // elements
-    SW_TARGET,                        // count mode: 0-based rank of the crossing element
-    SW_CNT_BELOW,                     // count mode: elements before the range
-    SW_HALF,                          // count mode: 1 exact half (mean with predecessor), 2 half at k*=1
-    SW_INRANGE,                       // elements (all ranks) in [LO, HI] after the last step
-    SW_CMODE,                         // 1: this rank's in-range elements are compacted in cbuf
-    SW_GN, SW_GW0, SW_GW1, SW_GW2,    // phase 2, this rank: filled (missing) rows -- all at the fill
-                                      // value -- count and raw weight limb sums, binned once per pass
-    SW_WB0, SW_WB1,                   // first pass: the bucket window gathered into cbuf (sampled)
-    SW_CERTN, SW_CW0, SW_CW1, SW_CW2, // phase 2, weight walk ended on one key: the elements (all ranks)
-                                      // holding it and their exact weight -- the certainty (:540-546)
-    SW_NWORDS
-};
-static_assert(SW_NWORDS <= SELS, "sel_state words");
-
-__device__ __forceinline__ L3 ld_l3(const uint64_t* p) { return {p[0], p[1], p[2]}; }
-__device__ __forceinline__ void st_l3(uint64_t* p, L3 v) {
-    p[0] = v.a;
-    p[1] = v.b;
-    p[2] = v.c;
-}
-// x - y for x >= y (both normalised)
-__device__ __forceinline__ L3 l3_sub(L3 x, L3 y) {
-    const uint64_t M = (1ull << 43);
-    uint64_t c = x.c, b = x.b, a = x.a;
-    if (c < y.c) {
-        c += M;
-        if (b == 0) {
-            b += M;
-            a -= 1;
-        }
-        b -= 1;
-    }
-    c -= y.c;
-    if (b < y.b) {
-        b += M;
-        a -= 1;
-    }
-    b -= y.b;
-    a -= y.a;
-    return l3_norm({a, b, c});
-}
-__device__ __forceinline__ L3 l3_absdiff(L3 x, L3 y) { return l3_cmp(x, y) >= 0 ? l3_sub(x, y) : l3_sub(y, x); }
-
-// |2 P - T| within the sequential-sum error bound of T?  The reference's cumulative
-// weights and midpoint are float sums of n terms (each <= (n-1) u sum|w|, weights >= 0;
-// phase 1 also divides every weight by a float total): both sides move by < (2n + 2) u T.
-// The bound doubles that and adds the weightedstats DBL_EPSILON test (weights sum to ~1).
-__device__ __forceinline__ bool near_half(L3 P, L3 T, uint64_t n) {
-    const double d = l3_to_double(l3_absdiff(l3_twice(P), T));
-    const double t = l3_to_double(T);
-    const double bound = t * ((4.0 * (double)n + 64.0) * 0x1p-53) + 16.0 * 0x1p-52;
-    return d <= bound;
-}
-
-__device__ __forceinline__ XW sel_load(const pcx_mat& m, int s, int64_t i) {
-    // phase 1 with reputation=None: every weight is rep = 1 / N (k_rep_local) -- not loaded
-    if (m.sel_phase == 1 && !m.rep_raw) return XW{m.T[(int64_t)s * m.n_rows + i], 1.0 / (double)m.n_total};
-    return XW{m.T[(int64_t)s * m.n_rows + i], m.sel_phase == 1 ? m.rep[i] : m.rowv[RV_SMOOTH * m.n_rows + i]};
-}
-
-__device__ __forceinline__ bool sel_decode(const pcx_mat& m, int s, XW v, double& x, double& w) {
-    if (m.sel_phase == 1) {
-        if (__builtin_isnan(v.x)) return false;
-        x = v.x;
-    } else {
-        x = __builtin_isnan(v.x) ? m.ev[EV_GUESS * m.n_events + m.scaled_cols[s]] : v.x;
-        if (__builtin_isnan(x)) return false;
-    }
-    w = v.w;
-    return true;
-}
-
-__device__ __forceinline__ bool sel_elem(const pcx_mat& m, int s, int64_t i, double& x, double& w) {
-    return sel_decode(m, s, sel_load(m, s, i), x, w);
-}
-
-__device__ __forceinline__ void sel_done(uint64_t* st, double r) {
-    st[SW_RESULT] = __double_as_longlong(r);
-    st[SW_STATUS] = 0;
-}
-
-// phase setup: which scaled events run a selection (phase 1: those with missing reports)
-__global__ void __launch_bounds__(BT) k_sel_setup(pcx_mat m) {
-    const int s = blockIdx.x * BT + threadIdx.x;
-    if (s >= m.n_scaled) return;
-    if (s == 0) m.info[IN_SEL_WLIMB] = 0;  // (k_sel_wlimbs ORs this phase's limb use in)
-    uint64_t* st = m.sel_state + (int64_t)s * SELS;
-    const int c = m.scaled_cols[s];
-    const bool need = m.sel_phase == 1 ? m.ev[EV_MISS * m.n_events + c] > 0 : true;
-    for (int k = 0; k < SELS; k++) st[k] = 0;
-    st[SW_STATUS] = need ? 1 : 0;
-    st[SW_NEED] = need ? 1 : 0;
-    if (m.sel_phase == 2 || need) m.hard[c] = HARD_NONE;
-}
-
-__device__ __forceinline__ int shift_for(uint64_t lo, uint64_t hi) {
-    const uint64_t d = hi - lo;
-    if (d == 0) return 0;
-    const int bits = 64 - __clzll(d);
-    return bits > 8 ? bits - 8 : 0;
-}
-
-// PCX selection init: the key range of every needed event without reading the column --
-// phase 1: the present values' extremes (M_COLSTATS, all ranks); phase 2: those and the fill
-// value (every missing row takes it, :310-312).  The first histogram pass (sel_first) then
-// covers that range and also collects what the reference's walk needs first: the exact total
-// weight, the count, the weight extremes and the filled rows' sums.  reputation=None in
-// phase 1: every weight is the same double, so that pass counts only (count mode).
-__global__ void __launch_bounds__(BT) k_sel_range(pcx_mat m) {
-    const int s = blockIdx.x * BT + threadIdx.x;
-    if (s >= m.n_scaled) return;
-    uint64_t* st = m.sel_state + (int64_t)s * SELS;
-    if (st[SW_STATUS] != 1) return;
-    const int E = (int)m.n_events;
-    const int c = m.scaled_cols[s];
-    double mn = m.ev[EV_MINX * E + c], mx = m.ev[EV_MAXX * E + c];
-    if (m.sel_phase == 2 && m.ev[EV_MISS * E + c] > 0) {
-        const double g = m.ev[EV_GUESS * E + c];
-        if (!__builtin_isnan(g)) {
-            mn = fmin(mn, g);
-            mx = fmax(mx, g);
-        }
-    }
-    uint64_t lo = 1, hi = 0;  // no element: an empty range
-    if (mn <= mx) {
-        lo = dkey(mn);
-        hi = dkey(mx);
-    }
-    st[SW_LO] = lo;
-    st[SW_HI] = hi;
-    st[SW_SHIFT] = lo <= hi ? shift_for(lo, hi) : 0;
-    st[SW_INRANGE] = 0;  // (with SW_COUNT = 0: the first pass never compacts)
-    st[SW_COUNT] = 0;
-    st[SW_MODE] = (m.sel_phase == 1 && !m.rep_raw) ? 1 : 0;
-}
-
-
-__device__ __forceinline__ void mark_hard(const pcx_mat& m, int s, uint64_t* st) {
-    st[SW_STATUS] = 3;
-    m.hard[m.scaled_cols[s]] = HARD_MEDIAN;
-}
-
-// start: totals of all ranks (already reduced); empty / no positive weight -> None (NaN);
-// equal weights -> the reference's walk by pcx_seqsum.h, then a count selection; else the
-// dominant-weight test (:any(w > midpoint)) and the exact weight selection
-// The totals come from the first pass's histogram (all ranks, reduced): exact integer sums of
-// its bucket counts and weight limbs, the extreme keys of its buckets; one thread per event of
-// that pass (active index a), whose histogram row k_sel_step then narrows in the same pass.
-// One wave per event: the lanes read the histogram row's buckets (coalesced) and reduce the
-// exact integer totals and key extremes; lane 0 then decides.
-__global__ void __launch_bounds__(BT) k_sel_start(pcx_mat m) {
-    const int a = blockIdx.x * (BT / WAVE) + threadIdx.x / WAVE;
-    const int lane = threadIdx.x % WAVE;
-    if (a >= (int)m.info[IN_SEL_ACTIVE]) return;  // wave-uniform
-    const int s = m.sel_act[a];
-    uint64_t* st = m.sel_state + (int64_t)s * SELS;
-    if (st[SW_STATUS] != 1) return;
-    const bool wsum = st[SW_MODE] == 0;  // the first pass summed weight limbs
-    const int64_t o = (int64_t)a * NB;
-    uint64_t ta = 0, tb = 0, tc = 0, n = 0, kmin = ~0ull, kmax = 0;
-    for (int b = lane; b < NB; b += WAVE) {
-        const uint64_t c = m.hist_n[o + b];
-        if (!c) continue;
-        n += c;
-        if (wsum) {
-            ta += m.hist_w[(o + b) * 3 + 0];
-            tb += m.hist_w[(o + b) * 3 + 1];
-            tc += m.hist_w[(o + b) * 3 + 2];
-        }
-        const uint64_t bmin = ~m.hist_min[o + b];  // (stored complemented: one MAX reduce, pcx_internal.h)
-        kmin = bmin < kmin ? bmin : kmin;
-        kmax = m.hist_max[o + b] > kmax ? m.hist_max[o + b] : kmax;
-    }
-#pragma unroll
-    for (int d = WAVE / 2; d >= 1; d >>= 1) {  // exact integer sums: any order
-        ta += __shfl_xor(ta, d, WAVE);
-        tb += __shfl_xor(tb, d, WAVE);
-        tc += __shfl_xor(tc, d, WAVE);
-        n += __shfl_xor(n, d, WAVE);
-        const uint64_t omn = __shfl_xor(kmin, d, WAVE), omx = __shfl_xor(kmax, d, WAVE);
-        kmin = omn < kmin ? omn : kmin;
-        kmax = omx > kmax ? omx : kmax;
-    }
-    if (lane != 0) return;
-    const uint64_t wminb = ~m.sel_imin[s * 2 + 1], wmaxb = m.sel_imax[s * 2 + 1];
-    // weights outside [0, 2^8) -- a negative reputation (rep / sum(rep) keeps its sign,
-    // __init__.py:142-145; smooth_rep inherits it, :472) or one above 256 times the total: the
-    // exact limbs hold only [0, 2^8) (pcx_device.h to_limbs), so replay in the reference's order.
-    // Over bit patterns (the MAX reduce): a sign bit, or [bits(256), bits(+inf)]; NaN keeps the
-    // limb path (NaN limbs are zero, as the generic conversion gives).
-    if (wsum && ((wmaxb >> 63) || (wmaxb >= 0x4070000000000000ull && wmaxb <= 0x7ff0000000000000ull))) {
-        mark_hard(m, s, st);
-        return;
-    }
-    // count mode known up front (equal weights): the total only needs to be nonzero
-    const L3 tot = wsum ? l3_norm({ta, tb, tc}) : L3{n && wmaxb ? 1ull : 0ull, 0, 0};
-    if (!wsum && wminb != wmaxb) {  // (cannot happen: reputation=None gives one weight) exact replay
-        mark_hard(m, s, st);
-        return;
-    }
-    st_l3(st + SW_TOT0, tot);
-    st_l3(st + SW_BELOW0, {0, 0, 0});
-    st[SW_BELOW_MAX] = 0;
-    st[SW_HAS_BELOW] = 0;
-    st[SW_CNT_BELOW] = 0;
-    st[SW_WMAX] = wmaxb;
-    st[SW_COUNT] = n;
-    // SW_LO / SW_HI / SW_SHIFT stay the first pass's (k_sel_step narrows that histogram)
-    st[SW_INRANGE] = n;
-    if (n == 0 || !(tot.a | tot.b | tot.c)) {  // weighted_median returns None -> NaN
-        sel_done(st, __builtin_nan(""));
-        return;
-    }
-    if (wminb == wmaxb) {
-        // equal weights: W0 = w (phase 1: w / sequential total, :294-302); mid = 0.5 * sum
-        const double w = __longlong_as_double(wmaxb);
-        const double W0 = m.sel_phase == 1 ? w / seqsum_const(w, (int64_t)n) : w;
-        const double mid = 0.5 * seqsum_const(W0, (int64_t)n);
-        if (W0 > mid) {  // dominant weight: data[first argmax] = the first element
-            st[SW_STATUS] = 2;
-            atomicAdd((unsigned long long*)&m.info[IN_SEL_ARGMAX], 1ull);
-            return;
-        }
-        if (!(W0 > 0.0)) {
-            sel_done(st, __builtin_nan(""));
-            return;
-        }
-        const int64_t ks = seqsum_first_above(W0, mid, (int64_t)n);
-        const double before = seqsum_const(W0, ks) - W0;
-        const bool half = fabs(before - mid) < 2.220446049250313080847e-16;
-        st[SW_MODE] = 1;
-        st[SW_TARGET] = (uint64_t)(ks - 1);
-        st[SW_HALF] = half ? (ks >= 2 ? 1 : (n == 1 ? 0 : 2)) : 0;
-    } else {
-        const L3 wmax = l3_of(__longlong_as_double(wmaxb));
-        if (near_half(wmax, tot, n)) {
-            mark_hard(m, s, st);
-            return;
-        }
-        if (l3_cmp(l3_twice(wmax), tot) > 0) {  // any(w > mid)
-            st[SW_STATUS] = 2;
-            atomicAdd((unsigned long long*)&m.info[IN_SEL_ARGMAX], 1ull);
-            return;
-        }
-        st[SW_MODE] = 0;
-    }
-    if (kmin == kmax) {  // one distinct value: every crossing returns it
-        sel_done(st, st[SW_HALF] == 2 ? __builtin_nan("") : dkey_inv(kmin));
-    }
-}
-
-// dominant weight: first global row (data order) holding the max weight -> sel_arg[s][0] (MIN)
-__global__ void __launch_bounds__(BT) k_sel_argmax(pcx_mat m) {
-    const int s = blockIdx.x;
-    const uint64_t* st = m.sel_state + (int64_t)s * SELS;
-    if (st[SW_STATUS] != 2) return;
-    const uint64_t wmaxb = st[SW_WMAX];
-    __shared__ unsigned long long best;
-    if (threadIdx.x == 0) best = ~0ull;
-    __syncthreads();
-    for (int64_t i = threadIdx.x; i < m.n_rows; i += BT) {
-        double x, w;
-        if (sel_elem(m, s, i, x, w) && (uint64_t)__double_as_longlong(w) == wmaxb) {
-            atomicMin(&best, (unsigned long long)(m.row_offset + i));
-            break;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m.sel_arg[s] = best;
-        m.sel_arg[m.n_scaled + s] = 0;
-    }
-}
-
-// the rank owning that row publishes its value key -> sel_arg[s][1] (MAX)
-__global__ void __launch_bounds__(BT) k_sel_value(pcx_mat m) {
-    const int s = blockIdx.x * BT + threadIdx.x;
-    if (s >= m.n_scaled) return;
-    const uint64_t* st = m.sel_state + (int64_t)s * SELS;
-    if (st[SW_STATUS] != 2) return;
-    const uint64_t gi = m.sel_arg[s];
-    uint64_t key = 0;
-    if (gi != ~0ull && (int64_t)gi >= m.row_offset && (int64_t)gi < m.row_offset + m.n_rows) {
-        double x, w;
-        sel_elem(m, s, (int64_t)gi - m.row_offset, x, w);
-        key = dkey(x);
-    }
-    m.sel_arg[m.n_scaled + s] = key;
-}
-
-__global__ void __launch_bounds__(BT) k_sel_value_finish(pcx_mat m) {
-    const int s = blockIdx.x * BT + threadIdx.x;
-    if (s >= m.n_scaled) return;
-    uint64_t* st = m.sel_state + (int64_t)s * SELS;
-    if (st[SW_STATUS] != 2) return;
-    const uint64_t key = m.sel_arg[m.n_scaled + s];
-    sel_done(st, key ? dkey_inv(key) : __builtin_nan(""));
-}
-
-// ordered compaction of [0, n) by pred into out[] (block-wide, order preserving); returns count
-template <class PRED, class EMIT>
-__device__ int64_t block_compact(int64_t n, PRED pred, EMIT emit) {
-    __shared__ int wsum[16];
-    __shared__ int64_t base_s;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6;
-    if (tid == 0) base_s = 0;
-    __syncthreads();
-    for (int64_t c0 = 0; c0 < n; c0 += blockDim.x) {
-        const int64_t i = c0 + tid;
-        const bool p = i < n && pred(i);
-        const uint64_t bal = __ballot(p);
-        const int before_lane = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wsum[wv] = __popcll(bal);
-        __syncthreads();
-        int off = 0;
-        for (int k = 0; k < wv; k++) off += wsum[k];
-        const int64_t base = base_s;
-        if (p) emit(i, base + off + before_lane);
-        __syncthreads();
-        if (tid == 0) {
-            int t = 0;
-            for (int k = 0; k < nw; k++) t += wsum[k];
-            base_s = base + t;
-        }
-        __syncthreads();
-    }
-    return base_s;
-}
-
-// active events (status 1) in event order -> sel_act, count -> info[IN_SEL_ACTIVE]; how many
-// of them walk weights (not counts) -> info[IN_SEL_WACTIVE] (their limb histograms are exchanged)
-__global__ void __launch_bounds__(1024) k_sel_compact(pcx_mat m) {
-    __shared__ unsigned long long nw;
-    if (threadIdx.x == 0) nw = 0;
-    __syncthreads();
-    const int64_t cnt = block_compact(
-        m.n_scaled, [&](int64_t s) { return m.sel_state[s * SELS + SW_STATUS] == 1; },
-        [&](int64_t s, int64_t pos) {
-            m.sel_act[pos] = (int32_t)s;
-            if (m.sel_state[s * SELS + SW_MODE] == 0) atomicAdd(&nw, 1ull);
-        });
-    if (threadIdx.x == 0) {
-        m.info[IN_SEL_ACTIVE] = cnt;
-        m.info[IN_SEL_WACTIVE] = (int64_t)nw;
-    }
-    // and the events marked for the exact replay so far (k_hard_list's list): after the pass that
-    // leaves no event active, the host's one read of info[IN_SEL_ACTIVE ..] also has their count
-    if (m.hard_cols) {
-        __syncthreads();  // (every thread has read block_compact's count before it is reset)
-        const int64_t nh = block_compact(
-            m.n_events, [&](int64_t c) { return m.hard[c] != HARD_NONE; },
-            [&](int64_t c, int64_t pos) {
-                m.hard_cols[pos] = (int32_t)c;
-                m.hard_modes[pos] = m.hard[c];
-            });
-        if (threadIdx.x == 0) m.info[IN_HARD] = nh;
-    }
-}
-
-// which of the three weight limbs any of this rank's rows uses in this phase (bit 0: L0, bit 2:
-// L2; bit 3: computed) -> info[IN_SEL_WLIMB].  k_sel_hist skips the LDS sums of a limb that is zero
-// for every row (C5's phase-2 weights, ~1e-6, leave L2 empty): a local saving, the histograms
-// and their exchange are unchanged.  (Measured, not kept: the counts carried in L0's sums from
-// bit 40 up when both fit, one atomic per element fewer -- 4.16 vs 4.14 ms at C5.)
-__global__ void __launch_bounds__(BT) k_sel_wlimbs(pcx_mat m) {
-    const double* w = m.sel_phase == 1 ? m.rep : m.rowv + RV_SMOOTH * m.n_rows;
-    uint64_t any0 = 0, any2 = 0;
-    for (int64_t i = (int64_t)blockIdx.x * BT + threadIdx.x; i < m.n_rows; i += (int64_t)gridDim.x * BT) {
-        const limbs3 L = to_limbs(w[i]);
-        any0 |= L.l0;
-        any2 |= L.l2;
-    }
-    __shared__ unsigned long long bits;
-    if (threadIdx.x == 0) bits = 8;
-    __syncthreads();
-    const bool b0 = __ballot(any0 != 0) != 0, b2 = __ballot(any2 != 0) != 0;
-    if (threadIdx.x % WAVE == 0 && (b0 || b2)) atomicOr(&bits, (b0 ? 1ull : 0ull) | (b2 ? 4ull : 0ull));
-    __syncthreads();
-    // one global atomic per block, and only when it adds a bit (thousands of ORs into one word
-    // serialise at its L2 channel: 50 us)
-    if (threadIdx.x == 0) {
-        unsigned long long* f = (unsigned long long*)&m.info[IN_SEL_WLIMB];
-        if ((__atomic_load_n(f, __ATOMIC_RELAXED) & bits) != bits) atomicOr(f, bits);
-    }
-}
-
-// The first pass's window: a sample of the column (1 / SEL_SAMPLE of its rows, all ranks'
-// samples summed) histogrammed in the first pass's buckets; the bucket where the sample's
-// weight crosses half, +- SEL_WIN buckets, is the window the first pass also gathers into cbuf.
-// When the exact crossing bucket lies inside it (nearly always) the later passes read only
-// cbuf -- one read of the column per phase instead of two.  A miss (or a cbuf overflow) only
-// falls back to the plain passes: the sample never decides a result.
-constexpr int SEL_SAMPLE = 64;
-constexpr int SEL_WIN = 3;
-__device__ __forceinline__ double* sel_sample_row(const pcx_mat& m, int a) {
-    return reinterpret_cast<double*>(m.hist_w) + (int64_t)a * NB * 3;  // [NB] weight, [NB] count
-}
-
-__global__ void __launch_bounds__(BT) k_sel_sample(pcx_mat m) {
-    const int a = blockIdx.x;
-    if (a >= (int)m.info[IN_SEL_ACTIVE]) return;
-    const int s = m.sel_act[a];
-    const uint64_t* st = m.sel_state + (int64_t)s * SELS;
-    __shared__ double sw[NB], sn[NB];
-    for (int b = threadIdx.x; b < NB; b += BT) sw[b] = sn[b] = 0.0;
-    __syncthreads();
-    const uint64_t lo = st[SW_LO], hi = st[SW_HI];
-    const int sh = (int)st[SW_SHIFT];
-    // runs of SEL_RUN consecutive rows every SEL_RUN * SEL_SAMPLE rows (the same 1/64 of the column
-    // as every 64th row, in whole cache lines: a strided sample read a line per element)
-    constexpr int SEL_RUN = 16;
-    const int64_t span = (int64_t)SEL_RUN * SEL_SAMPLE, full = m.n_rows / span;
-    const int64_t rem = m.n_rows - full * span;
-    const int64_t ns = full * SEL_RUN + (rem < SEL_RUN ? rem : SEL_RUN);
-    for (int64_t j = threadIdx.x; j < ns; j += BT) {
-        double x, w;
-        const XW v = sel_load(m, s, (j / SEL_RUN) * span + (j % SEL_RUN));
-        if (!sel_decode(m, s, v, x, w)) continue;
-        const uint64_t k = dkey(x);
-        if (k < lo || k > hi) continue;
-        const int b = (int)((k - lo) >> sh);
-        atomicAdd(&sw[b], w);
-        // phase 2: a filled row (all at the fill value) is binned once by k_sel_hist, never
-        // gathered into cbuf -- it weighs in the crossing, not in the window's size estimate
-        if (!(m.sel_phase == 2 && __builtin_isnan(v.x))) atomicAdd(&sn[b], 1.0);
-    }
-    __syncthreads();
-    double* o = sel_sample_row(m, a);
-    for (int b = threadIdx.x; b < NB; b += BT) {
-        o[b] = sw[b];
-        o[NB + b] = sn[b];
-    }
-}
-
-// exact weight / count histogram of the keys inside [lo, hi] (NB buckets) of active event a
-// One block per active event.  Once the key range holds at most ccap elements (all ranks),
-// the pass that reads the whole column also compacts this rank's in-range (key, weight)
-// pairs into cbuf; later passes read only those (the histogram is a set of exact integer
-// sums / minima / maxima, so the compacted order does not matter).
-// NT threads per event: 256, or 1,024 when the active events leave CUs idle (C4: 250 events on 256
-// CUs -- one 256-thread workgroup per CU kept four waves streaming each column)
-// CM: phase 1 under reputation=None, where every pass counts (every weight is 1 / N): no weight
-// loads, limbs or weight extremes, 32-bit counts (n_rows < 2^32, sel_hist), a 16-row load batch
-// held to 64 VGPRs (eight waves per SIMD: 2.30 -> 2.03 ms at C5 against 8-row batches; 65 VGPRs
-// unforced cost a wave per SIMD)
-template <int NT, bool CM>
-__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(CM ? 8 : PCX_SEL_WWAVES))) k_sel_hist(pcx_mat m) {
-    const int a = blockIdx.x;
-    if (a >= (int)m.info[IN_SEL_ACTIVE]) return;  // the first pass is launched for every scaled event
-    const int s = m.sel_act[a];
-    uint64_t* st = m.sel_state + (int64_t)s * SELS;
-    // SEL_HC copies of every bucket, bucket b's copy c at b SEL_HC + c and a thread binning into
-    // copy threadIdx.x % SEL_HC: lanes of a wave whose keys share a bucket split over the copies
-    // (same-address LDS atomics serialise); the copies merge exactly (integer sums, min, max)
-    constexpr int HC = CM ? 4 : SEL_HC;  // (count mode, half the arrays: four copies, 2.38 -> 2.26 ms at C5)
-    constexpr int HW = CM ? 1 : NB * HC;
-    __shared__ unsigned long long ha[HW], hb[HW], hc[HW], hmin[NB * HC], hmax[NB * HC];
-    // (32-bit LDS counts in the weight-mode kernel measured: no faster)
-    typedef typename std::conditional<CM, unsigned int, unsigned long long>::type hn_t;
-    __shared__ hn_t hn[NB * HC];
-    __shared__ unsigned long long gcount, f_wlo, f_whi, f_ga, f_gb, f_gc, f_gn;
-    for (int b = threadIdx.x; b < NB * HC; b += NT) {
-        if constexpr (!CM) ha[b] = hb[b] = hc[b] = 0;
-        hn[b] = 0;
-        hmin[b] = ~0ull;
-        hmax[b] = 0;
-    }
-    if (threadIdx.x == 0) {
-        gcount = 0;
-        f_wlo = ~0ull;
-        f_whi = 0;
-        f_ga = f_gb = f_gc = f_gn = 0;
-    }
-    __syncthreads();
-    // first pass (sel_first): the weight extremes of every element, and in phase 2 the filled
-    // rows (all at the fill value) summed apart and binned once at the end
-    const bool first = m.sel_first != 0;
-    const bool gfirst = !CM && first && m.sel_phase == 2;
-    uint64_t wlo = ~0ull, whi = 0, ga = 0, gb = 0, gc = 0, gn = 0;
-    __shared__ int win_s[2];
-    if (first && threadIdx.x == 0) {  // the sampled window (k_sel_sample, all ranks)
-        const double* smp = sel_sample_row(m, a);
-        const bool wm = st[SW_MODE] == 0;
-        double tot = 0.0;
-        for (int b = 0; b < NB; b++) tot += wm ? smp[b] : smp[NB + b];
-        int b0 = 1, b1 = 0;  // empty
-        if (tot > 0.0 && m.cbuf) {
-            double cum = 0.0;
-            int bx = NB - 1;
-            for (int b = 0; b < NB; b++) {
-                cum += wm ? smp[b] : smp[NB + b];
-                if (2.0 * cum >= tot) {
-                    bx = b;
-                    break;
-                }
-            }
-            // widen by up to SEL_WIN buckets a side while this rank's estimated share of the
-            // window (sampled count x SEL_SAMPLE / world) stays within half of cbuf; a crossing
-            // bucket denser than that gets no window (the plain passes narrow it first)
-            // (and within 1/8 of the column: a wider window re-reads about as much from cbuf
-            // as the plain pass reads from the column, after paying for the gather)
-            const double share = fmin(0.5 * (double)m.ccap, (double)m.n_rows / 8.0);
-            const double cap = share * (double)m.world / (double)SEL_SAMPLE;
-            double est = smp[NB + bx];
-            if (est <= cap) {
-                b0 = b1 = bx;
-                for (int r = 1; r <= SEL_WIN; r++) {
-                    const double l = bx - r >= 0 ? smp[NB + bx - r] : 0.0;
-                    const double h = bx + r < NB ? smp[NB + bx + r] : 0.0;
-                    if (est + l + h > cap) break;
-                    est += l + h;
-                    b0 = bx - r >= 0 ? bx - r : 0;
-                    b1 = bx + r < NB ? bx + r : NB - 1;
-                }
-            }
-        }
-        win_s[0] = b0;
-        win_s[1] = b1;
-        st[SW_WB0] = (uint64_t)b0;
-        st[SW_WB1] = (uint64_t)b1;
-    }
-    __syncthreads();
-    const int wb0 = first ? win_s[0] : 1, wb1 = first ? win_s[1] : 0;
-    const bool wgather = first && wb0 <= wb1;
-    const uint64_t lo = st[SW_LO], hi = st[SW_HI];
-    const int sh = (int)st[SW_SHIFT];
-    const bool wmode = !CM && st[SW_MODE] == 0;
-    const bool from_buf = st[SW_CMODE] == 1;
-    // phase 2: the filled rows all sit at the fill value -- binned once, not per element
-    const bool gties = !CM && m.sel_phase == 2 && st[SW_GN] > 0;
-    const uint64_t gk = gties ? dkey(m.ev[EV_GUESS * m.n_events + m.scaled_cols[s]]) : 0;
-    const bool gin = gties && gk >= lo && gk <= hi;
-    const uint64_t ties_all = gin ? (uint64_t)m.ev[EV_MISS * m.n_events + m.scaled_cols[s]] : 0;  // all ranks
-    const uint64_t need = st[SW_INRANGE] > ties_all ? st[SW_INRANGE] - ties_all : 0;
-    // gather only once the range has narrowed: later passes then read 16 B per in-range element
-    // instead of the column, which pays when the range holds a small part of it (a shard whose
-    // whole column fits cbuf would otherwise gather everything and re-read it per pass)
-    const bool gather = !from_buf && m.cbuf && st[SW_INRANGE] > 0 && need <= (uint64_t)m.ccap &&
-                        8 * need <= st[SW_COUNT];
-    uint64_t* cb = m.cbuf ? m.cbuf + (int64_t)s * m.ccap * 2 : nullptr;
-    const int hcp = HC > 1 ? (int)(threadIdx.x % HC) : 0;
-    const int64_t wl = CM ? 0 : m.info[IN_SEL_WLIMB];  // (k_sel_wlimbs: a limb no row uses is not summed)
-    const bool use0 = !(wl & 8) || (wl & 1), use2 = !(wl & 8) || (wl & 4);
-    // Phase 2's first pass bins the present values of phase 1's first pass (the same rows, the
-    // same keys) plus the filled rows, which it bins apart: over the same range and shift the
-    // buckets' counts and key extremes of the present values are the ones phase 1 counted.  Phase
-    // 1's first pass keeps them (this rank's, before the reduction: vsave), and phase 2's takes
-    // them instead of three LDS atomics per element -- the weight limbs are new, the rest is not.
-    // (A filled row's fill value may lie outside phase 1's range, int_dtype truncating it: a
-    // changed range recounts.)
-    uint64_t* const vkey = m.vsave ? m.vsave + (int64_t)m.n_scaled * NB * 3 + (int64_t)s * 4 : nullptr;
-    const bool vput = first && m.sel_phase == 1 && vkey;
-    const bool vreuse = !CM && first && m.sel_phase == 2 && vkey && vkey[3] == 1 && vkey[0] == lo &&
-                        vkey[1] == hi && vkey[2] == (uint64_t)sh;
-    auto bin = [&](uint64_t k, double w) {
-        const int b = (int)((k - lo) >> sh) * HC + hcp;
-        if constexpr (!CM) {
-            if (wmode) {
-                const limbs3 L = to_limbs(w);
-                if (use0) atomicAdd(&ha[b], (unsigned long long)L.l0);
-                atomicAdd(&hb[b], (unsigned long long)L.l1);
-                if (use2) atomicAdd(&hc[b], (unsigned long long)L.l2);
-            }
-        }
-        if (!CM && vreuse) return;
-        atomicAdd(&hn[b], (hn_t)1);
-        // (measured: reading the extremes first and skipping the atomics that cannot change them
-        // is slower, 9.4 -> 12.0 ms at C5 -- the read's latency sits in every element's path,
-        // where the no-return atomics are fire-and-forget; min / max interleaved in one array,
-        // 9.4 -> 9.7 ms -- twice the bank conflicts of two arrays; exact extremes only inside the
-        // sampled window, nominal bounds elsewhere, 9.4 -> 9.7 ms)
-        atomicMin(&hmin[b], (unsigned long long)k);
-        atomicMax(&hmax[b], (unsigned long long)k);
-    };
-    if (from_buf) {
-        const int64_t nc = m.ccount[s];
-        for (int64_t j = threadIdx.x; j < nc; j += NT) {
-            const uint64_t k = cb[2 * j];
-            if (k < lo || k > hi) continue;
-            bin(k, __longlong_as_double(cb[2 * j + 1]));
-        }
-    } else {
-        const double* const tcol = m.T + (int64_t)s * m.n_rows;
-        const double wc = 1.0 / (double)m.n_total;  // (CM: sel_load's weight)
-        rows_strided<(CM ? 16 : SEL_WUNROLL)>(threadIdx.x, NT, m.n_rows, [&](int64_t i) {
-                                     if constexpr (CM) return XW{tcol[i], wc};
-                                     else return sel_load(m, s, i);
-                                 },
-                                 [&](int64_t, XW v) {
-            double x, w;
-            if (gties && __builtin_isnan(v.x)) return;  // a filled row
-            if constexpr (CM) {
-                if (__builtin_isnan(v.x)) return;
-                x = v.x;
-                w = v.w;
-            } else if (!sel_decode(m, s, v, x, w)) return;
-            if (!CM && first) {
-                const uint64_t wb = (uint64_t)__double_as_longlong(w);  // weights >= 0 order like their bits
-                wlo = wb < wlo ? wb : wlo;
-                whi = wb > whi ? wb : whi;
-                if (gfirst && __builtin_isnan(v.x)) {  // a filled row: summed here, binned once below
-                    if (wmode) {
-                        const limbs3 L = to_limbs(w);
-                        ga += L.l0;
-                        gb += L.l1;
-                        gc += L.l2;
-                    }
-                    gn++;
-                    return;
-                }
-            }
-            const uint64_t k = dkey(x);
-            if (k < lo || k > hi) return;
-            bin(k, w);
-            if (wgather || gather) {
-                const int b = (int)((k - lo) >> sh);
-                const bool put = gather || (b >= wb0 && b <= wb1);
-                // one LDS atomic per wave: the lanes that append take consecutive slots
-                const uint64_t pm = __ballot(put);
-                if (pm) {
-                    const int lead = __ffsll((long long)pm) - 1;
-                    const int lane = threadIdx.x % WAVE;
-                    unsigned long long base = 0;
-                    if (lane == lead) base = atomicAdd(&gcount, (unsigned long long)__popcll(pm));
-                    base = (unsigned long long)__shfl((long long)base, lead, WAVE);
-                    const unsigned long long j = base + __popcll(pm & ((1ull << lane) - 1ull));
-                    if (put && j < (unsigned long long)m.ccap) {
-                        cb[2 * j] = k;
-                        cb[2 * j + 1] = (uint64_t)__double_as_longlong(w);
-                    }
-                }
-            }
-        });
-    }
-    if (first) {
-        if (CM) wlo = whi = (uint64_t)__double_as_longlong(1.0 / (double)m.n_total);
-        atomicMin(&f_wlo, (unsigned long long)wlo);
-        atomicMax(&f_whi, (unsigned long long)whi);
-        if (gn) {
-            atomicAdd(&f_ga, (unsigned long long)ga);
-            atomicAdd(&f_gb, (unsigned long long)gb);
-            atomicAdd(&f_gc, (unsigned long long)gc);
-            atomicAdd(&f_gn, (unsigned long long)gn);
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            m.sel_imin[s * 2 + 1] = ~f_wlo;  // all ranks: (complemented) MAX before k_sel_start
-            m.sel_imax[s * 2 + 1] = f_whi;
-            if (!CM && f_gn) {  // this rank's filled rows, all at the fill value (inside [lo, hi])
-                st[SW_GN] = f_gn;
-                st[SW_GW0] = f_ga;
-                st[SW_GW1] = f_gb;
-                st[SW_GW2] = f_gc;
-                const uint64_t fk = dkey(m.ev[EV_GUESS * m.n_events + m.scaled_cols[s]]);
-                const int b = (int)((fk - lo) >> sh) * HC;
-                if constexpr (!CM) {
-                    if (wmode) {
-                        atomicAdd(&ha[b], f_ga);
-                        atomicAdd(&hb[b], f_gb);
-                        atomicAdd(&hc[b], f_gc);
-                    }
-                }
-                atomicAdd(&hn[b], (hn_t)f_gn);
-                atomicMin(&hmin[b], (unsigned long long)fk);
-                atomicMax(&hmax[b], (unsigned long long)fk);
-            }
-        }
-    }
-    if (gin && threadIdx.x == 0) {
-        const int b = (int)((gk - lo) >> sh) * HC;
-        if constexpr (!CM) {
-            if (wmode) {
-                atomicAdd(&ha[b], (unsigned long long)st[SW_GW0]);
-                atomicAdd(&hb[b], (unsigned long long)st[SW_GW1]);
-                atomicAdd(&hc[b], (unsigned long long)st[SW_GW2]);
-            }
-        }
-        atomicAdd(&hn[b], (hn_t)st[SW_GN]);
-        atomicMin(&hmin[b], (unsigned long long)gk);
-        atomicMax(&hmax[b], (unsigned long long)gk);
-    }
-    __syncthreads();
-    if (gather && threadIdx.x == 0) {
-        m.ccount[s] = (int64_t)gcount;
-        st[SW_CMODE] = 1;
-    }
-    if (wgather && threadIdx.x == 0) {  // pending: valid once the crossing bucket is inside the window
-        const bool fits = gcount <= (unsigned long long)m.ccap;
-        m.ccount[s] = fits ? (int64_t)gcount : 0;
-        st[SW_CMODE] = fits ? 2 : 0;
-    }
-    if (vput && threadIdx.x == 0) {
-        vkey[0] = lo;
-        vkey[1] = hi;
-        vkey[2] = (uint64_t)sh;
-        vkey[3] = 1;
-    }
-    const int64_t o = (int64_t)a * NB;
-    for (int b = threadIdx.x; b < NB; b += NT) {
-        unsigned long long sa = 0, sb = 0, sc = 0, mn = ~0ull, mx = 0;
-        uint64_t sn = 0;
-#pragma unroll
-        for (int c = 0; c < HC; c++) {
-            if constexpr (!CM) {
-                sa += ha[b * HC + c];
-                sb += hb[b * HC + c];
-                sc += hc[b * HC + c];
-            }
-            sn += (uint64_t)hn[b * HC + c];
-            mn = hmin[b * HC + c] < mn ? hmin[b * HC + c] : mn;
-            mx = hmax[b * HC + c] > mx ? hmax[b * HC + c] : mx;
-        }
-        uint64_t* const vs = m.vsave ? m.vsave + ((int64_t)s * NB + b) * 3 : nullptr;
-        if (vput) {  // this rank's present values of the range (before the reduction over ranks)
-            vs[0] = sn;
-            vs[1] = mn;
-            vs[2] = mx;
-        } else if (vreuse) {
-            sn += vs[0];
-            mn = vs[1] < mn ? vs[1] : mn;
-            mx = vs[2] > mx ? vs[2] : mx;
-        }
-        if (wmode) {
-            m.hist_w[(o + b) * 3 + 0] = sa;
-            m.hist_w[(o + b) * 3 + 1] = sb;
-            m.hist_w[(o + b) * 3 + 2] = sc;
-        }
-        m.hist_n[o + b] = sn;
-        m.hist_min[o + b] = ~mn;  // complemented: the ranks' minima and maxima reduce in one MAX
-        m.hist_max[o + b] = mx;
-    }
-}
-
-// walk the buckets (reduced over ranks): weight mode keeps the bucket where the exact
-// prefix crosses half the total, count mode the one holding rank `target`; a single-key
-// bucket resolves (weight mode: unless the crossing is near a rounding-decided half)
-// one wave per active event: lane l owns buckets PB*l .. PB*l+PB-1.  The exact prefix sums
-// of the bucket counts and weight limbs come from a wave scan (integer limbs: order-free), the
-// first bucket whose prefix crosses the half (weights) / target (counts) by ballot, and that
-// bucket's lane applies the narrowing (a 256-step serial scan per event before).
-constexpr int SEL_PB = NB / WAVE;
-__device__ __forceinline__ uint64_t scan_add_u64(uint64_t v, int lane) {  // inclusive
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const uint64_t u = __shfl_up(v, d, WAVE);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
-__device__ __forceinline__ uint64_t scan_max_u64(uint64_t v, int lane) {  // inclusive
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const uint64_t u = __shfl_up(v, d, WAVE);
-        if (lane >= d) v = u > v ? u : v;
-    }
-    return v;
-}
-
-__global__ void __launch_bounds__(BT) k_sel_step(pcx_mat m, int n_active) {
-    const int a = blockIdx.x * (BT / WAVE) + threadIdx.x / WAVE;
-    const int lane = threadIdx.x % WAVE;
-    if (a >= n_active || a >= (int)m.info[IN_SEL_ACTIVE]) return;  // wave-uniform
-    const int s = m.sel_act[a];
-    uint64_t* st = m.sel_state + (int64_t)s * SELS;
-    if (st[SW_STATUS] != 1) return;  // the first pass's start may have finished it
-    const bool wmode = st[SW_MODE] == 0;
-    const L3 tot = ld_l3(st + SW_TOT0);
-    const uint64_t n_all = st[SW_COUNT], target = st[SW_TARGET];
-    const L3 below0 = ld_l3(st + SW_BELOW0);
-    const uint64_t cbelow0 = st[SW_CNT_BELOW], below_max0 = st[SW_BELOW_MAX];
-    const bool has_below0 = st[SW_HAS_BELOW] != 0;
-    const int64_t o = (int64_t)a * NB;
-    uint64_t nb[SEL_PB], kmn[SEL_PB], kmx[SEL_PB];
-    L3 hw[SEL_PB];
-    uint64_t sc = 0, sa = 0, sb = 0, sl = 0, smax = 0;  // lane totals (counts, limbs), last key
-#pragma unroll
-    for (int j = 0; j < SEL_PB; j++) {
-        const int b = lane * SEL_PB + j;
-        nb[j] = m.hist_n[o + b];
-        const uint64_t* hs = m.hist_w + (o + b) * 3;
-        hw[j] = (wmode && nb[j]) ? l3_norm({hs[0], hs[1], hs[2]}) : L3{0, 0, 0};
-        kmn[j] = ~m.hist_min[o + b];
-        kmx[j] = m.hist_max[o + b];
-        sc += nb[j];
-        sa += hw[j].a;
-        sb += hw[j].b;
-        sl += hw[j].c;
-        if (nb[j]) smax = kmx[j];  // keys rise with the bucket index
-    }
-    // exclusive prefixes over the lanes below
-    const uint64_t ic = scan_add_u64(sc, lane), ia = scan_add_u64(sa, lane), ib = scan_add_u64(sb, lane),
-                   il = scan_add_u64(sl, lane), imax = scan_max_u64(smax, lane);
-    uint64_t pc = ic - sc, pa = ia - sa, pb = ib - sb, pl = il - sl;
-    uint64_t pmax = __shfl_up(imax, 1, WAVE);
-    if (lane == 0) pmax = 0;
-    int first = SEL_PB;  // this lane's first crossing bucket
-    L3 below{}, upto{};
-    uint64_t cbelow = 0, below_max = 0;
-    bool has_below = false;
-#pragma unroll
-    for (int j = 0; j < SEL_PB; j++) {
-        const L3 bl = l3_norm({below0.a + pa, below0.b + pb, below0.c + pl});
-        const L3 up = l3_norm({bl.a + hw[j].a, bl.b + hw[j].b, bl.c + hw[j].c});
-        const bool cross = nb[j] && (wmode ? l3_cmp(l3_twice(up), tot) > 0 : cbelow0 + pc + nb[j] > target);
-        if (cross && first == SEL_PB) {
-            first = j;
-            below = bl;
-            upto = up;
-            cbelow = cbelow0 + pc;
-            const bool any = pmax != 0 || pc != 0;  // nonempty buckets passed in this pass
-            below_max = any ? pmax : below_max0;
-            has_below = has_below0 || any;
-        }
-        pc += nb[j];
-        pa += hw[j].a;
-        pb += hw[j].b;
-        pl += hw[j].c;
-        if (nb[j]) pmax = kmx[j];
-    }
-    const uint64_t mask = __ballot(first < SEL_PB);
-    if (mask == 0) {  // no crossing (cannot happen with exact sums)
-        if (lane == 0) sel_done(st, __builtin_nan(""));
-        return;
-    }
-    if (lane != __ffsll((long long)mask) - 1) return;
-    const uint64_t n = nb[first], kmin = kmn[first], kmax = kmx[first];
-    if (kmin == kmax) {
-        const double xs = dkey_inv(kmin);
-        if (wmode) {
-            if (near_half(below, tot, n_all) || near_half(upto, tot, n_all)) {
-                mark_hard(m, s, st);
-                return;
-            }
-            if (m.sel_phase == 2) {  // every element equal to the outcome is in this bucket
-                st[SW_CERTN] = n;
-                st_l3(st + SW_CW0, hw[first]);
-            }
-            sel_done(st, xs);
-        } else {
-            double r = xs;
-            if (st[SW_HALF] == 2) {
-                r = __builtin_nan("");
-            } else if (st[SW_HALF] == 1) {
-                const double pred = target >= cbelow + 1 ? xs : dkey_inv(below_max);
-                r = (pred + xs) / 2.0;  // sum(bounds) / float(len(bounds))
-            }
-            sel_done(st, r);
-        }
-    } else {
-        // the first pass's window holds this rank's elements of the crossing bucket when the
-        // bucket lies inside it: later passes read cbuf (else the column, as without a window)
-        if (st[SW_CMODE] == 2) {
-            const int b = lane * SEL_PB + first;
-            st[SW_CMODE] = (b >= (int)st[SW_WB0] && b <= (int)st[SW_WB1]) ? 1 : 0;
-        }
-        st[SW_LO] = kmin;
-        st[SW_HI] = kmax;
-        st[SW_SHIFT] = shift_for(kmin, kmax);
-        st[SW_INRANGE] = n;
-        st_l3(st + SW_BELOW0, below);
-        st[SW_CNT_BELOW] = cbelow;
-        st[SW_BELOW_MAX] = below_max;
-        st[SW_HAS_BELOW] = has_below ? 1 : 0;
-    }
-}
-
-// results into guess (phase 1; int dtype truncates, :312) / outcomes (phase 2, :537-538)
-__global__ void __launch_bounds__(BT) k_sel_finish(pcx_mat m) {
-    const int s = blockIdx.x * BT + threadIdx.x;
-    if (s >= m.n_scaled) return;
-    const int E = (int)m.n_events;
-    const int c = m.scaled_cols[s];
-    uint64_t* st = m.sel_state + (int64_t)s * SELS;
-    const double r = __longlong_as_double(st[SW_RESULT]);
-    if (m.sel_phase == 1) {
-        if (st[SW_NEED]) m.ev[EV_GUESS * E + c] = m.int_dtype ? trunc(r) : r;
-    } else {
-        m.ev[EV_RAW * E + c] = r;
-        m.ev[EV_ADJ * E + c] = r;
-        double f = r * (m.hi[c] - m.lo[c]);  // :537-538, two roundings
-        f = f + m.lo[c];
-        m.ev[EV_FIN * E + c] = f;
-    }
-}
-
-// Exact replay of weightedstats.weighted_median with the reference's float arithmetic,
-// for one scaled event whose element count fits the block (n <= SEL_EXACT_MAX; single
-// rank).  Phase 1 (:287-303): weights rep_j / (sequential sum of present rep), over the
-// present reports in row order.  Phase 2 (:520-523): weights smooth_rep over all rows.
-// mid = 0.5 * builtin sum (row order); dominant weight -> first argmax; else bitonic sort
-// by (value, weight) and the sequential walk with the DBL_EPSILON exact-half test.
-__global__ void __launch_bounds__(1024) k_sel_exact(pcx_mat m) {
-    const int s = blockIdx.x;
-    uint64_t* st = m.sel_state + (int64_t)s * SELS;
-    if (st[SW_STATUS] == 0) return;
-    __shared__ double xs[SEL_EXACT_MAX];
-    __shared__ double ws[SEL_EXACT_MAX];
-    __shared__ uint32_t pres[SEL_EXACT_MAX / 32];  // the rows' present bits (phase 1: a report; 2: a value)
-    __shared__ int cnt;
-    __shared__ double mid_s, wmax_s;
-    __shared__ int first_s;
-    const int tid = threadIdx.x;
-    const int n_rows = (int)m.n_rows;
-    // the column's (x, w) in row order into LDS by every thread (coalesced; thread 0 read them one
-    // dependent global load at a time: 0.7 ms of a 1k x 100 consensus), the present bits beside;
-    // an absent row holds (+inf, +inf), which the sort puts after every present pair, so nothing is
-    // compacted (an in-place compaction by one thread waited on its own LDS stores)
-    const bool ph1 = m.sel_phase == 1;
-    for (int k = tid; k < SEL_EXACT_MAX / 32; k += 1024) pres[k] = 0;
-    __syncthreads();
-    for (int i = tid; i < n_rows; i += 1024) {
-        double x = 0.0, w = 0.0;
-        const bool ok = sel_elem(m, s, i, x, w);
-        if (ok) atomicOr(&pres[i >> 5], 1u << (i & 31));
-        xs[i] = ok ? x : __builtin_inf();
-        ws[i] = ok ? w : __builtin_inf();
-    }
-    __syncthreads();
-    auto present = [&](int i) { return ((pres[i >> 5] >> (i & 31)) & 1u) != 0; };
-    __shared__ double tot_s;
-    if (ph1 && tid == 0) {  // the present total, sequential in row order (read only: the loads pipeline)
-        double tot = 0.0;
-        for (int i = 0; i < n_rows; i++)
-            if (present(i)) tot += ws[i];
-        tot_s = tot;
-    }
-    __syncthreads();
-    if (ph1)  // rep_j / tot, each its own division
-        for (int i = tid; i < n_rows; i += 1024)
-            if (present(i)) ws[i] = ws[i] / tot_s;
-    __syncthreads();
-    if (tid == 0) {
-        int k = 0;
-        double W = 0.0;
-        for (int i = 0; i < n_rows; i++)
-            if (present(i)) {
-                W += ws[i];
-                k++;
-            }
-        cnt = k;
-        mid_s = 0.5 * W;
-        first_s = n_rows;
-        wmax_s = 0.0;
-    }
-    __syncthreads();
-    const int n = cnt;
-    const double mid = mid_s;
-    // dominance: any(w > mid) -> data[first index of max(w)]; any positive weight (exact
-    // reductions over the present rows, spread over the block)
-    {
-        __shared__ double red[1024];
-        __shared__ int dom_s, first_p;
-        if (tid == 0) {
-            dom_s = 0;
-            first_p = n_rows;
-        }
-        double mx = -__builtin_inf();
-        bool dom = false, pos = false;
-        for (int i = tid; i < n_rows; i += 1024) {
-            if (!present(i)) continue;
-            mx = fmax(mx, ws[i]);
-            dom |= ws[i] > mid;
-            pos |= ws[i] > 0.0;
-            atomicMin(&first_p, i);
-        }
-        red[tid] = mx;
-        dom = __syncthreads_or(dom);
-        pos = __syncthreads_or(pos);
-        for (int h = 512; h >= 1; h >>= 1) {
-            if (tid < h) red[tid] = fmax(red[tid], red[tid + h]);
-            __syncthreads();
-        }
-        // (the sequential max of the SPEC starts at the first present weight: a NaN there stays,
-        // and nothing equals it)
-        const double mxa = (n > 0 && __builtin_isnan(ws[first_p])) ? __builtin_nan("") : red[0];
-        if (dom)
-            for (int i = tid; i < n_rows; i += 1024)
-                if (present(i) && ws[i] == mxa) atomicMin(&first_s, i);
-        if (tid == 0) {
-            dom_s = dom ? 1 : 0;
-            wmax_s = pos ? 1.0 : 0.0;
-        }
-        __syncthreads();
-        if (tid == 0 && !dom_s) first_s = -1;
-        __syncthreads();
-    }
-    if (first_s >= 0) {
-        if (tid == 0) sel_done(st, xs[first_s]);
-        return;
-    }
-    if (wmax_s == 0.0) {  // no positive weight: None
-        if (tid == 0) sel_done(st, __builtin_nan(""));
-        return;
-    }
-    // bitonic sort of (x, w) pairs, padded to a power of two with +inf (the absent rows are too)
-    int P = 1;
-    while (P < n_rows) P <<= 1;
-    for (int k = n_rows + tid; k < P; k += 1024) {
-        xs[k] = __builtin_inf();
-        ws[k] = __builtin_inf();
-    }
-    __syncthreads();
-    for (int size = 2; size <= P; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < P / 2; t += 1024) {
-                const int lo = 2 * stride * (t / stride) + (t % stride);
-                const int hi = lo + stride;
-                const bool up = ((lo & size) == 0);
-                const double xa = xs[lo], xb = xs[hi], wa = ws[lo], wb = ws[hi];
-                const bool gt = (xa > xb) || (xa == xb && wa > wb);
-                if (gt == up) {
-                    xs[lo] = xb;
-                    xs[hi] = xa;
-                    ws[lo] = wb;
-                    ws[hi] = wa;
-                }
-            }
-            __syncthreads();
-        }
-    if (tid == 0) {
-        double cum = 0.0;
-        int k = 0;
-        bool fail = false;
-        while (cum <= mid) {
-            if (k == n) {
-                fail = true;
-                break;
-            }
-            cum += ws[k];
-            k++;
-        }
-        double res;
-        if (fail) {
-            res = __builtin_nan("");
-        } else {
-            const double before = cum - ws[k - 1];
-            if (fabs(before - mid) < 2.220446049250313080847e-16) {
-                if (k >= 2)
-                    res = (xs[k - 2] + xs[k - 1]) / 2.0;
-                else
-                    res = n == 1 ? xs[0] / 1.0 : __builtin_nan("");
-            } else {
-                res = xs[k - 1];
-            }
-        }
-        sel_done(st, res);
-    }
-}
-
-// ------------------------------------------------------------------ hard replay
-// Events whose decision sits within rounding of a threshold are replayed in the
-// reference's own order.  Phase 1 (interpolate, :287-309): the present reports of the
-// event in row order with weights rep_j / (sequential total); binary events: the
-// sequential weighted mean then catch; scaled events: weightedstats on those pairs.
-// Phase 2 (:519-523): weightedstats over the filled column with smooth_rep.
-
-// this rank's elements of hard event j in row order -> send[j][0 .. cnt)
-__global__ void __launch_bounds__(1024) k_hard_gather(pcx_mat m, HardArgs h) {
-    const int j = blockIdx.x;
-    const int c = h.cols[j];
-    const ColParam p = col_param(m, c, true);
-    double* out = h.send + (int64_t)j * h.cap * 2;
-    const double* wsrc = m.sel_phase == 1 ? m.rep : m.rowv + RV_SMOOTH * m.n_rows;
-    const int64_t E = m.n_events;
-    const int sidx = m.scaled_index ? m.scaled_index[c] : -1;
-    if (h.modes[j] == HARD_MEDIAN && sidx >= 0) {
-        // a median's values come from T (k_colstats: the rescaled present value, NaN where missing,
-        // one contiguous column) instead of a strided column of the row-major reports
-        const double* Tc = m.T + (int64_t)sidx * m.n_rows;
-        const double g = p.guess;
-        const int64_t nt = block_compact(
-            m.n_rows,
-            [&](int64_t i) {
-                const double v = Tc[i];
-                if (m.sel_phase == 1) return !__builtin_isnan(v);
-                return !__builtin_isnan(__builtin_isnan(v) ? g : v);
-            },
-            [&](int64_t i, int64_t pos) {
-                const double v = Tc[i];
-                out[pos * 2 + 0] = __builtin_isnan(v) ? g : v;
-                out[pos * 2 + 1] = wsrc[i];
-            });
-        if (threadIdx.x == 0) h.send_cnt[j] = nt;
-        return;
-    }
-    const int64_t n = block_compact(
-        m.n_rows,
-        [&](int64_t i) {
-            const double x = rescale(m.reports[i * E + c], p, m.int_dtype);
-            if (m.sel_phase == 1) return !missing(x);
-            return !__builtin_isnan(missing(x) ? p.guess : x);
-        },
-        [&](int64_t i, int64_t pos) {
-            const double x = rescale(m.reports[i * E + c], p, m.int_dtype);
-            out[pos * 2 + 0] = missing(x) ? p.guess : x;
-            out[pos * 2 + 1] = wsrc[i];
-        });
-    if (threadIdx.x == 0) h.send_cnt[j] = n;
-}
-
-// The hard replay's sequential fp64 chains (weightedstats' builtin sums and its walk) run on one
-// lane: a dependent add per element is the floor (~8 cycles).  The lane reads its operands from
-// an LDS tile in 16-element chunks, the next chunk's loads issued before the current chunk's adds,
-// so the LDS latency (~50-60 cycles) hides behind the chain instead of stalling it every 8
-// elements; the tiles are double-buffered: waves 1.. fill tile t+1 while lane 0 chains tile t.
-constexpr int CHAIN = 16;
-
-// acc + t[0] + t[1] + ... + t[len-1], left to right
-__device__ __forceinline__ double chain_add(const double* t, int len, double acc) {
-    double a[CHAIN], b[CHAIN];
-    int k = 0;
-    if (len >= CHAIN) {
-#pragma unroll
-        for (int j = 0; j < CHAIN; j++) a[j] = t[j];
-        for (; k + 2 * CHAIN <= len; k += 2 * CHAIN) {
-#pragma unroll
-            for (int j = 0; j < CHAIN; j++) b[j] = t[k + CHAIN + j];
-#pragma unroll
-            for (int j = 0; j < CHAIN; j++) acc = acc + a[j];
-            if (k + 3 * CHAIN <= len) {
-#pragma unroll
-                for (int j = 0; j < CHAIN; j++) a[j] = t[k + 2 * CHAIN + j];
-            }
-#pragma unroll
-            for (int j = 0; j < CHAIN; j++) acc = acc + b[j];
-        }
-        if (k + CHAIN <= len) {  // a chunk loaded into a[] and not yet added
-#pragma unroll
-            for (int j = 0; j < CHAIN; j++) acc = acc + a[j];
-            k += CHAIN;
-        }
-    }
-    for (; k < len; k++) acc = acc + t[k];
-    return acc;
-}
-
-// sequential left-to-right fp64 sum of f(k), k in [0, n): lane 0 chains, waves 1.. stage the
-// tiles (tile: 2 * TILE doubles of LDS)
-template <class F>
-__device__ double block_serial_sum(int64_t n, F f, double* tile, int TILE) {
-    __shared__ double acc_s;
-    double acc = 0.0;
-    const int loaders = (int)blockDim.x - WAVE;
-    for (int k = threadIdx.x; k < TILE && k < n; k += blockDim.x) tile[k] = f(k);
-    __syncthreads();
-    int it = 0;
-    for (int64_t t0 = 0; t0 < n; t0 += TILE, it++) {
-        const int len = (int)(n - t0 < TILE ? n - t0 : TILE);
-        const double* cur = tile + (it & 1) * TILE;
-        double* nxt = tile + ((it + 1) & 1) * TILE;
-        if (threadIdx.x == 0) {
-            acc = chain_add(cur, len, acc);
-        } else if ((int)threadIdx.x >= WAVE) {
-            const int64_t n0 = t0 + TILE;
-            const int nl = (int)(n - n0 < TILE ? (n - n0 > 0 ? n - n0 : 0) : TILE);
-            for (int k = threadIdx.x - WAVE; k < nl; k += loaders) nxt[k] = f(n0 + k);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) acc_s = acc;
-    __syncthreads();
-    return acc_s;
-}
-
-constexpr int HARD_TILE = 4096;
-
-__global__ void __launch_bounds__(1024) k_hard_prep(pcx_mat m, HardArgs h) {
-    __shared__ double tile[2 * HARD_TILE];
-    __shared__ unsigned long long wkey_s, first_s;
-    __shared__ int pos_s, dom_s, neg_s;
-    const int j = blockIdx.x;
-    const int c = h.cols[j];
-    const int mode = h.modes[j];
-    const int64_t N = m.n_total;
-    double* X = h.X + (int64_t)j * N;
-    double* W = h.W + (int64_t)j * N;
-    double* hs = h.hs + (int64_t)j * 4;
-    // concatenate the ranks' rows (rank order = row order)
-    int64_t n = 0;
-    for (int w = 0; w < m.world; w++) {
-        const int64_t cw = h.recv_cnt[(int64_t)w * h.n_hard + j];
-        const double* src = h.recv + ((int64_t)w * h.n_hard + j) * h.cap * 2;
-        for (int64_t k = threadIdx.x; k < cw; k += blockDim.x) {
-            X[n + k] = src[2 * k];
-            W[n + k] = src[2 * k + 1];
-        }
-        n += cw;
-    }
-    __syncthreads();
-    if (m.sel_phase == 1) {  // weights rep_j / sequential total of the present rep (:294-302)
-        const double tot = block_serial_sum(n, [&](int64_t k) { return W[k]; }, tile, HARD_TILE);
-        for (int64_t k = threadIdx.x; k < n; k += blockDim.x) W[k] = W[k] / tot;
-        __syncthreads();
-    }
-    const int s = m.scaled_index ? m.scaled_index[c] : -1;
-    if (mode == HARD_MEAN) {  // guess = sum_seq(w * x) then catch (:304-309)
-        const double g = block_serial_sum(n, [&](int64_t k) { return W[k] * X[k]; }, tile, HARD_TILE);
-        if (threadIdx.x == 0) {
-            double v = n > 0 ? catch_value(g, m.catch_tolerance) : catch_value(0.0, m.catch_tolerance);
-            if (m.int_dtype) v = trunc(v);
-            m.ev[EV_GUESS * m.n_events + c] = v;
-            hs[2] = 0.0;
-        }
-        return;
-    }
-    uint64_t* st = m.sel_state + (int64_t)s * SELS;
-    const double mid = 0.5 * block_serial_sum(n, [&](int64_t k) { return W[k]; }, tile, HARD_TILE);
-    // dominance: any(w > mid) -> data[first index of max(w)]; no positive weight -> None.
-    // Weights may be negative (a negative reputation): max over order-preserving keys.
-    if (threadIdx.x == 0) {
-        wkey_s = 0;
-        first_s = ~0ull;
-        pos_s = 0;
-        dom_s = 0;
-        neg_s = 0;
-    }
-    __syncthreads();
-    double wl = -__builtin_inf();
-    int posl = 0, doml = 0, negl = 0;
-    for (int64_t k = threadIdx.x; k < n; k += blockDim.x) {
-        wl = fmax(wl, W[k]);
-        posl |= W[k] > 0.0;
-        doml |= W[k] > mid;
-        negl |= W[k] < 0.0;
-    }
-    if (negl) neg_s = 1;
-    wl = wave_max_d(wl);
-    if ((threadIdx.x & 63) == 0) atomicMax(&wkey_s, (unsigned long long)dkey(wl));
-    if (posl) pos_s = 1;
-    if (doml) dom_s = 1;
-    __syncthreads();
-    if (dom_s) {
-        const double wmax = dkey_inv(wkey_s);  // some W[k] > mid: the max is a finite element
-        for (int64_t k = threadIdx.x; k < n; k += blockDim.x)
-            if (W[k] == wmax) {
-                atomicMin(&first_s, (unsigned long long)k);
-                break;
-            }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            sel_done(st, X[first_s]);
-            hs[2] = 0.0;
-        }
-        return;
-    }
-    if (!pos_s) {
-        if (threadIdx.x == 0) {
-            sel_done(st, __builtin_nan(""));
-            hs[2] = 0.0;
-        }
-        return;
-    }
-    uint64_t* keys = h.keys + (int64_t)j * h.P * 2;
-    for (int64_t k = threadIdx.x; k < h.P; k += blockDim.x) {
-        keys[2 * k + 0] = k < n ? dkey(X[k]) : ~0ull;
-        keys[2 * k + 1] = k < n ? dkey(W[k]) : ~0ull;
-    }
-    if (threadIdx.x == 0) {
-        hs[0] = mid;
-        hs[1] = (double)n;
-        hs[2] = 1.0;  // sort + walk pending
-        hs[3] = neg_s ? 1.0 : 0.0;  // some weight < 0: the walk's partial sums are not monotone
-    }
-}
-
-// bitonic sort of every segment keys[j][0 .. P) by (value key, weight key)
-__device__ __forceinline__ bool key_gt(uint64_t ah, uint64_t al, uint64_t bh, uint64_t bl) {
-    return ah > bh || (ah == bh && al > bl);
-}
-
-constexpr int BS_TILE = 4096;  // elements sorted in LDS per block (64 KB)
-
-// stages size <= min(P, BS_TILE) of the network (init) or strides < BS_TILE of one size (merge)
-__global__ void __launch_bounds__(1024) k_bsort_lds(uint64_t* keys, int64_t P, int64_t size_only) {
-    __shared__ uint64_t kh[BS_TILE], kl[BS_TILE];
-    const int64_t tile = P < BS_TILE ? P : BS_TILE;
-    const int64_t base = (int64_t)blockIdx.x * tile;  // global element index (segments are contiguous)
-    for (int k = threadIdx.x; k < tile; k += 1024) {
-        kh[k] = keys[2 * (base + k)];
-        kl[k] = keys[2 * (base + k) + 1];
-    }
-    __syncthreads();
-    const int64_t s0 = size_only ? size_only : 2;
-    const int64_t s1 = size_only ? size_only : tile;
-    for (int64_t size = s0; size <= s1; size <<= 1) {
-        for (int64_t stride = (size_only ? tile : size) >> 1; stride > 0; stride >>= 1) {
-            if (stride >= size) continue;
-            for (int t = threadIdx.x; t < tile / 2; t += 1024) {
-                const int lo = (int)(2 * stride * (t / stride) + (t % stride));
-                const int hi = lo + (int)stride;
-                const int64_t g = (base + lo) % P;  // index within the segment: direction
-                const bool up = (g & size) == 0;
-                const bool gt = key_gt(kh[lo], kl[lo], kh[hi], kl[hi]);
-                if (gt == up) {
-                    const uint64_t a = kh[lo], b = kl[lo];
-                    kh[lo] = kh[hi];
-                    kl[lo] = kl[hi];
-                    kh[hi] = a;
-                    kl[hi] = b;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int k = threadIdx.x; k < tile; k += 1024) {
-        keys[2 * (base + k)] = kh[k];
-        keys[2 * (base + k) + 1] = kl[k];
-    }
-}
-
-__global__ void __launch_bounds__(BT) k_bsort_global(uint64_t* keys, int64_t P, int64_t total, int64_t size,
-                                                     int64_t stride) {
-    for (int64_t t = blockIdx.x * (int64_t)BT + threadIdx.x; t < total / 2; t += (int64_t)gridDim.x * BT) {
-        const int64_t lo = 2 * stride * (t / stride) + (t % stride);
-        const int64_t hi = lo + stride;
-        const bool up = ((lo % P) & size) == 0;
-        const uint64_t ah = keys[2 * lo], al = keys[2 * lo + 1], bh = keys[2 * hi], bl = keys[2 * hi + 1];
-        if (key_gt(ah, al, bh, bl) == up) {
-            keys[2 * lo] = bh;
-            keys[2 * lo + 1] = bl;
-            keys[2 * hi] = ah;
-            keys[2 * hi + 1] = al;
-        }
-    }
-}
-
-// the walk (:weighted_median while loop) over the sorted pairs of each pending event
-__global__ void __launch_bounds__(1024) k_hard_walk(pcx_mat m, HardArgs h) {
-    constexpr int TWS = HARD_TILE + 2 * CHAIN;  // a tile and the padding the chain's prefetch reads
-    __shared__ double tw[2 * TWS];
-    __shared__ int done_s;
-    __shared__ int64_t k_s;
-    __shared__ double cum_s;
-    const int j = blockIdx.x;
-    double* hs = h.hs + (int64_t)j * 4;
-    if (h.modes[j] != HARD_MEDIAN || hs[2] != 1.0) return;
-    const int c = h.cols[j];
-    uint64_t* st = m.sel_state + (int64_t)m.scaled_index[c] * SELS;
-    const uint64_t* keys = h.keys + (int64_t)j * h.P * 2;
-    const double mid = hs[0];
-    const int64_t n = (int64_t)hs[1];
-    const bool monotone = hs[3] == 0.0;  // every weight >= 0: a chunk's last partial is its largest
-    if (threadIdx.x == 0) {
-        done_s = 0;
-        k_s = 0;
-        cum_s = 0.0;
-    }
-    // (a partial tile is followed by zeros: a chunk that runs past the last weight adds + 0.0)
-    for (int k = threadIdx.x; k < TWS; k += blockDim.x) tw[k] = k < n && k < HARD_TILE ? dkey_inv(keys[2 * k + 1]) : 0.0;
-    __syncthreads();
-    // cum += w while cum <= mid (weightedstats' walk; mid > 0 here, so the first add always runs):
-    // lane 0 adds a chunk's weights unconditionally -- partial sums up to the first one above mid
-    // are exactly the walk's -- then finds that first one; waves 1.. stage the next tile meanwhile
-    const int loaders = (int)blockDim.x - WAVE;
-    int it = 0;
-    for (int64_t t0 = 0; t0 < n; t0 += HARD_TILE, it++) {
-        const int len = (int)(n - t0 < HARD_TILE ? n - t0 : HARD_TILE);
-        const double* cur = tw + (it & 1) * TWS;
-        double* nxt = tw + ((it + 1) & 1) * TWS;
-        if (threadIdx.x == 0) {
-            // static register indices only (a dynamic p[hit] sends the array to scratch); the tiles
-            // are padded by 2 CHAIN so the next chunk's loads need no bounds test
-            double cum = cum_s, hit_cum = 0.0;
-            int hit_at = -1;
-            double nv[CHAIN];
-#pragma unroll
-            for (int q = 0; q < CHAIN; q++) nv[q] = cur[q];
-            for (int k = 0; k < len; k += CHAIN) {
-                double v[CHAIN], p[CHAIN];
-#pragma unroll
-                for (int q = 0; q < CHAIN; q++) v[q] = nv[q];  // (past len: the tile's zero padding)
-#pragma unroll
-                for (int q = 0; q < CHAIN; q++) nv[q] = cur[k + CHAIN + q];  // the next chunk, in flight
-                double acc = cum;
-#pragma unroll
-                for (int q = 0; q < CHAIN; q++) {
-                    acc = acc + v[q];
-                    p[q] = acc;
-                }
-                if (monotone && !(acc > mid)) {  // no partial of this chunk exceeds mid
-                    cum = acc;
-                    continue;
-                }
-                int h = -1;
-                double hc = 0.0;
-#pragma unroll
-                for (int q = CHAIN - 1; q >= 0; q--)
-                    if (p[q] > mid) {  // (padded partials repeat the last real one)
-                        h = q;
-                        hc = p[q];
-                    }
-                if (h >= 0) {
-                    hit_at = k + h;
-                    hit_cum = hc;
-                    break;
-                }
-                cum = acc;
-            }
-            if (hit_at >= 0) {
-                cum_s = hit_cum;
-                k_s = t0 + hit_at + 1;
-                done_s = 1;
-            } else {
-                cum_s = cum;
-                k_s = t0 + len;
-            }
-        } else if ((int)threadIdx.x >= WAVE) {
-            const int64_t n0 = t0 + HARD_TILE;
-            const int nl = (int)(n - n0 < HARD_TILE ? (n - n0 > 0 ? n - n0 : 0) : HARD_TILE);
-            for (int k = threadIdx.x - WAVE; k < TWS; k += loaders) nxt[k] = k < nl ? dkey_inv(keys[2 * (n0 + k) + 1]) : 0.0;
-        }
-        __syncthreads();
-        if (done_s) break;
-    }
-    if (threadIdx.x == 0) {
-        double res;
-        const int64_t k = k_s;
-        if (!done_s) {
-            res = __builtin_nan("");  // the walk ran off the end (the reference raises IndexError)
-        } else {
-            const double wk = dkey_inv(keys[2 * (k - 1) + 1]);
-            const double before = cum_s - wk;
-            const double xk = dkey_inv(keys[2 * (k - 1)]);
-            if (fabs(before - mid) < 2.220446049250313080847e-16) {
-                if (k >= 2)
-                    res = (dkey_inv(keys[2 * (k - 2)]) + xk) / 2.0;
-                else
-                    res = n == 1 ? xk / 1.0 : __builtin_nan("");
-            } else {
-                res = xk;
-            }
-        }
-        sel_done(st, res);
-        hs[2] = 0.0;
-    }
-}
-
-// events marked hard (m.hard[c] != 0) in event order -> cols / modes, count -> info[IN_HARD]
-__global__ void __launch_bounds__(1024) k_hard_list(pcx_mat m, int32_t* cols, int32_t* modes) {
-    const int64_t cnt = block_compact(
-        m.n_events, [&](int64_t c) { return m.hard[c] != HARD_NONE; },
-        [&](int64_t c, int64_t pos) {
-            cols[pos] = (int32_t)c;
-            modes[pos] = m.hard[c];
-        });
-    if (threadIdx.x == 0) m.info[IN_HARD] = cnt;
 }
 
 // PCX_M_SCALED_CERT: sum of smooth_rep over rows whose filled value equals the outcome
@@ -5088,14 +3481,14 @@ __global__ void __launch_bounds__(1024) k_final(pcx_mat m) {
         sh[3] = dd_to_double(r3);
         const double avg_cert = dd_to_double(r4) / (double)E;
         const double pna = 1.0 - dd_to_double(r5) / (double)E;
-        m.pvec[3 * (m.n_events + 64) + 4] = pna;
+        pv_s(m)[PS_PNA] = pna;
         if (m.scalars) {
             m.scalars[0] = 1.0 - pna;
             m.scalars[1] = avg_cert;
         }
     }
     __syncthreads();
-    const double pna = m.pvec[3 * (m.n_events + 64) + 4];
+    const double pna = pv_s(m)[PS_PNA];
     const bool rep_masked = rep_fully_masked(m);
     for (int c = threadIdx.x; c < E; c += 1024) {
         const double cert = m.ev[EV_CERT * E + c];
@@ -5138,7 +3531,7 @@ __global__ void __launch_bounds__(BT) k_rowsums(pcx_mat m) {
 __global__ void __launch_bounds__(BT) k_agents(pcx_mat m) {
     const int E = (int)m.n_events;
     const double S = dd_to_double(scl(m, SC_AR)), Sp = dd_to_double(scl(m, SC_ARP));
-    const double pna = m.pvec[3 * (m.n_events + 64) + 4];
+    const double pna = pv_s(m)[PS_PNA];
     const bool rep_masked = rep_fully_masked(m);
     for (int64_t i = blockIdx.x * (int64_t)BT + threadIdx.x; i < m.n_rows; i += (int64_t)gridDim.x * BT) {
         const bool masked = (int)m.rowstat[2 * i] == E;
@@ -5360,13 +3753,6 @@ hipError_t eig_stage(pcx_mat& m, hipStream_t st, std::string& err) {
                        (const double*)coef, (const int*)idx, k, m.ev + EV_SPARE * E);
     m.components = m.algorithm == 3 ? k : -1;
     return hipStreamSynchronize(st);
-}
-
-int grid_rows(int64_t n, int per_block) {
-    int64_t g = (n + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    if (g > 4096) g = 4096;
-    return (int)g;
 }
 
 // ================================================================== clustering algorithms
@@ -5949,39 +4335,6 @@ hipError_t cluster_stage(pcx_mat& m, const ClusterArgs& a, int step, hipStream_t
     return hipGetLastError();
 }
 
-hipError_t hard_stage(pcx_mat& m, const HardArgs& h, int stage, hipStream_t st, std::string& err) {
-    if (h.n_hard <= 0) return hipSuccess;
-    switch (stage) {
-        case M_HARD_GATHER:
-            hipLaunchKernelGGL(k_hard_gather, dim3(h.n_hard), dim3(1024), 0, st, m, h);
-            break;
-        case M_HARD_PREP:
-            hipLaunchKernelGGL(k_hard_prep, dim3(h.n_hard), dim3(1024), 0, st, m, h);
-            break;
-        case M_HARD_SORT: {
-            // bitonic network over n_hard contiguous segments of P (a power of two)
-            const int64_t P = h.P, total = P * h.n_hard;
-            const int64_t tile = P < BS_TILE ? P : BS_TILE;
-            const unsigned nblk = (unsigned)(total / tile);
-            hipLaunchKernelGGL(k_bsort_lds, dim3(nblk), dim3(1024), 0, st, h.keys, P, (int64_t)0);
-            for (int64_t size = tile * 2; size <= P; size <<= 1) {
-                for (int64_t stride = size >> 1; stride >= tile; stride >>= 1)
-                    hipLaunchKernelGGL(k_bsort_global, dim3(grid_rows(total / 2, BT)), dim3(BT), 0, st, h.keys, P,
-                                       total, size, stride);
-                hipLaunchKernelGGL(k_bsort_lds, dim3(nblk), dim3(1024), 0, st, h.keys, P, size);
-            }
-            break;
-        }
-        case M_HARD_WALK:
-            hipLaunchKernelGGL(k_hard_walk, dim3(h.n_hard), dim3(1024), 0, st, m, h);
-            break;
-        default:
-            err = "hard_stage: unknown stage";
-            return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
 // the compact column passes: general tile positions [0, gb) and grid positions [gb, E) as two
 // launches of the same row chunks (blockIdx.y)
 template <class KG, class KR>
@@ -6019,7 +4372,6 @@ hipError_t mat_stage(pcx_mat& m, int stage, hipStream_t st, std::string& err) {
     const int ceb = (E + BT - 1) / BT;
     const dim3 colgrid(ceb, m.col_blocks);
     const int rg = grid_rows(m.n_rows, BT);
-    const int sg = (m.n_scaled + BT - 1) / BT;
     switch (stage) {
         case M_REPUTATION:
             if (m.rep_raw) hipLaunchKernelGGL(k_rep_total, dim3(1), dim3(1024), 0, st, m);
@@ -6300,51 +4652,15 @@ hipError_t mat_stage(pcx_mat& m, int stage, hipStream_t st, std::string& err) {
         case M_WMEAN_OUT:
             hipLaunchKernelGGL(k_wmean_out, dim3(ceb), dim3(BT), 0, st, m);
             break;
-        case M_SEL_INIT:  // status, key range and the active list of the first histogram pass
-            if (m.n_scaled == 0) break;
-            hipLaunchKernelGGL(k_sel_setup, dim3(sg), dim3(BT), 0, st, m);
-            if (m.sel_phase == 2 || m.rep_raw) {
-                const int64_t wb = (m.n_rows + BT - 1) / BT;
-                hipLaunchKernelGGL(k_sel_wlimbs, dim3(wb < 512 ? (wb > 0 ? wb : 1) : 512), dim3(BT), 0, st, m);
-            }
-            hipLaunchKernelGGL(k_sel_range, dim3(sg), dim3(BT), 0, st, m);
-            hipLaunchKernelGGL(k_sel_compact, dim3(1), dim3(1024), 0, st, m);
-            hipLaunchKernelGGL(k_sel_sample, dim3(m.n_scaled), dim3(BT), 0, st, m);
-            break;
+        case M_SEL_INIT:
         case M_SEL_EXACT:
-            if (m.n_scaled == 0) break;
-            if (m.world != 1 || m.n_rows > SEL_EXACT_MAX) {
-                err = "M_SEL_EXACT needs one rank and n_rows <= 8192";
-                return hipErrorInvalidValue;
-            }
-            hipLaunchKernelGGL(k_sel_setup, dim3(sg), dim3(BT), 0, st, m);
-            hipLaunchKernelGGL(k_sel_exact, dim3(m.n_scaled), dim3(1024), 0, st, m);
-            break;
         case M_SEL_START:
-            if (m.n_scaled == 0) break;
-            hipLaunchKernelGGL(k_info_clear, dim3(1), dim3(1), 0, st, m, (int)IN_SEL_ARGMAX);
-            hipLaunchKernelGGL(k_sel_start, dim3((unsigned)((m.n_scaled + BT / WAVE - 1) / (BT / WAVE))), dim3(BT), 0,
-                               st, m);
-            break;
         case M_SEL_ARGMAX:
-            if (m.n_scaled == 0) break;
-            hipLaunchKernelGGL(k_sel_argmax, dim3(m.n_scaled), dim3(BT), 0, st, m);
-            break;
         case M_SEL_VALUE:
-            if (m.n_scaled == 0) break;
-            hipLaunchKernelGGL(k_sel_value, dim3(sg), dim3(BT), 0, st, m);
-            break;
         case M_SEL_VALUE_FINISH:
-            if (m.n_scaled == 0) break;
-            hipLaunchKernelGGL(k_sel_value_finish, dim3(sg), dim3(BT), 0, st, m);
-            break;
         case M_SEL_COMPACT:
-            hipLaunchKernelGGL(k_sel_compact, dim3(1), dim3(1024), 0, st, m);
-            break;
         case M_SEL_FINISH:
-            if (m.n_scaled == 0) break;
-            hipLaunchKernelGGL(k_sel_finish, dim3(sg), dim3(BT), 0, st, m);
-            break;
+            return select_stage(m, stage, st, err);
         case M_POWER: {
             // replicated on every rank (C is identical everywhere); host loop with polling.  The
             // finite / non-zero flags of C come from M_COV_REDUCE (one rank) or M_COV_FINISH and are
@@ -6363,9 +4679,7 @@ hipError_t mat_stage(pcx_mat& m, int stage, hipStream_t st, std::string& err) {
                 // between the two working matrices (the same leading eigenvector, gap ratio squared)
                 const double* M = m.C;
                 double* Tm = m.Mw;
-                // (info word 15: free -- word 8 holds the plan's general count, which the compact
-                // passes after this stage read)
-                unsigned long long* mxb = (unsigned long long*)&m.info[15];
+                unsigned long long* mxb = (unsigned long long*)&m.info[IN_PI_MAXBITS];
                 const int64_t* fl = &m.info[IN_FLAGS];
                 // split-K squaring for E >= 512 when the slabs fit the covariance's (free by now);
                 // smaller E keeps the single pass (the goldens' arithmetic)
@@ -6399,7 +4713,7 @@ hipError_t mat_stage(pcx_mat& m, int stage, hipStream_t st, std::string& err) {
                 const bool early = presq == 0;
                 const int maxit = 2048, poll = 8;
                 int since = 0;
-                double ps[3] = {1.0, 0.0, 0.0};  // delta, converged, steps (pv_s)
+                double ps[PS_STEPS + 1] = {1.0, 0.0, 0.0};  // (the power iteration's pv_s words)
                 while (iters < maxit) {
                     for (int k = 0; k < poll; k++) {
                         if (early && E % 2 == 0)
@@ -6408,19 +4722,19 @@ hipError_t mat_stage(pcx_mat& m, int stage, hipStream_t st, std::string& err) {
                             hipLaunchKernelGGL(k_pi_gemv, dim3(gb), dim3(BT), 0, st, m, M, (int)early);
                         hipLaunchKernelGGL(k_pi_norm, dim3(1), dim3(1024), 0, st, m, (int)early);
                     }
-                    e = hipMemcpyAsync(ps, m.pvec + 3 * (E + 64), sizeof(ps), hipMemcpyDeviceToHost, st);
+                    e = hipMemcpyAsync(ps, m.pvec + PV_S * pv_stride(E), sizeof(ps), hipMemcpyDeviceToHost, st);
                     if (e == hipSuccess) e = hipStreamSynchronize(st);
                     if (e != hipSuccess) return e;
-                    iters = early ? (int)ps[2] : iters + poll;
+                    iters = early ? (int)ps[PS_STEPS] : iters + poll;
                     since += poll;
-                    if (early ? ps[1] != 0.0 : ps[0] <= PI_TOL_M) break;
+                    if (early ? ps[PS_DONE] != 0.0 : ps[PS_DELTA] <= PI_TOL_M) break;
                     if (since >= 32 && sq < 8) {
                         square();
                         sq++;
                         since = 0;
                     }
                 }
-                if (!(ps[0] <= PI_TOL_M)) maxit_flag = 4;
+                if (!(ps[PS_DELTA] <= PI_TOL_M)) maxit_flag = 4;
                 if (sq > 0)  // polish with C itself (after squarings)
                     for (int k = 0; k < 4; k++) {
                         hipLaunchKernelGGL(k_pi_gemv, dim3(gb), dim3(BT), 0, st, m, (const double*)m.C, 0);
@@ -6449,41 +4763,8 @@ hipError_t mat_stage(pcx_mat& m, int stage, hipStream_t st, std::string& err) {
     return hipGetLastError();
 }
 
-// hard-list compaction (events with m.hard[c] != 0) into cols / modes, count -> info[IN_HARD]
-hipError_t hard_list(pcx_mat& m, int32_t* cols, int32_t* modes, hipStream_t st) {
-    hipLaunchKernelGGL(k_hard_list, dim3(1), dim3(1024), 0, st, m, cols, modes);
-    return hipGetLastError();
-}
-
-hipError_t sel_hist(pcx_mat& m, int n_active, hipStream_t st) {
-    if (n_active <= 0) return hipSuccess;
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-            ncu = n;
-        if (ncu <= 0) ncu = 256;
-    }
-    const bool cm = m.sel_phase == 1 && !m.rep_raw && m.n_rows < (1ll << 32);  // (every pass of this phase counts)
-    if (n_active <= ncu) {
-        if (cm)
-            hipLaunchKernelGGL((k_sel_hist<1024, true>), dim3(n_active), dim3(1024), 0, st, m);
-        else
-            hipLaunchKernelGGL((k_sel_hist<1024, false>), dim3(n_active), dim3(1024), 0, st, m);
-    } else if (cm) {  // (49 VGPRs: eight waves per SIMD, so 512 threads an event at four events a CU)
-        hipLaunchKernelGGL((k_sel_hist<512, true>), dim3(n_active), dim3(512), 0, st, m);
-    } else {
-        // (weight mode: 107 VGPRs, four waves per SIMD; with 75 VGPRs and 384 threads an event the
-        // weight passes ran 5.1 vs 4.5 ms at C5 -- more waves contend for the LDS atomics)
-        hipLaunchKernelGGL((k_sel_hist<BT, false>), dim3(n_active), dim3(BT), 0, st, m);
-    }
-    return hipGetLastError();
-}
-
-hipError_t sel_step(pcx_mat& m, int n_active, hipStream_t st) {
-    if (n_active <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_sel_step, dim3((n_active + BT / WAVE - 1) / (BT / WAVE)), dim3(BT), 0, st, m, n_active);
-    return hipGetLastError();
+void info_clear(const pcx_mat& m, int slot, hipStream_t st) {
+    hipLaunchKernelGGL(k_info_clear, dim3(1), dim3(1), 0, st, m, slot);
 }
 
 }  // namespace pcx

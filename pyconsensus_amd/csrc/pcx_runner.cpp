@@ -1,6 +1,6 @@
 // pcx_runner.cpp -- the single-matrix consensus as ONE library call.
 //
-// Sequences the stages of pcx_matrix.hip for Oracle.consensus() (__init__.py:502-611)
+// Sequences the stages of mat_stage (pcx_matrix.hip, pcx_mat_*.hip) for Oracle.consensus() (__init__.py:502-611)
 // and for the reference's stage methods (interpolate / wpca / lie_detector /
 // nonconformity(_rank), :260-500); owns the scratch (cached per context) and the
 // cross-rank exchange between stages (pcx_comm.cpp: RCCL, in-process group, callbacks).
@@ -27,18 +27,11 @@
 #include <vector>
 
 #include "pcx_internal.h"
+#include "pcx_mat_layout.h"
 #include "pcx_sync.h"
 
 namespace {
-constexpr int BT = 256;
-constexpr int CS = 16;  // dd slots per column in cstat
-constexpr int CM = 8;   // doubles per column in mpart / cmax
-constexpr int EV_SLOTS = 19;  // E-sized rows of ev (pcx_matrix.hip ev_slot)
-constexpr int SS = 16;  // dd slots in scal
-constexpr int SC_BIGTOK_SLOT = 10;  // scal slot: count of tokens outside [0, 63] (pcx_matrix.hip SC_BIGTOK)
-constexpr int COV_TILE = 128;
 constexpr int COV_STAGE = 64 * PCX_GEMM_KS > 128 ? 64 * PCX_GEMM_KS : 128;  // wcd rows: whole stages of the int8 GEMM
-constexpr int SELS = 40;
 // k-slice cost model of the covariance products (calibrated on C5, profiles/r3): one 64-row
 // stage of one 256 x 256 int8 tile, one 8-row stage of one 128 x 128 fp64 tile (3 per CU), and
 // the effective rate at which a slab is written and read back by k_cov_reduce
@@ -257,12 +250,12 @@ pcx_workspace* workspace(pcx_ctx* c, int64_t n_rows, int64_t E, int64_t n_total,
         {(void**)&w->zsum, (size_t)E * 8, true},
         {(void**)&w->scal, (size_t)(world * SS * 2) * 8, true},
         {(void**)&w->spart, (size_t)(4096 * 8) * 8, true},
-        {(void**)&w->ev, (size_t)(EV_SLOTS * E) * 8, true},
-        {(void**)&w->pvec, (size_t)(4 * (E + 64)) * 8, true},
-        {(void**)&w->rowv, (size_t)(6 * n_rows) * 8, true},
+        {(void**)&w->ev, (size_t)(EV_NSLOT * E) * 8, true},
+        {(void**)&w->pvec, (size_t)(PV_NROW * pv_stride(E)) * 8, true},
+        {(void**)&w->rowv, (size_t)(RV_NSLOT * n_rows) * 8, true},
         {(void**)&w->rowstat, (size_t)(2 * n_rows) * 4, true},
         {(void**)&w->skey, (size_t)(world * 4) * 8, true},
-        {(void**)&w->info, (size_t)16 * 8, true},
+        {(void**)&w->info, (size_t)IN_NSLOT * 8, true},
         {(void**)&w->sel_state, (size_t)(S * SELS) * 8, true},
         {(void**)&w->sel_isum, (size_t)(S * 4) * 8, true},
 
@@ -627,7 +620,7 @@ void hard_replay(Run& R, pcx_mat& m, pcx_workspace* w, pcx_result* res, int64_t 
         R.mark(M_HARD_LIST);
         R.hip(hard_list(m, w->hard_cols, w->hard_modes, R.st), "k_hard_list");
         R.mark(-1);
-        H = R.read(m.info + INFO_HARD);
+        H = R.read(m.info + IN_HARD);
     }
     if (H <= 0) return;
     res->n_hard += (int32_t)H;
@@ -743,7 +736,7 @@ void select(Run& R, pcx_mat& m, pcx_workspace* w, int phase, pcx_result* res) {
         R.mark(-1);
         R.stage(m, M_SEL_COMPACT);
         int64_t inf5[5];  // active, argmax, (pick1), (hard), weight-mode active
-        R.hip(hipMemcpyAsync(inf5, m.info + INFO_SEL_ACTIVE, sizeof(inf5), hipMemcpyDeviceToHost, R.st), "D2H");
+        R.hip(hipMemcpyAsync(inf5, m.info + IN_SEL_ACTIVE, sizeof(inf5), hipMemcpyDeviceToHost, R.st), "D2H");
         R.sync();
         int64_t active = inf5[0], wactive = inf5[4];
         known_H = inf5[3];
@@ -790,7 +783,7 @@ void select(Run& R, pcx_mat& m, pcx_workspace* w, int phase, pcx_result* res) {
                 R.check_err(sel_step(m, (int)a_ub, R.st), "k_sel_step");
                 R.mark(-1);
                 R.stage(m, M_SEL_COMPACT);
-                R.hip(hipMemcpyAsync(c->sel_pin + 8 * slot, m.info + INFO_SEL_ACTIVE, 5 * sizeof(int64_t),
+                R.hip(hipMemcpyAsync(c->sel_pin + 8 * slot, m.info + IN_SEL_ACTIVE, 5 * sizeof(int64_t),
                                      hipMemcpyDeviceToHost, R.st),
                       "D2H");
                 R.hip(hipEventRecord(c->sel_ev[slot], R.st), "event record");
@@ -1225,7 +1218,7 @@ int run_matrix(pcx_ctx* c, const pcx_problem* p, pcx_result* r, int entry, const
         const int64_t cpitch = CS * 2;
         // a1: reputation, tokens (:138-146)
         R.stage(m, M_REPUTATION);
-        R.gather_slots(w->scal, 1, SS * 2, 0, SC_BIGTOK_SLOT + 2, w);  // .. SC_MAXTOK
+        R.gather_slots(w->scal, 1, SS * 2, 0, SC_MAXTOK + 1, w);
         // a2/a3: rescale + NA + present sums (:266-299)
         R.stage(m, M_COLSTATS);
         R.gather_slots(w->cstat, E, cpitch, 0, 4, w);
@@ -1253,7 +1246,7 @@ int run_matrix(pcx_ctx* c, const pcx_problem* p, pcx_result* r, int entry, const
                 m.escale = w->dscale + w->wcd_ld;
                 R.stage(m, M_COV_PLAN);
                 int64_t plan[3];  // general events, mixed pairs on int8, every token the same power of two
-                R.hip(hipMemcpyAsync(plan, m.info + INFO_COV_GENERAL, sizeof(plan), hipMemcpyDeviceToHost, R.st),
+                R.hip(hipMemcpyAsync(plan, m.info + IN_COV_GENERAL, sizeof(plan), hipMemcpyDeviceToHost, R.st),
                       "D2H plan");
                 R.sync();
                 const int64_t n_general = plan[0];
@@ -1403,7 +1396,7 @@ int run_matrix(pcx_ctx* c, const pcx_problem* p, pcx_result* r, int entry, const
                     // the covariance is recomputed: the remaining digit pairs, or fp64 (k_syrk)
                     R.stage(m, M_COV_GUARD);
                     int64_t gi[3];
-                    R.hip(hipMemcpyAsync(gi, m.info + INFO_COV_GUARD, sizeof(gi), hipMemcpyDeviceToHost, R.st),
+                    R.hip(hipMemcpyAsync(gi, m.info + IN_COV_GUARD, sizeof(gi), hipMemcpyDeviceToHost, R.st),
                           "D2H guard");
                     R.sync();
                     r->cov_guard = (int32_t)gi[0];
@@ -1430,7 +1423,7 @@ int run_matrix(pcx_ctx* c, const pcx_problem* p, pcx_result* r, int entry, const
                 // covariance makes the reference's second svd raise (Oracle: LinAlgError).  (PCA
                 // needs no flags on the host here: no read, no sync)
                 if (entry != 2 && alg != PCX_ALG_PCA && !clustering) {
-                    flags = R.read(m.info + INFO_FLAGS);
+                    flags = R.read(m.info + IN_FLAGS);
                     if (!(flags & PCX_FLAG_SVD_FAIL)) R.stage(m, M_EIG);
                 }
             } else {
@@ -1446,13 +1439,13 @@ int run_matrix(pcx_ctx* c, const pcx_problem* p, pcx_result* r, int entry, const
             if (entry == 2) {
                 R.stage(m, M_WMEAN_OUT);
                 if (cov_out) R.hip(hipMemcpyAsync(cov_out, w->C, E * E * 8, hipMemcpyDeviceToDevice, R.st), "cov");
-                if (ld_out) R.hip(hipMemcpyAsync(ld_out, w->ev + 3 * E, E * 8, hipMemcpyDeviceToDevice, R.st), "ld");
+                if (ld_out) R.hip(hipMemcpyAsync(ld_out, w->ev + EV_LD * E, E * 8, hipMemcpyDeviceToDevice, R.st), "ld");
                 if (sc_out) R.hip(hipMemcpyAsync(sc_out, w->rowv, n_rows * 8, hipMemcpyDeviceToDevice, R.st), "scores");
             } else {
                 if ((alg != PCX_ALG_ABSOLUTE && !clustering) || entry == 4) {
                     // a8/a9: sign-choice rule (:487-500; the other algorithms: nonconformity, :475-485)
                     R.stage(m, M_NCSUMS);
-                    R.gather_slots(w->scal, 1, SS * 2, 2, 6, w);
+                    R.gather_slots(w->scal, 1, SS * 2, SC_A1, SC_A2P + 1, w);
                     R.stage(m, M_GEMV2);
                     R.gather_slots(w->cstat, E, cpitch, 4, 6, w);
                     R.stage(m, M_DECIDE);
@@ -1462,12 +1455,12 @@ int run_matrix(pcx_ctx* c, const pcx_problem* p, pcx_result* r, int entry, const
                 } else {
                     // a10: reputation update (:460-472)
                     R.stage(m, M_REPU);
-                    R.gather_slots(w->scal, 1, SS * 2, 6, 8, w);
+                    R.gather_slots(w->scal, 1, SS * 2, SC_U, SC_UP + 1, w);
                     R.stage(m, M_SMOOTH);
                     if (lie) {
                         R.stage(m, M_AGENTS);
                         if (ld_out)
-                            R.hip(hipMemcpyAsync(ld_out, w->ev + 3 * E, E * 8, hipMemcpyDeviceToDevice, R.st), "ld");
+                            R.hip(hipMemcpyAsync(ld_out, w->ev + EV_LD * E, E * 8, hipMemcpyDeviceToDevice, R.st), "ld");
                     } else {
                         // a12-a14: outcomes, participation, certainty (:510-546)
                         R.stage(m, M_OUTCOMES);
@@ -1479,7 +1472,7 @@ int run_matrix(pcx_ctx* c, const pcx_problem* p, pcx_result* r, int entry, const
                         R.gather_slots(w->cstat, E, cpitch, 14, 16, w);
                         R.stage(m, M_FINAL);
                         R.stage(m, M_ROWSUMS);
-                        R.gather_slots(w->scal, 1, SS * 2, 8, 10, w);
+                        R.gather_slots(w->scal, 1, SS * 2, SC_AR, SC_ARP + 1, w);
                         R.stage(m, M_AGENTS);
                         if (!mats_written) R.stage(m, M_MATRICES);
                     }
@@ -1518,9 +1511,9 @@ int run_matrix(pcx_ctx* c, const pcx_problem* p, pcx_result* r, int entry, const
         r->participation = sc2[0];
         r->avg_certainty = sc2[1];
         const bool branchless = (alg == PCX_ALG_ABSOLUTE && entry != 4) || clustering || entry == 1 || entry == 2;
-        r->branch = branchless ? PCX_BRANCH_NONE : (int32_t)info[INFO_BRANCH];
-        r->pi_iters = (int32_t)info[INFO_PI_ITERS];
-        r->flags = (int32_t)info[INFO_FLAGS];
+        r->branch = branchless ? PCX_BRANCH_NONE : (int32_t)info[IN_BRANCH];
+        r->pi_iters = (int32_t)info[IN_PI_ITERS];
+        r->flags = (int32_t)info[IN_FLAGS];
         r->components = m.components;
         r->comm_bytes = R.comm_bytes;
         // per-stage device time

@@ -9,7 +9,7 @@ result is computed by libpcx's HIP kernels:
   kernel (csrc/pcx_batched.hip) -- the same kernel as the batched Monte Carlo
   regime, with a batch of one;
 * larger matrices run the single-matrix pipeline (one call of pcx_consensus_f64,
-  csrc/pcx_runner.cpp + csrc/pcx_matrix.hip) on one GPU, or -- with
+  csrc/pcx_runner.cpp + csrc/pcx_matrix.hip, csrc/pcx_mat_*.hip) on one GPU, or -- with
   ``devices=[0, 1, ...]`` -- row-sharded over several GPUs of this process
   (pcx_create_devices: one worker thread per GPU, RCCL over xGMI inside libpcx).
 

@@ -1,4 +1,4 @@
-"""The rescale division of the single-matrix kernels (csrc/pcx_matrix.hip div_rn): (r - lo) /
+"""The rescale division of the single-matrix kernels (csrc/pcx_mat_device.h div_rn): (r - lo) /
 range as q0 = d y, r = fma(-q0, b, d), q = fma(r, y, q0) with y = RN(1 / b), falling back to the
 division where an intermediate leaves the normal range.  The reference divides
 (pyconsensus/__init__.py:266-269, numpy's IEEE division), so the sequence with its guard must
@@ -25,7 +25,7 @@ SRC = textwrap.dedent(r"""
         double a = fabs(b);
         return (a >= 0x1p-100 && a <= 0x1p100) ? 1.0 / b : NAN;
     }
-    static double div_rn(double d, double b, double y) {  /* pcx_matrix.hip div_rn */
+    static double div_rn(double d, double b, double y) {  /* pcx_mat_device.h div_rn */
         volatile double q0 = d * y;
         volatile double r = fma(-q0, b, d);
         double q = fma(r, y, q0);

@@ -1,4 +1,4 @@
-"""GPU parity of the single-matrix pipeline (csrc/pcx_matrix.hip via pipeline.py).
+"""GPU parity of the single-matrix pipeline (csrc/pcx_matrix.hip and pcx_mat_*.hip via pipeline.py).
 
 * golden vectors (KATs, mixed shapes, synthetic 50x20, C2 1000x100) forced through
   the matrix path, north_star tolerances, near-tie rounds counted separately;
