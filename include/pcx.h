@@ -285,6 +285,69 @@ int pcx_sim_metrics_f64(pcx_ctx* ctx, const pcx_sim* sim, const pcx_sim_rounds* 
 int pcx_simulate_f64(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* result);
 
 /* ------------------------------------------------------------------------ */
+/* Simulator sweeps (added under ABI 9; detect by symbol): C cells, each with   */
+/* its own number of rounds, shape, generator probabilities and seed, in one    */
+/* call (a curve or a grid of a Monte Carlo study).  The rounds of all cells lie */
+/* end to end in cell order in pcx_ragged's flat layout: B = sum R_c rounds,     */
+/* reporter arrays [sum R_c N_c], event arrays [sum R_c E_c], reports            */
+/* [sum R_c N_c E_c].  Cell c's slice of every output is byte for byte what      */
+/* pcx_simulate_f64 gives for n_rounds = R_c, n_reporters = N_c, n_events = E_c, */
+/* the cell's seed and probabilities and the shared parameters: the generator's  */
+/* round counter is the round's index inside its cell and its key the cell's     */
+/* seed, so cells that share a seed see common random numbers.  "big-five" caps  */
+/* max_components at E_c on the device (the equal-shape call it compares with     */
+/* gets min(max_components, E_c)); "clusterfeck" with cluster_threshold <= 0      */
+/* takes the device's per-round rule, as pcx_consensus_ragged_wide_f64.           */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+    int64_t  n_rounds;            /* R_c in [1, 2^31)                            */
+    int32_t  n_reporters;         /* N_c in [1, 256]                             */
+    int32_t  n_events;            /* E_c in [1, 64]                              */
+    uint64_t seed;                /* the cell's Philox key                       */
+    double  liar_frac, collude_frac, distort, na_frac, scaled_frac;  /* as pcx_sim's */
+} pcx_sim_cell;
+
+typedef struct {
+    int64_t  n_cells;             /* C; 0 succeeds and launches nothing          */
+    const pcx_sim_cell* cells;    /* HOST [C]                                    */
+    int64_t  n_timesteps;         /* T in [1, 2^24)                              */
+    double  scaled_tol;
+    /* the consensus parameters, shared by the cells (k-means and cokurtosis are refused) */
+    double  catch_tolerance;
+    double  alpha;
+    int32_t algorithm;
+    int32_t max_components;
+    double  variance_threshold;
+    double  hierarchy_threshold;
+    double  cluster_threshold;
+    const double* reputation0;    /* DEVICE [sum R_c N_c] reputation of timestep 0, or NULL = uniform */
+} pcx_sim_sweep;
+
+/* Pure (no context, no device): validates a sweep.  totals = {B, sum R_c N_c, sum R_c E_c,
+ * sum R_c N_c E_c}; counts / lds_bytes are what pcx_ragged_plan_wide reports for the sweep's
+ * rounds.  On refusal returns PCX_EINVAL with *bad_cell = the first offending cell (-1: a shared
+ * parameter); pcx_last_error names it.  Any output may be NULL. */
+int pcx_sim_sweep_plan(const pcx_sim_sweep* sweep, int64_t totals[4], int64_t counts[4], int64_t lds_bytes[4],
+                       int64_t* bad_cell);
+/* The sweep's rounds of one timestep on the CPU (HOST pointers, no context; flat layout), from
+ * the same inline code as the device kernel. */
+int pcx_sim_sweep_generate_host(const pcx_sim_sweep* sweep, int timestep, pcx_sim_rounds* rounds);
+/* The same on the device; asynchronous on the context's stream. */
+int pcx_sim_sweep_generate_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, int timestep, pcx_sim_rounds* rounds);
+/* Score the sweep's rounds: metrics [B][PCX_SIM_NMETRICS] (required), summary
+ * [C][PCX_SIM_NMETRICS] or NULL: each cell's means over its R_c rounds in pcx_simulate_f64's
+ * summary order.  rounds->scaled, lo, hi, truth and liar are required.  Asynchronous. */
+int pcx_sim_sweep_metrics_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const pcx_sim_rounds* rounds,
+                              const double* old_rep, const double* smooth_rep, const double* outcomes_final,
+                              double* metrics, double* summary);
+/* T timesteps of generate -> pcx_consensus_ragged_wide_f64's launches -> metrics -> per-cell
+ * summary -> reputation carry, asynchronous on the context's stream with no host wait in the
+ * loop (the descriptor tables are built and uploaded once per call).  The result is read with
+ * flat layouts: metrics [T][B][6], summary [T][C][6], reputation [sum R_c N_c], last / last_out as
+ * pcx_ragged's flat arrays.  The work buffers are pcx_simulate_f64's (kept in the context). */
+int pcx_simulate_sweep_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* result);
+
+/* ------------------------------------------------------------------------ */
 /* Single-matrix regime: one N x E report matrix, optionally sharded by        */
 /* contiguous reporter rows over several GPUs (one process -- or one thread --  */
 /* per rank).  One call runs the whole Oracle(...).consensus() of              */

@@ -126,6 +126,24 @@ class SimResult(C.Structure):
                 ("last", SimRounds), ("last_out", BatchResult)]
 
 
+class SimCell(C.Structure):
+    """pcx_sim_cell: one cell of a sweep (its rounds, shape, seed and generator probabilities)."""
+    _fields_ = [
+        ("n_rounds", C.c_int64), ("n_reporters", C.c_int32), ("n_events", C.c_int32), ("seed", C.c_uint64),
+        ("liar_frac", C.c_double), ("collude_frac", C.c_double), ("distort", C.c_double),
+        ("na_frac", C.c_double), ("scaled_frac", C.c_double)]
+
+
+class SimSweep(C.Structure):
+    """pcx_sim_sweep: C cells (a HOST array) and the parameters they share."""
+    _fields_ = [
+        ("n_cells", C.c_int64), ("cells", C.c_void_p), ("n_timesteps", C.c_int64),
+        ("scaled_tol", C.c_double), ("catch_tolerance", C.c_double), ("alpha", C.c_double),
+        ("algorithm", C.c_int32), ("max_components", C.c_int32),
+        ("variance_threshold", C.c_double), ("hierarchy_threshold", C.c_double),
+        ("cluster_threshold", C.c_double), ("reputation0", C.c_void_p)]
+
+
 # ---------------------------------------------------------------- single-matrix regime
 MEM_DEVICE, MEM_HOST = 0, 1
 F64, U64 = 0, 1                  # enum pcx_dtype

@@ -16,6 +16,7 @@
 
 #include "../../include/pcx.h"
 #include "pcx_internal.h"
+#include "pcx_sim_sweep.h"
 #include "pcx_sync.h"
 #include "pcx_seqsum.h"
 
@@ -665,6 +666,108 @@ int pcx_test_scratch_cap(pcx_ctx* ctx, int64_t bytes) {
     return PCX_OK;
 }
 
+// The descriptor tables of one wide ragged call in a staging slot, and what its launches need of
+// them.  They depend on the rounds' shapes and the algorithm alone, not on any data pointer:
+// pcx_consensus_ragged_wide_f64 builds them, uploads them and launches once; a simulator sweep
+// (pcx_simulate_sweep_f64) builds and uploads them once and launches every timestep.
+struct WidePlan {
+    pcx_ctx::RaggedSlot* slot = nullptr;
+    int64_t B = 0, nw = 0, nm = 0, chunk = 0;
+    int64_t cnt[4] = {0, 0, 0, 0}, lds[4] = {0, 0, 0, 0}, first[4] = {0, 0, 0, 0}, stride[3] = {0, 0, 0};
+    // slot offsets: the workgroup rounds' descriptors, the wave rounds' indices, the caller's `extra`
+    // bytes; `bytes` are uploaded, the wave rounds' six [B] outputs follow at off_t on the device
+    size_t off_m = 0, off_i = 0, off_x = 0, bytes = 0, off_t = 0;
+    bool filled = false;  // the caller gives `filled`: no N x E scratch of the library's
+};
+
+// Plan's tables into a staging slot taken here (cnt / lds as ragged_plan_wide found them), the
+// workgroup scratch reserved; `extra` bytes (a multiple of 8) of the caller's ride along at off_x.
+// One staging slot, one upload: the wave rounds' descriptors, the workgroup rounds' descriptors
+// class after class (3, 2, 1; a class's rounds in their order), the wave rounds' indices.  The
+// device side holds, past what is uploaded, the wave rounds' six [B] outputs until their scatter.
+// With wave rounds only (nm == 0) the first table is pcx_consensus_ragged_f64's own.
+static int wide_tables(pcx_ctx* ctx, int64_t B, const int32_t* n_reporters, const int32_t* n_events, int algorithm,
+                       bool one_class, const int64_t cnt[4], const int64_t lds[4], bool filled, size_t extra,
+                       WidePlan* plan) {
+    WidePlan& p = *plan;
+    p.B = B;
+    p.nw = cnt[0];
+    p.nm = B - p.nw;
+    p.filled = filled;
+    for (int k = 0; k < 4; k++) {
+        p.cnt[k] = cnt[k];
+        p.lds[k] = lds[k];
+    }
+    const int64_t nw = p.nw, nm = p.nm;
+    p.off_m = (size_t)nw * sizeof(pcx::RaggedDesc);
+    p.off_i = p.off_m + (size_t)nm * sizeof(pcx::MediumDesc);
+    p.off_x = (p.off_i + (size_t)nw * sizeof(int32_t) + 7) / 8 * 8;
+    p.bytes = p.off_t = p.off_x + extra;
+    if (const int rc = ragged_slot_take(ctx, p.off_t + (size_t)nw * 32, &p.slot)) return rc;
+    char* pin = static_cast<char*>(p.slot->pin);
+    pcx::RaggedDesc* dw = reinterpret_cast<pcx::RaggedDesc*>(pin);
+    pcx::MediumDesc* dm = reinterpret_cast<pcx::MediumDesc*>(pin + p.off_m);
+    int32_t* idx = reinterpret_cast<int32_t*>(pin + p.off_i);
+    int64_t at[4] = {0, 0, 0, 0};  // next entry of each class in dm: class 3 first
+    at[2] = cnt[3];
+    at[1] = cnt[3] + cnt[2];
+    for (int k = 0; k < 4; k++) p.first[k] = k ? at[k] : 0;
+    int64_t cell = 0, row = 0, ev = 0, w = 0;
+    for (int64_t b = 0; b < B; b++) {
+        const int32_t N = n_reporters[b], E = n_events[b];
+        const int k = wide_slot(N, E, algorithm, one_class);
+        if (k == 0) {
+            dw[w] = pcx::RaggedDesc{cell, row, ev, N, E};
+            idx[w++] = (int32_t)b;
+        } else {
+            dm[at[k]++] = pcx::MediumDesc{cell, row, ev, N, E, (int32_t)b, 0};
+            pcx::medium_slot_strides(N, E, algorithm, p.stride);
+        }
+        cell += (int64_t)N * E;
+        row += N;
+        ev += E;
+    }
+    if (nm == 0) return PCX_OK;
+    // the workgroup scratch: slot strides of the call's largest round, chunks that fit the cap
+    const size_t cap = ctx->test_scratch_cap > 0 ? (size_t)ctx->test_scratch_cap : MEDIUM_SCRATCH_CAP;
+    const size_t per = (size_t)((filled ? 0 : p.stride[0]) + p.stride[1] + p.stride[2]) * sizeof(double);
+    p.chunk = std::min<int64_t>(std::max<int64_t>((int64_t)(cap / per), 1), nm);
+    return medium_scratch_reserve(ctx, per * (size_t)p.chunk);
+}
+
+// the launches of a wide ragged call over uploaded tables, with these inputs, options and outputs
+static hipError_t wide_launch(pcx_ctx* ctx, const WidePlan& p, const pcx::BatchArgs& a) {
+    char* dev = static_cast<char*>(p.slot->dev);
+    const int64_t nw = p.nw;
+    if (p.nm == 0)
+        return pcx::launch_ragged(a, reinterpret_cast<const pcx::RaggedDesc*>(dev), (size_t)p.lds[0], ctx->stream);
+    double* Fscr = (double*)ctx->mscr;
+    double* Cscr = Fscr + (p.filled ? 0 : (size_t)p.chunk * p.stride[0]);
+    double* Xscr = Cscr + (size_t)p.chunk * p.stride[1];
+    hipError_t e = hipSuccess;
+    if (nw > 0) {
+        pcx::BatchArgs aw = a;
+        aw.B = nw;
+        const pcx::WaveTmp t = pcx::ragged_wave_tmp(dev + p.off_t, nw);
+        aw.participation = t.participation;
+        aw.avg_certainty = t.avg_certainty;
+        aw.branch = t.branch;
+        aw.flags = t.flags;
+        aw.pi_iters = t.pi_iters;
+        aw.components = t.components;
+        e = pcx::launch_ragged(aw, reinterpret_cast<const pcx::RaggedDesc*>(dev), (size_t)p.lds[0], ctx->stream);
+        if (e == hipSuccess)
+            e = pcx::launch_ragged_scatter(a, reinterpret_cast<const int32_t*>(dev + p.off_i), nw, dev + p.off_t,
+                                           ctx->stream);
+    }
+    const pcx::MediumDesc* ddm = reinterpret_cast<const pcx::MediumDesc*>(dev + p.off_m);
+    for (int k = 3; k >= 1 && e == hipSuccess; k--)
+        for (int64_t b0 = 0; b0 < p.cnt[k] && e == hipSuccess; b0 += p.chunk)
+            e = pcx::launch_ragged_medium(a, ddm + p.first[k] + b0, std::min<int64_t>(p.chunk, p.cnt[k] - b0),
+                                          (size_t)p.lds[k], p.stride, Fscr, Cscr, Xscr, ctx->stream);
+    return e;
+}
+
 int pcx_consensus_ragged_wide_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_result* out) {
     if (!ctx || !in || !out) return fail(PCX_EINVAL, "pcx_consensus_ragged_wide_f64: null argument");
     const char* env = getenv("PCX_RAGGED_ONE_CLASS");  // diagnostic: every workgroup round in one launch
@@ -674,79 +777,24 @@ int pcx_consensus_ragged_wide_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_
                                         cnt, lds, nullptr))
         return rc;
     if (in->n_rounds == 0) return PCX_OK;
-    const int64_t B = in->n_rounds, nw = cnt[0], nm = B - nw;
-    if (nm == 0) return pcx_consensus_ragged_f64(ctx, in, out);  // wave-sized rounds only: that call as it is
+    if (cnt[0] == in->n_rounds)  // wave-sized rounds only: that call as it is
+        return pcx_consensus_ragged_f64(ctx, in, out);
     // (max_components is capped at E_b per round on the device)
     const bool bad_five = in->algorithm == PCX_ALG_BIG_FIVE && in->max_components < 1;
     if (const int rc = check_options("ragged", in, bad_five ? "big-five needs max_components >= 1" : nullptr))
         return rc;
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    // One staging slot, one upload: the wave rounds' descriptors, the workgroup rounds' descriptors
-    // class after class (3, 2, 1; a class's rounds in their order), the wave rounds' indices.  The
-    // device side holds, past what is uploaded, the wave rounds' six [B] outputs until their scatter.
-    const size_t off_m = (size_t)nw * sizeof(pcx::RaggedDesc), off_i = off_m + (size_t)nm * sizeof(pcx::MediumDesc),
-                 bytes = (off_i + (size_t)nw * sizeof(int32_t) + 7) / 8 * 8, off_t = bytes;
-    pcx_ctx::RaggedSlot* sp = nullptr;
-    if (const int rc = ragged_slot_take(ctx, off_t + (size_t)nw * 32, &sp)) return rc;
-    pcx_ctx::RaggedSlot& s = *sp;
-    char* pin = static_cast<char*>(s.pin);
-    char* dev = static_cast<char*>(s.dev);
-    pcx::RaggedDesc* dw = reinterpret_cast<pcx::RaggedDesc*>(pin);
-    pcx::MediumDesc* dm = reinterpret_cast<pcx::MediumDesc*>(pin + off_m);
-    int32_t* idx = reinterpret_cast<int32_t*>(pin + off_i);
-    int64_t at[4] = {0, 0, 0, 0};  // next entry of each class in dm: class 3 first
-    at[2] = cnt[3];
-    at[1] = cnt[3] + cnt[2];
-    const int64_t first[4] = {0, at[1], at[2], at[3]};
-    int64_t cell = 0, row = 0, ev = 0, w = 0, stride[3] = {0, 0, 0};
-    for (int64_t b = 0; b < B; b++) {
-        const int32_t N = in->n_reporters[b], E = in->n_events[b];
-        const int k = wide_slot(N, E, in->algorithm, one_class);
-        if (k == 0) {
-            dw[w] = pcx::RaggedDesc{cell, row, ev, N, E};
-            idx[w++] = (int32_t)b;
-        } else {
-            dm[at[k]++] = pcx::MediumDesc{cell, row, ev, N, E, (int32_t)b, 0};
-            pcx::medium_slot_strides(N, E, in->algorithm, stride);
-        }
-        cell += (int64_t)N * E;
-        row += N;
-        ev += E;
-    }
-    // the workgroup scratch: slot strides of the call's largest round, chunks that fit the cap
-    const size_t cap = ctx->test_scratch_cap > 0 ? (size_t)ctx->test_scratch_cap : MEDIUM_SCRATCH_CAP;
-    const size_t per = (size_t)((out->filled ? 0 : stride[0]) + stride[1] + stride[2]) * sizeof(double);
-    const int64_t chunk = std::min<int64_t>(std::max<int64_t>((int64_t)(cap / per), 1), nm);
-    if (const int rc = medium_scratch_reserve(ctx, per * (size_t)chunk)) return rc;
-    double* Fscr = (double*)ctx->mscr;
-    double* Cscr = Fscr + (out->filled ? 0 : (size_t)chunk * stride[0]);
-    double* Xscr = Cscr + (size_t)chunk * stride[1];
-    e = ragged_slot_upload(ctx, s, bytes);
+    WidePlan p;
+    if (const int rc = wide_tables(ctx, in->n_rounds, in->n_reporters, in->n_events, in->algorithm, one_class, cnt,
+                                   lds, out->filled != nullptr, 0, &p))
+        return rc;
+    e = ragged_slot_upload(ctx, *p.slot, p.bytes);
     if (e != hipSuccess) return hip_fail(e, "ragged: descriptor upload");
     pcx::BatchArgs a = shared_args(in, out);
-    a.B = B;
-    if (nw > 0) {
-        pcx::BatchArgs aw = a;
-        aw.B = nw;
-        const pcx::WaveTmp t = pcx::ragged_wave_tmp(dev + off_t, nw);
-        aw.participation = t.participation;
-        aw.avg_certainty = t.avg_certainty;
-        aw.branch = t.branch;
-        aw.flags = t.flags;
-        aw.pi_iters = t.pi_iters;
-        aw.components = t.components;
-        e = pcx::launch_ragged(aw, reinterpret_cast<const pcx::RaggedDesc*>(dev), (size_t)lds[0], ctx->stream);
-        if (e == hipSuccess)
-            e = pcx::launch_ragged_scatter(a, reinterpret_cast<const int32_t*>(dev + off_i), nw, dev + off_t,
-                                           ctx->stream);
-    }
-    const pcx::MediumDesc* ddm = reinterpret_cast<const pcx::MediumDesc*>(dev + off_m);
-    for (int k = 3; k >= 1 && e == hipSuccess; k--)
-        for (int64_t b0 = 0; b0 < cnt[k] && e == hipSuccess; b0 += chunk)
-            e = pcx::launch_ragged_medium(a, ddm + first[k] + b0, std::min<int64_t>(chunk, cnt[k] - b0), (size_t)lds[k],
-                                          stride, Fscr, Cscr, Xscr, ctx->stream);
-    if (e == hipSuccess) e = hipEventRecord(s.kern_ev, ctx->stream);
+    a.B = in->n_rounds;
+    e = wide_launch(ctx, p, a);
+    if (e == hipSuccess) e = hipEventRecord(p.slot->kern_ev, ctx->stream);
     return e == hipSuccess ? PCX_OK : hip_fail(e, "ragged wide launch");
 }
 
@@ -1141,6 +1189,294 @@ int pcx_simulate_f64(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* res) {
     if (res->reputation && bn) {
         e = hipMemcpyAsync(res->reputation, rep, bn * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "pcx_simulate_f64: reputation copy");
+    }
+    return PCX_OK;
+}
+
+// ---------------------------------------------------------------- simulator sweeps
+namespace {
+int sweep_fail(int64_t* bad_cell, int64_t c, const char* who, const std::string& why) {
+    if (bad_cell) *bad_cell = c;
+    return fail(PCX_EINVAL, std::string(who) + ": " + (c >= 0 ? "cell " + std::to_string(c) + ": " : "") + why);
+}
+
+// The checks every sweep entry shares (pure): the shared parameters as sim_check checks them
+// (*bad_cell = -1), then cell after cell.  Fills what pcx_sim_sweep_plan reports; 0 = ok.
+int sweep_check(const pcx_sim_sweep* s, const char* who, int64_t totals[4], int64_t counts[4], int64_t lds_bytes[4],
+                int64_t* bad_cell) {
+    if (bad_cell) *bad_cell = -1;
+    if (s->n_cells < 0) return sweep_fail(bad_cell, -1, who, "n_cells must be >= 0");
+    if (s->n_cells > 0 && !s->cells) return sweep_fail(bad_cell, -1, who, "cells is NULL");
+    if (s->n_timesteps < 1 || s->n_timesteps >= (1 << 24))
+        return sweep_fail(bad_cell, -1, who, "n_timesteps must be in [1, 2^24)");
+    if (!(s->scaled_tol >= 0.0) || !std::isfinite(s->scaled_tol))
+        return sweep_fail(bad_cell, -1, who, "scaled_tol must be finite and >= 0");
+    if (s->algorithm < PCX_ALG_PCA || s->algorithm > PCX_ALG_CLUSTERFECK)
+        return sweep_fail(bad_cell, -1, who, "algorithm must be an enum pcx_algorithm value (0..7)");
+    if (s->algorithm == PCX_ALG_KMEANS)
+        return sweep_fail(bad_cell, -1, who, "k-means is not simulated (its code books are drawn on the host)");
+    if (s->algorithm == PCX_ALG_COKURTOSIS)
+        return sweep_fail(bad_cell, -1, who, "cokurtosis is not simulated (it needs the caller's scores)");
+    if (s->algorithm == PCX_ALG_HIERARCHICAL && std::isnan(s->hierarchy_threshold))
+        return sweep_fail(bad_cell, -1, who, "hierarchy_threshold is NaN");
+    // (max_components is capped at E_c per round on the device)
+    if (s->algorithm == PCX_ALG_BIG_FIVE && s->max_components < 1)
+        return sweep_fail(bad_cell, -1, who, "big-five needs max_components >= 1");
+    if (s->algorithm == PCX_ALG_FIXED_VARIANCE && !std::isfinite(s->variance_threshold))
+        return sweep_fail(bad_cell, -1, who, "variance_threshold must be finite");
+    if (!std::isfinite(s->catch_tolerance) || !std::isfinite(s->alpha))
+        return sweep_fail(bad_cell, -1, who, "catch_tolerance/alpha must be finite");
+    int64_t tot[4] = {0, 0, 0, 0}, cnt[4] = {0, 0, 0, 0};
+    size_t lds[4] = {0, 0, 0, 0};
+    for (int64_t c = 0; c < s->n_cells; c++) {
+        const pcx_sim_cell& k = s->cells[c];
+        if (k.n_reporters < 1 || k.n_reporters > 256 || k.n_events < 1 || k.n_events > 64)
+            return sweep_fail(bad_cell, c, who,
+                              "is " + std::to_string(k.n_reporters) + " x " + std::to_string(k.n_events) +
+                                  "; a cell's rounds must be within [1, 256] x [1, 64]");
+        if (k.n_rounds < 1 || k.n_rounds > 0x7fffffff)
+            return sweep_fail(bad_cell, c, who, "n_rounds must be in [1, 2^31)");
+        const struct {
+            const char* name;
+            double p;
+        } probs[] = {{"liar_frac", k.liar_frac}, {"collude_frac", k.collude_frac}, {"distort", k.distort},
+                     {"na_frac", k.na_frac},     {"scaled_frac", k.scaled_frac}};
+        for (const auto& q : probs)
+            if (!(q.p >= 0.0 && q.p <= 1.0))  // false for NaN too
+                return sweep_fail(bad_cell, c, who, std::string(q.name) + " must be a probability in [0, 1]");
+        const int64_t R = k.n_rounds, N = k.n_reporters, E = k.n_events;
+        tot[0] += R;
+        if (tot[0] > 0x7fffffff)
+            return sweep_fail(bad_cell, c, who, "the rounds up to this cell reach 2^31 (sum of n_rounds must be < 2^31)");
+        tot[1] += R * N;
+        tot[2] += R * E;
+        tot[3] += R * N * E;
+        const int slot = wide_slot((int)N, (int)E, s->algorithm, false);
+        cnt[slot] += R;
+        lds[slot] = std::max(lds[slot], slot ? pcx::medium_lds_bytes((int)N, (int)E, s->algorithm)
+                                             : pcx::ragged_lds_bytes((int)N, (int)E, s->algorithm));
+    }
+    for (int k = 0; k < 4 && totals; k++) totals[k] = tot[k];
+    for (int k = 0; k < 4 && counts; k++) counts[k] = cnt[k];
+    for (int k = 0; k < 4 && lds_bytes; k++) lds_bytes[k] = (int64_t)lds[k];
+    return PCX_OK;
+}
+
+pcx::sim::Gen sweep_gen(const pcx_sim_cell& k) {
+    pcx::sim::Gen g;
+    g.key0 = (uint32_t)k.seed;
+    g.key1 = (uint32_t)(k.seed >> 32);
+    g.thr_liar = sim_threshold(k.liar_frac);
+    g.thr_collude = sim_threshold(k.collude_frac);
+    g.thr_distort = sim_threshold(k.distort);
+    g.thr_na = sim_threshold(k.na_frac);
+    g.thr_scaled = sim_threshold(k.scaled_frac);
+    return g;
+}
+
+// bytes of a checked sweep's tables: the cell table, then the round prefix sums [C + 1]
+size_t sweep_table_bytes(const pcx_sim_sweep* s) {
+    return (size_t)s->n_cells * sizeof(pcx::SweepCell) + (size_t)(s->n_cells + 1) * sizeof(int64_t);
+}
+
+// the tables of a checked sweep written at `host`; what the kernels get points at `dev`, where
+// the caller uploads them
+pcx::SweepTables sweep_tables_fill(const pcx_sim_sweep* s, void* host, const void* dev) {
+    const int64_t C = s->n_cells;
+    pcx::SweepCell* cells = static_cast<pcx::SweepCell*>(host);
+    int64_t* prefix = reinterpret_cast<int64_t*>(cells + C);
+    int64_t round = 0, cell = 0, row = 0, ev = 0;
+    for (int64_t c = 0; c < C; c++) {
+        const pcx_sim_cell& k = s->cells[c];
+        const int64_t R = k.n_rounds, N = k.n_reporters, E = k.n_events;
+        cells[c] = pcx::SweepCell{round, cell, row, ev, R, (int32_t)N, (int32_t)E, sweep_gen(k)};
+        prefix[c] = round;
+        round += R;
+        cell += R * N * E;
+        row += R * N;
+        ev += R * E;
+    }
+    prefix[C] = round;
+    pcx::SweepTables t;
+    t.cells = static_cast<const pcx::SweepCell*>(dev);
+    t.prefix = reinterpret_cast<const int64_t*>(t.cells + C);
+    t.C = (int32_t)C;
+    t.B = round;
+    return t;
+}
+}  // namespace
+
+// a checked sweep's tables through a staging slot of their own to the device, on the stream (the
+// stand-alone generator and metrics entries); the caller records the slot's kern_ev after its launches
+static int sweep_tables_upload(pcx_ctx* ctx, const pcx_sim_sweep* s, pcx_ctx::RaggedSlot** slot, pcx::SweepTables* t) {
+    const size_t bytes = sweep_table_bytes(s);
+    if (const int rc = ragged_slot_take(ctx, bytes, slot)) return rc;
+    *t = sweep_tables_fill(s, (*slot)->pin, (*slot)->dev);
+    const hipError_t e = ragged_slot_upload(ctx, **slot, bytes);
+    return e == hipSuccess ? PCX_OK : hip_fail(e, "sweep: table upload");
+}
+
+int pcx_sim_sweep_plan(const pcx_sim_sweep* sweep, int64_t totals[4], int64_t counts[4], int64_t lds_bytes[4],
+                       int64_t* bad_cell) {
+    if (!sweep) return fail(PCX_EINVAL, "pcx_sim_sweep_plan: null argument");
+    return sweep_check(sweep, "pcx_sim_sweep_plan", totals, counts, lds_bytes, bad_cell);
+}
+
+int pcx_sim_sweep_generate_host(const pcx_sim_sweep* sweep, int timestep, pcx_sim_rounds* rounds) {
+    if (!sweep || !rounds) return fail(PCX_EINVAL, "pcx_sim_sweep_generate_host: null argument");
+    if (const int rc = sweep_check(sweep, "pcx_sim_sweep_generate_host", nullptr, nullptr, nullptr, nullptr)) return rc;
+    if (const int rc = sim_check_timestep(timestep, "pcx_sim_sweep_generate_host")) return rc;
+    std::vector<char> tab(sweep_table_bytes(sweep));
+    sweep_tables_fill(sweep, tab.data(), tab.data());
+    pcx::sim_sweep_generate_host(reinterpret_cast<const pcx::SweepCell*>(tab.data()), sweep->n_cells,
+                                 (uint32_t)timestep, *rounds);
+    return PCX_OK;
+}
+
+int pcx_sim_sweep_generate_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, int timestep, pcx_sim_rounds* rounds) {
+    if (!ctx || !sweep || !rounds) return fail(PCX_EINVAL, "pcx_sim_sweep_generate_f64: null argument");
+    if (const int rc = sweep_check(sweep, "pcx_sim_sweep_generate_f64", nullptr, nullptr, nullptr, nullptr)) return rc;
+    if (const int rc = sim_check_timestep(timestep, "pcx_sim_sweep_generate_f64")) return rc;
+    if (sweep->n_cells == 0) return PCX_OK;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    pcx_ctx::RaggedSlot* slot = nullptr;
+    pcx::SweepTables tab;
+    if (const int rc = sweep_tables_upload(ctx, sweep, &slot, &tab)) return rc;
+    e = pcx::launch_sim_sweep_generate(tab, (uint32_t)timestep, *rounds, ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(slot->kern_ev, ctx->stream);
+    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_sim_sweep_generate launch");
+}
+
+int pcx_sim_sweep_metrics_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const pcx_sim_rounds* rounds,
+                              const double* old_rep, const double* smooth_rep, const double* outcomes_final,
+                              double* metrics, double* summary) {
+    if (!ctx || !sweep || !rounds) return fail(PCX_EINVAL, "pcx_sim_sweep_metrics_f64: null argument");
+    if (const int rc = sweep_check(sweep, "pcx_sim_sweep_metrics_f64", nullptr, nullptr, nullptr, nullptr)) return rc;
+    if (sweep->n_cells == 0) return PCX_OK;
+    if (!old_rep || !smooth_rep || !outcomes_final || !metrics)
+        return fail(PCX_EINVAL, "pcx_sim_sweep_metrics_f64: null argument");
+    if (!rounds->scaled || !rounds->lo || !rounds->hi || !rounds->truth || !rounds->liar)
+        return fail(PCX_EINVAL, "pcx_sim_sweep_metrics_f64: rounds needs scaled, lo, hi, truth and liar");
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    pcx_ctx::RaggedSlot* slot = nullptr;
+    pcx::SweepTables tab;
+    if (const int rc = sweep_tables_upload(ctx, sweep, &slot, &tab)) return rc;
+    e = pcx::launch_sim_sweep_metrics(tab, sweep->scaled_tol, *rounds, old_rep, smooth_rep, outcomes_final, metrics,
+                                      ctx->stream);
+    if (e == hipSuccess && summary) e = pcx::launch_sim_sweep_summary(tab, metrics, summary, ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(slot->kern_ev, ctx->stream);
+    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_sim_sweep_metrics / k_sim_sweep_summary launch");
+}
+
+int pcx_simulate_sweep_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* res) {
+    if (!ctx || !sweep || !res) return fail(PCX_EINVAL, "pcx_simulate_sweep_f64: null argument");
+    int64_t tot[4], cnt[4], lds[4];
+    if (const int rc = sweep_check(sweep, "pcx_simulate_sweep_f64", tot, cnt, lds, nullptr)) return rc;
+    const int64_t C = sweep->n_cells, B = tot[0], T = sweep->n_timesteps;
+    if (C == 0) return PCX_OK;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    // the cells expanded into the wide ragged call's per-round shapes
+    std::vector<int32_t> shape;
+    try {
+        shape.resize((size_t)B * 2);
+    } catch (const std::bad_alloc&) {
+        return fail(PCX_ENOMEM, "pcx_simulate_sweep_f64: no host memory for the per-round shapes");
+    }
+    int32_t* nrep = shape.data();
+    int32_t* nev = nrep + B;
+    for (int64_t c = 0, b = 0; c < C; c++)
+        for (int64_t r = 0; r < sweep->cells[c].n_rounds; r++, b++) {
+            nrep[b] = sweep->cells[c].n_reporters;
+            nev[b] = sweep->cells[c].n_events;
+        }
+    // work buffers, pcx_simulate_f64's layout over the flat arrays
+    const size_t bn = (size_t)tot[1], be = (size_t)tot[2], bne = (size_t)tot[3];
+    const size_t n_f64 = bne + 4 * be + 3 * bn + (size_t)B * PCX_SIM_NMETRICS;
+    if (const int rc = sim_reserve(ctx, std::max<size_t>(n_f64 * sizeof(double) + be + bn, 16))) return rc;
+    double* p = (double*)ctx->sim_buf;
+    auto take = [&p](size_t n) {
+        double* q = p;
+        p += n;
+        return q;
+    };
+    pcx_sim_rounds work;
+    work.reports = take(bne);
+    work.lo = take(be);
+    work.hi = take(be);
+    work.truth = take(be);
+    double* w_outcomes = take(be);
+    double* w_old = take(bn);
+    double* w_smooth[2] = {take(bn), take(bn)};
+    double* w_metrics = take((size_t)B * PCX_SIM_NMETRICS);
+    work.scaled = (uint8_t*)p;
+    work.liar = work.scaled + be;
+    // every table of the call in one staging slot, uploaded once: the wide ragged call's descriptors
+    // (the same every timestep: only the data pointers change), then the sweep's own
+    WidePlan plan;
+    if (const int rc = wide_tables(ctx, B, nrep, nev, sweep->algorithm, false, cnt, lds, false,
+                                   sweep_table_bytes(sweep), &plan))
+        return rc;
+    const pcx::SweepTables tab = sweep_tables_fill(sweep, static_cast<char*>(plan.slot->pin) + plan.off_x,
+                                                   static_cast<char*>(plan.slot->dev) + plan.off_x);
+    e = ragged_slot_upload(ctx, *plan.slot, plan.bytes);
+    if (e != hipSuccess) return hip_fail(e, "sweep: table upload");
+    const double* rep = sweep->reputation0;
+    for (int64_t t = 0; t < T; t++) {  // launches only: no host wait in this loop
+        const bool last = t == T - 1;
+        pcx_sim_rounds r = work;
+        pcx_batch_result o{};
+        if (last) {  // the caller's buffers where given
+            const pcx_sim_rounds& u = res->last;
+            if (u.reports) r.reports = u.reports;
+            if (u.scaled) r.scaled = u.scaled;
+            if (u.lo) r.lo = u.lo;
+            if (u.hi) r.hi = u.hi;
+            if (u.truth) r.truth = u.truth;
+            if (u.liar) r.liar = u.liar;
+            o = res->last_out;
+        }
+        if (!o.old_rep) o.old_rep = w_old;
+        if (!o.smooth_rep) o.smooth_rep = w_smooth[t & 1];
+        if (!o.outcomes_final) o.outcomes_final = w_outcomes;
+        e = pcx::launch_sim_sweep_generate(tab, (uint32_t)t, r, ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "k_sim_sweep_generate launch");
+        pcx_ragged in{};
+        in.n_rounds = B;
+        in.reports = r.reports;
+        in.reputation = rep;
+        in.scaled = r.scaled;
+        in.lo = r.lo;
+        in.hi = r.hi;
+        in.catch_tolerance = sweep->catch_tolerance;
+        in.alpha = sweep->alpha;
+        in.algorithm = sweep->algorithm;
+        in.max_components = sweep->max_components;
+        in.variance_threshold = sweep->variance_threshold;
+        in.hierarchy_threshold = sweep->hierarchy_threshold;
+        in.cluster_threshold = sweep->cluster_threshold;
+        pcx::BatchArgs a = shared_args(&in, &o);
+        a.B = B;
+        e = wide_launch(ctx, plan, a);
+        if (e != hipSuccess) return hip_fail(e, "sweep: ragged wide launch");
+        if (res->metrics || res->summary) {
+            double* m = res->metrics ? res->metrics + (size_t)t * B * PCX_SIM_NMETRICS : w_metrics;
+            e = pcx::launch_sim_sweep_metrics(tab, sweep->scaled_tol, r, o.old_rep, o.smooth_rep, o.outcomes_final, m,
+                                              ctx->stream);
+            if (e == hipSuccess && res->summary)
+                e = pcx::launch_sim_sweep_summary(tab, m, res->summary + (size_t)t * C * PCX_SIM_NMETRICS,
+                                                  ctx->stream);
+            if (e != hipSuccess) return hip_fail(e, "k_sim_sweep_metrics / k_sim_sweep_summary launch");
+        }
+        rep = o.smooth_rep;  // the next timestep's reputation
+    }
+    e = hipEventRecord(plan.slot->kern_ev, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "sweep: hipEventRecord");
+    if (res->reputation && bn) {
+        e = hipMemcpyAsync(res->reputation, rep, bn * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "pcx_simulate_sweep_f64: reputation copy");
     }
     return PCX_OK;
 }

@@ -10,6 +10,11 @@ timestep's reputation.
     python -m pyconsensus_amd.simulate --rounds 65536 --timesteps 8 --seed 1
 
 prints the per-timestep means of the metrics as JSON.
+
+A study is a curve or a grid, not a point: :func:`sweep` runs cells of different shapes, rates and
+seeds in one call (``pcx_simulate_sweep_f64``), each cell byte for byte its own
+:func:`simulate`, and :func:`grid` builds the cell list of a cartesian product.  On the command
+line a comma list for a shape or a rate (``--liars 0.1,0.2,0.3 --reporters 20,50``) runs the grid.
 """
 from __future__ import annotations
 
@@ -163,24 +168,260 @@ def simulate(B, N=50, E=20, T=1, seed=0, liar_frac=0.3, collude_frac=0.5, distor
     return out
 
 
+# ---------------------------------------------------------------- sweeps
+CELL_FIELDS = ("rounds", "reporters", "events", "seed", "liar_frac", "collude_frac", "distort", "na_frac",
+               "scaled_frac")
+_CELL_DEFAULTS = {"reporters": 50, "events": 20, "seed": 0, "liar_frac": 0.3, "collude_frac": 0.5, "distort": 0.1,
+                  "na_frac": 0.1, "scaled_frac": 0.25}  # simulate()'s
+_OFFSETS = ("rounds", "reporters", "events", "cells")
+
+
+def _cells(cells):
+    """The cells as a list of full dicts, the pcx_sim_cell array and the per-cell starts."""
+    norm = []
+    for c, cell in enumerate(cells):
+        if not isinstance(cell, dict):
+            cell = tuple(cell)
+            if not 1 <= len(cell) <= len(CELL_FIELDS):
+                raise ValueError("cell %d: a tuple cell is (%s), from the left" % (c, ", ".join(CELL_FIELDS)))
+            cell = dict(zip(CELL_FIELDS, cell))
+        unknown = set(cell) - set(CELL_FIELDS)
+        if unknown:
+            raise ValueError("cell %d: unknown field(s) %s" % (c, sorted(unknown)))
+        if "rounds" not in cell:
+            raise ValueError("cell %d: needs 'rounds'" % c)
+        norm.append(dict(_CELL_DEFAULTS, **cell))
+    arr = (_abi.SimCell * max(len(norm), 1))()
+    for k, d in zip(arr, norm):
+        k.n_rounds, k.n_reporters, k.n_events = int(d["rounds"]), int(d["reporters"]), int(d["events"])
+        k.seed = int(d["seed"]) & 0xFFFFFFFFFFFFFFFF
+        for f in ("liar_frac", "collude_frac", "distort", "na_frac", "scaled_frac"):
+            setattr(k, f, float(d[f]))
+    R = np.array([int(d["rounds"]) for d in norm], dtype=np.int64)
+    N = np.array([int(d["reporters"]) for d in norm], dtype=np.int64)
+    E = np.array([int(d["events"]) for d in norm], dtype=np.int64)
+    zero = np.zeros(1, dtype=np.int64)
+    offsets = {"rounds": np.concatenate([zero, np.cumsum(R)]), "reporters": np.concatenate([zero, np.cumsum(R * N)]),
+               "events": np.concatenate([zero, np.cumsum(R * E)]), "cells": np.concatenate([zero, np.cumsum(R * N * E)])}
+    return norm, arr, offsets
+
+
+def _sweep(cells, T=1, scaled_tol=0.1, algorithm="PCA", catch_tolerance=0.1, alpha=0.1, max_components=5,
+           variance_threshold=0.9, hierarchy_threshold=0.5, cluster_threshold=None, reputation0=None):
+    alg = _abi.ALGORITHMS.get(algorithm)
+    if alg is None:
+        raise NotImplementedError("algorithm %r is not on the GPU path" % (algorithm,))
+    norm, arr, offsets = _cells(cells)
+    # (max_components is capped at E_c on the device; cluster_threshold None = the device's per-round rule)
+    s = _abi.SimSweep(len(norm), C.addressof(arr), int(T), float(scaled_tol), float(catch_tolerance), float(alpha),
+                      alg, int(max_components), float(variance_threshold), float(hierarchy_threshold),
+                      0.0 if cluster_threshold is None else float(cluster_threshold), reputation0)
+    return s, arr, norm, offsets
+
+
+def sweep_plan(cells, T=1, algorithm="PCA", **params):
+    """Validate a sweep without a device (``pcx_sim_sweep_plan``): ``(totals, counts, lds_bytes)`` as int64
+    arrays of four: totals = (B, sum R N, sum R E, sum R N E); counts / lds_bytes are
+    ``ragged_plan(wide=True)``'s for the sweep's rounds.  Raises with the cell's index on refusal."""
+    s, arr, _, _ = _sweep(cells, T, algorithm=algorithm, **params)
+    out = [(C.c_int64 * 4)() for _ in range(3)]
+    bad = C.c_int64(-2)
+    _lib.check(_lib.lib().pcx_sim_sweep_plan(C.byref(s), out[0], out[1], out[2], C.byref(bad)))
+    return tuple(np.array(list(x), dtype=np.int64) for x in out)
+
+
+def _flat_len(kind, offsets):
+    return int({"N": offsets["reporters"], "E": offsets["events"], "NE": offsets["cells"]}[kind][-1])
+
+
+def sweep_generate_host(cells, t=0):
+    """The rounds of timestep ``t`` of every cell drawn on the CPU (``pcx_sim_sweep_generate_host``):
+    flat numpy arrays named as :func:`generate_host`'s, the cells' rounds end to end, and ``offsets``,
+    a dict of int64 [C + 1] starts per cell: ``rounds``, ``reporters`` (``liar``), ``events``
+    (``scaled``, ``lo``, ``hi``, ``truth``) and ``cells`` (``reports``)."""
+    s, arr, _, offsets = _sweep(cells, max(1, int(t) + 1))
+    rounds, c = {}, _abi.SimRounds()
+    for name, kind, dt in _abi.SIM_ROUNDS:
+        a = np.empty(_flat_len(kind, offsets), dtype=_NP[dt])
+        rounds[name] = a
+        setattr(c, name, a.ctypes.data)
+    _lib.check(_lib.lib().pcx_sim_sweep_generate_host(C.byref(s), int(t), C.byref(c)))
+    rounds["offsets"] = offsets
+    return rounds
+
+
+def _device_flat_rounds(t, dev, offsets, fields=None):
+    rounds, c = {}, _abi.SimRounds()
+    for name, kind, dt in _abi.SIM_ROUNDS:
+        if fields is not None and name not in fields:
+            continue
+        x = t.empty(_flat_len(kind, offsets), dtype=_torch_dtype(t, dt), device=dev)
+        rounds[name] = x
+        setattr(c, name, x.data_ptr())
+    return rounds, c
+
+
+def sweep_generate(cells, t=0, fields=None, device=None):
+    """:func:`sweep_generate_host` on the device: flat torch tensors (``fields``: only these arrays,
+    the others are not written).  Asynchronous on torch's current stream."""
+    tc = _device.require_gpu()
+    dev = tc.device(device) if device is not None else tc.device("cuda", tc.cuda.current_device())
+    s, arr, _, offsets = _sweep(cells, max(1, int(t) + 1))
+    rounds, c = _device_flat_rounds(tc, dev, offsets, fields)
+    h = _lib.bind_stream(dev.index, _device.current_stream_handle(dev))
+    _lib.check(_lib.lib().pcx_sim_sweep_generate_f64(h, C.byref(s), int(t), C.byref(c)))
+    rounds["offsets"] = offsets
+    return rounds
+
+
+def sweep_metrics(cells, rounds, old_rep, smooth_rep, outcomes_final, scaled_tol=0.1, summary=True, device=None):
+    """Score a sweep's flat rounds (``pcx_sim_sweep_metrics_f64``): ``metrics (B,6)`` and, unless
+    ``summary`` is false, ``summary (C,6)``, every cell's means over its rounds."""
+    tc = _device.require_gpu()
+    dev = tc.device(device) if device is not None else tc.device("cuda", tc.cuda.current_device())
+    s, arr, norm, offsets = _sweep(cells, 1, scaled_tol=scaled_tol)
+    c, keep = _abi.SimRounds(), []
+    for name, kind, dt in _abi.SIM_ROUNDS:
+        if name != "reports":
+            x = _device.as_device(rounds[name], _torch_dtype(tc, dt), dev)
+            if tuple(x.shape) != (_flat_len(kind, offsets),):
+                raise ValueError("rounds[%r] must be flat, %d long" % (name, _flat_len(kind, offsets)))
+            keep.append(x)
+            setattr(c, name, x.data_ptr())
+    old, smooth, outc = (_device.as_device(x, tc.float64, dev) for x in (old_rep, smooth_rep, outcomes_final))
+    tn, te = _flat_len("N", offsets), _flat_len("E", offsets)
+    if tuple(old.shape) != (tn,) or tuple(smooth.shape) != (tn,) or tuple(outc.shape) != (te,):
+        raise ValueError("old_rep / smooth_rep must be flat [sum R N] and outcomes_final flat [sum R E]")
+    B = int(offsets["rounds"][-1])
+    m = tc.empty((B, _abi.SIM_NMETRICS), dtype=tc.float64, device=dev)
+    sm = tc.empty((len(norm), _abi.SIM_NMETRICS), dtype=tc.float64, device=dev) if summary else None
+    h = _lib.bind_stream(dev.index, _device.current_stream_handle(dev))
+    _lib.check(_lib.lib().pcx_sim_sweep_metrics_f64(h, C.byref(s), C.byref(c), old.data_ptr(), smooth.data_ptr(),
+                                                    outc.data_ptr(), m.data_ptr(), _device.ptr(sm)))
+    return {"metrics": m, "summary": sm, "offsets": offsets, "_inputs": (keep, old, smooth, outc)}
+
+
+def sweep(cells, T=1, scaled_tol=0.1, algorithm="PCA", catch_tolerance=0.1, alpha=0.1, max_components=5,
+          variance_threshold=0.9, hierarchy_threshold=0.5, cluster_threshold=None, reputation=None,
+          keep_rounds=False, keep_outputs=False, device=None):
+    """T timesteps of a whole study in one call: C cells, each with its own rounds, shape, rates and seed.
+
+    ``cells`` is a list of dicts (or tuples, from the left) with ``rounds``, ``reporters``, ``events``,
+    ``seed``, ``liar_frac``, ``collude_frac``, ``distort``, ``na_frac``, ``scaled_frac``; what a dict
+    leaves out is :func:`simulate`'s default.  Shapes go up to 256 x 64.  The timesteps, ``scaled_tol``
+    and the consensus parameters are shared.  The rounds of all cells lie end to end in cell order
+    in :func:`consensus_ragged`'s flat layout and run as one wide ragged batch per timestep.
+
+    Cell c's slice of every output is byte for byte ``simulate(R_c, N_c, E_c, T, seed_c, ...)``: the
+    generator counts a round inside its cell and takes the cell's seed as its key.  So cells that
+    share a seed see COMMON RANDOM NUMBERS (the same reporters lie, the same events are scaled,
+    wherever the rates allow it): the usual variance reduction for a parameter curve.  Cells with
+    different seeds are independent.  ("big-five" caps ``max_components`` at E_c per cell;
+    "clusterfeck" without a ``cluster_threshold`` takes the device's log10(E_c)/1.77 per cell.)
+
+    Returns device tensors ``metrics (T,B,6)`` with B = sum R_c, ``summary (T,C,6)`` (each cell's
+    means in :func:`simulate`'s order), the flat ``reputation`` [sum R_c N_c], and ``offsets``, numpy
+    int64 [C + 1] starts per cell (``rounds``, ``reporters``, ``events``, ``cells``) to slice with.
+    ``reputation`` in: a flat starting reputation or None (uniform).  ``keep_rounds`` /
+    ``keep_outputs`` add the last timestep's flat ``rounds`` / consensus ``outputs``.
+
+    Asynchronous on torch's current stream, with no host wait between the timesteps.  A sweep runs
+    the generic ragged kernels: a study of ONE shape belongs on :func:`simulate`, whose compiled
+    equal-shape kernel is faster."""
+    tc = _device.require_gpu()
+    dev = tc.device(device) if device is not None else tc.device("cuda", tc.cuda.current_device())
+    rep = _device.as_device(reputation, tc.float64, dev)
+    s, arr, norm, offsets = _sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_components,
+                                   variance_threshold, hierarchy_threshold, cluster_threshold, _device.ptr(rep))
+    sweep_plan(cells, T, algorithm=algorithm, scaled_tol=scaled_tol, catch_tolerance=catch_tolerance, alpha=alpha,
+               max_components=max_components, variance_threshold=variance_threshold,
+               hierarchy_threshold=hierarchy_threshold, cluster_threshold=cluster_threshold)  # refuses by cell
+    T, Cn, B, tn = int(T), len(norm), int(offsets["rounds"][-1]), _flat_len("N", offsets)
+    if rep is not None and tuple(rep.shape) != (tn,):
+        raise ValueError("reputation must be flat, sum R_c N_c = %d long" % tn)
+    out = {"metrics": tc.empty((T, B, _abi.SIM_NMETRICS), dtype=tc.float64, device=dev),
+           "summary": tc.empty((T, Cn, _abi.SIM_NMETRICS), dtype=tc.float64, device=dev),
+           "reputation": tc.empty((tn,), dtype=tc.float64, device=dev), "offsets": offsets}
+    res = _abi.SimResult()
+    res.metrics, res.summary, res.reputation = (out[k].data_ptr() for k in ("metrics", "summary", "reputation"))
+    if keep_rounds:
+        out["rounds"], res.last = _device_flat_rounds(tc, dev, offsets)
+    if keep_outputs:
+        outs = {}
+        totals = tuple(_flat_len(k, offsets) for k in ("N", "E", "NE"))
+        for name, kind, dt in _abi.BATCH_OUTPUTS:
+            if name in ("original", "filled"):
+                continue
+            outs[name] = tc.empty(_abi.ragged_out_len(kind, B, totals), dtype=_torch_dtype(tc, dt), device=dev)
+            setattr(res.last_out, name, outs[name].data_ptr())
+        out["outputs"] = outs
+    h = _lib.bind_stream(dev.index, _device.current_stream_handle(dev))
+    _lib.check(_lib.lib().pcx_simulate_sweep_f64(h, C.byref(s), C.byref(res)))
+    out["_inputs"] = (rep,)  # alive until the caller syncs
+    return out
+
+
+_GRID_AXES = ("reporters", "events", "liar_frac", "collude_frac", "distort", "na_frac", "scaled_frac")
+
+
+def grid(rounds, seed=0, independent=False, **axes):
+    """The cell list of a cartesian product: every axis (``reporters``, ``events``, ``liar_frac``,
+    ``collude_frac``, ``distort``, ``na_frac``, ``scaled_frac``) a value or a sequence of values, the
+    first axis given varying slowest; ``rounds`` per cell.  All cells share ``seed`` (common random
+    numbers along every axis) unless ``independent``: then cell k has ``seed + k``."""
+    import itertools
+
+    unknown = set(axes) - set(_GRID_AXES)
+    if unknown:
+        raise ValueError("grid: unknown axis %s (axes: %s)" % (sorted(unknown), ", ".join(_GRID_AXES)))
+    names = list(axes)
+    values = [list(v) if isinstance(v, (list, tuple, np.ndarray, range)) else [v] for v in axes.values()]
+    cells = []
+    for k, combo in enumerate(itertools.product(*values)):
+        cell = {"rounds": int(rounds), "seed": int(seed) + (k if independent else 0)}
+        cell.update(zip(names, (v.item() if isinstance(v, np.generic) else v for v in combo)))
+        cells.append(cell)
+    return cells
+
+
+def _comma_list(kind):
+    def parse(text):
+        return [kind(x) for x in text.split(",")]
+    return parse
+
+
 def main(argv=None):
     import argparse
     import json
 
     ap = argparse.ArgumentParser(prog="python -m pyconsensus_amd.simulate", description=__doc__.split("\n\n")[0])
     ap.add_argument("--rounds", type=int, default=1024, help="B, rounds per timestep")
-    ap.add_argument("--reporters", type=int, default=50)
-    ap.add_argument("--events", type=int, default=20)
+    ap.add_argument("--reporters", type=_comma_list(int), default=[50], help="N; a comma list runs a grid")
+    ap.add_argument("--events", type=_comma_list(int), default=[20], help="E; a comma list runs a grid")
     ap.add_argument("--timesteps", type=int, default=1)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--liars", type=float, default=0.3, help="liar_frac")
-    ap.add_argument("--collude", type=float, default=0.5, help="collude_frac")
-    ap.add_argument("--distort", type=float, default=0.1)
-    ap.add_argument("--missing", type=float, default=0.1, help="na_frac")
-    ap.add_argument("--scaled", type=float, default=0.25, help="scaled_frac")
+    flt = _comma_list(float)
+    ap.add_argument("--liars", type=flt, default=[0.3], help="liar_frac (or a comma list)")
+    ap.add_argument("--collude", type=flt, default=[0.5], help="collude_frac (or a comma list)")
+    ap.add_argument("--distort", type=flt, default=[0.1], help="(or a comma list)")
+    ap.add_argument("--missing", type=flt, default=[0.1], help="na_frac (or a comma list)")
+    ap.add_argument("--scaled", type=flt, default=[0.25], help="scaled_frac (or a comma list)")
     ap.add_argument("--scaled-tol", type=float, default=0.1)
     ap.add_argument("--algorithm", default="PCA")
     a = ap.parse_args(argv)
+    lists = {"reporters": a.reporters, "events": a.events, "liar_frac": a.liars, "collude_frac": a.collude,
+             "distort": a.distort, "na_frac": a.missing, "scaled_frac": a.scaled}
+    if any(len(v) > 1 for v in lists.values()):  # a grid: --rounds per cell, one shared seed
+        cells = grid(a.rounds, seed=a.seed, **lists)
+        r = sweep(cells, a.timesteps, scaled_tol=a.scaled_tol, algorithm=a.algorithm)
+        summary = r["summary"].cpu().numpy()  # (the copy synchronises)
+        print(json.dumps({"rounds": a.rounds, "seed": a.seed, "algorithm": a.algorithm,
+                          "cells": [dict({k: v for k, v in cell.items() if k not in ("rounds", "seed")},
+                                         summary=[dict(zip(METRICS, (float(v) for v in row)), timestep=t)
+                                                  for t, row in enumerate(summary[:, c])])
+                                    for c, cell in enumerate(cells)]}))
+        return 0
+    a.reporters, a.events, a.liars, a.collude, a.distort, a.missing, a.scaled = (v[0] for v in lists.values())
     r = simulate(a.rounds, a.reporters, a.events, a.timesteps, seed=a.seed, liar_frac=a.liars,
                  collude_frac=a.collude, distort=a.distort, na_frac=a.missing, scaled_frac=a.scaled,
                  scaled_tol=a.scaled_tol, algorithm=a.algorithm)
