@@ -348,6 +348,71 @@ int pcx_sim_sweep_metrics_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const pc
 int pcx_simulate_sweep_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* result);
 
 /* ------------------------------------------------------------------------ */
+/* Simulator studies (added under ABI 9; detect by symbol): a sweep that also   */
+/* writes twelve detail metrics per round every timestep and, after the last    */
+/* timestep, reduces every per-round value to per-cell statistics and to paired */
+/* differences against a base cell (cells that share a seed see common random   */
+/* numbers: the paired difference is where that variance reduction shows).      */
+/* DESIGN.md 5.4.2 is the specification; csrc/pcx_sim_study.h is the one source  */
+/* of the device kernels and of the *_host entries, which agree bit for bit.     */
+/* Every entry above keeps its outputs.                                          */
+/* ------------------------------------------------------------------------ */
+#define PCX_SIM_NDETAIL 12        /* correct_binary, correct_scaled, indeterminate, flipped, nan_outcomes,
+                                     scaled_err, tp, fn, fp, tn, mcc, colluder_rep_after */
+#define PCX_SIM_NVALUES (PCX_SIM_NMETRICS + PCX_SIM_NDETAIL)  /* per round: the metrics, then the detail */
+#define PCX_SIM_NSTATS 5          /* n, mean, var, min, max over a cell's rounds whose value is not NaN */
+#define PCX_SIM_NPAIRED 3         /* n, mean, var of v_cell[b] - v_base[b] where neither is NaN */
+
+typedef struct {
+    double* detail;               /* [T][B][PCX_SIM_NDETAIL], or NULL: kept in the context's workspace */
+    double* stats;                /* [T][C][PCX_SIM_NVALUES][PCX_SIM_NSTATS]    */
+    double* paired;               /* [T][C][PCX_SIM_NVALUES][PCX_SIM_NPAIRED], or NULL */
+} pcx_sim_study_result;
+
+/* Detail metrics of B equal-shape rounds: detail [B][PCX_SIM_NDETAIL].  The arguments are
+ * pcx_sim_metrics_f64's (rounds->scaled, lo, hi, truth and liar are required).  A ratio with a zero
+ * denominator is NaN (no binary event, no scaled event, a zero factor under mcc's root); a reporter
+ * is punished when smooth_rep < old_rep.  Asynchronous. */
+int pcx_sim_detail_f64(pcx_ctx* ctx, const pcx_sim* sim, const pcx_sim_rounds* rounds, const double* old_rep,
+                       const double* smooth_rep, const double* outcomes_final, double* detail);
+/* The same for a sweep's rounds in the flat layout (pcx_sim_sweep_metrics_f64's arguments). */
+int pcx_sim_sweep_detail_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const pcx_sim_rounds* rounds,
+                             const double* old_rep, const double* smooth_rep, const double* outcomes_final,
+                             double* detail);
+/* Both on the CPU: HOST pointers, no context, the same inline code as the kernel. */
+int pcx_sim_detail_host(const pcx_sim* sim, const pcx_sim_rounds* rounds, const double* old_rep,
+                        const double* smooth_rep, const double* outcomes_final, double* detail);
+int pcx_sim_sweep_detail_host(const pcx_sim_sweep* sweep, const pcx_sim_rounds* rounds, const double* old_rep,
+                              const double* smooth_rep, const double* outcomes_final, double* detail);
+/* Pure: what pcx_sim_sweep_plan refuses, then pair_base (HOST int32 [C] or NULL: cell c's base cell,
+ * or -1 for none): a base outside [0, C), a cell that is its own base, or a base with another number
+ * of rounds gives PCX_EINVAL with *bad_cell = that cell (pcx_last_error names it).  The base need
+ * not share the seed (the pairing is then merely uninformative). */
+int pcx_sim_study_check(const pcx_sim_sweep* sweep, const int32_t* pair_base, int64_t* bad_cell);
+/* Per-cell statistics of metrics [T][B][PCX_SIM_NMETRICS] and detail [T][B][PCX_SIM_NDETAIL] (device),
+ * T = sweep->n_timesteps: stats [T][C][PCX_SIM_NVALUES][5] = {n, mean, var, min, max} over the cell's
+ * non-NaN values.  Sums run in pcx_simulate_f64's summary order (256 strided lanes, then a tree), so
+ * with no NaN the mean of a metric is byte for byte the sweep's summary; var is a second pass over
+ * (v - mean)^2, divided by n - 1 (NaN for n < 2; n = 0: mean, min, max NaN).  paired
+ * [T][C][PCX_SIM_NVALUES][3] = {n, mean, var} of v_c[b] - v_base[b], b the round inside its cell, over
+ * the rounds where both are not NaN (base -1: n = 0 and NaN).  paired and pair_base may be NULL
+ * together.  No atomics: the bytes do not depend on the launch geometry.  Asynchronous, one launch. */
+int pcx_sim_sweep_stats_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const double* metrics, const double* detail,
+                            const int32_t* pair_base, double* stats, double* paired);
+/* The same on the CPU (HOST pointers, no context): the lanes and the tree replayed in a loop. */
+int pcx_sim_sweep_stats_host(const pcx_sim_sweep* sweep, const double* metrics, const double* detail,
+                             const int32_t* pair_base, double* stats, double* paired);
+/* pcx_simulate_sweep_f64 with the detail launch after every timestep's metrics and one statistics
+ * launch after the last timestep; asynchronous on the context's stream with no host wait of its own.
+ * Every field of `result` is byte for byte what pcx_simulate_sweep_f64 writes for the sweep;
+ * study->detail[t] is pcx_sim_sweep_detail_f64 on timestep t's rounds and outputs, study->stats /
+ * paired are pcx_sim_sweep_stats_f64 on the call's own metrics and detail (result->metrics NULL: the
+ * metrics are kept in the workspace too).  study->stats is required; paired needs pair_base.
+ * Refuses what pcx_sim_study_check refuses before it launches anything; C = 0 launches nothing. */
+int pcx_simulate_study_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const int32_t* pair_base,
+                           pcx_sim_result* result, pcx_sim_study_result* study);
+
+/* ------------------------------------------------------------------------ */
 /* Single-matrix regime: one N x E report matrix, optionally sharded by        */
 /* contiguous reporter rows over several GPUs (one process -- or one thread --  */
 /* per rank).  One call runs the whole Oracle(...).consensus() of              */

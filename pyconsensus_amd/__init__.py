@@ -9,11 +9,12 @@ row-sharded over GPUs: :func:`pyconsensus_amd.pipeline.consensus_matrix`.
 Monte Carlo trajectories generated, run and scored on the device: :func:`simulate`
 (with :func:`generate`, :func:`generate_host` and the metric names :data:`METRICS`; the
 module's other names: ``from pyconsensus_amd.simulate import ...``); a whole study, cells of
-different shapes, rates and seeds, in one call: :func:`sweep` over a cell list or a :func:`grid`.
+different shapes, rates and seeds, in one call: :func:`sweep` over a cell list or a :func:`grid`;
+with error bars, liar-detection metrics and paired differences between cells: :func:`study`.
 """
 __version__ = "0.1.0"
 
 from .batched import consensus_batched, consensus_ragged  # noqa: E402,F401
 from .oracle import Oracle  # noqa: E402,F401
 from .many import consensus_many  # noqa: E402,F401
-from .simulate import METRICS, generate, generate_host, grid, simulate, sweep  # noqa: E402,F401
+from .simulate import METRICS, generate, generate_host, grid, simulate, study, sweep  # noqa: E402,F401

@@ -144,6 +144,17 @@ class SimSweep(C.Structure):
         ("cluster_threshold", C.c_double), ("reputation0", C.c_void_p)]
 
 
+# simulator studies: the detail metrics, the per-cell statistics and the paired differences
+SIM_NDETAIL = 12                 # PCX_SIM_NDETAIL
+SIM_NVALUES = SIM_NMETRICS + SIM_NDETAIL  # PCX_SIM_NVALUES
+SIM_NSTATS, SIM_NPAIRED = 5, 3   # PCX_SIM_NSTATS, PCX_SIM_NPAIRED
+
+
+class SimStudyResult(C.Structure):
+    """pcx_sim_study_result: what a study writes beside a sweep's pcx_sim_result."""
+    _fields_ = [("detail", C.c_void_p), ("stats", C.c_void_p), ("paired", C.c_void_p)]
+
+
 # ---------------------------------------------------------------- single-matrix regime
 MEM_DEVICE, MEM_HOST = 0, 1
 F64, U64 = 0, 1                  # enum pcx_dtype

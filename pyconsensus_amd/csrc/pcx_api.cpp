@@ -16,6 +16,7 @@
 
 #include "../../include/pcx.h"
 #include "pcx_internal.h"
+#include "pcx_sim_study.h"
 #include "pcx_sim_sweep.h"
 #include "pcx_sync.h"
 #include "pcx_seqsum.h"
@@ -1370,12 +1371,44 @@ int pcx_sim_sweep_metrics_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const pc
     return e == hipSuccess ? PCX_OK : hip_fail(e, "k_sim_sweep_metrics / k_sim_sweep_summary launch");
 }
 
-int pcx_simulate_sweep_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* res) {
-    if (!ctx || !sweep || !res) return fail(PCX_EINVAL, "pcx_simulate_sweep_f64: null argument");
+// bytes of pair_base [C] behind a sweep's tables in a staging slot (a multiple of 8)
+static size_t pair_base_bytes(const pcx_sim_sweep* s) { return ((size_t)s->n_cells * sizeof(int32_t) + 7) / 8 * 8; }
+
+// the pair_base checks of pcx_sim_study_check, on a sweep that sweep_check has passed
+static int study_check(const pcx_sim_sweep* s, const int32_t* pair_base, const char* who, int64_t* bad_cell) {
+    if (bad_cell) *bad_cell = -1;
+    for (int64_t c = 0; pair_base && c < s->n_cells; c++) {
+        const int64_t base = pair_base[c];
+        if (base == -1) continue;
+        if (base < 0 || base >= s->n_cells)
+            return sweep_fail(bad_cell, c, who,
+                              "pair_base " + std::to_string(base) + " is outside [0, " + std::to_string(s->n_cells) +
+                                  ") (-1 = no base)");
+        if (base == c) return sweep_fail(bad_cell, c, who, "pair_base is the cell itself");
+        if (s->cells[base].n_rounds != s->cells[c].n_rounds)
+            return sweep_fail(bad_cell, c, who,
+                              "has " + std::to_string(s->cells[c].n_rounds) + " rounds, its base cell " +
+                                  std::to_string(base) + " has " + std::to_string(s->cells[base].n_rounds) +
+                                  " (a pair is round b of both)");
+    }
+    return PCX_OK;
+}
+
+// The loop of pcx_simulate_sweep_f64 and pcx_simulate_study_f64 (`who`).  study NULL: the sweep.
+// Otherwise every timestep's metrics launch is followed by the detail launch, and one statistics
+// launch follows the last timestep.
+static int sweep_run(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* res, const int32_t* pair_base,
+                     const pcx_sim_study_result* study, const char* who) {
+    const std::string name(who);
     int64_t tot[4], cnt[4], lds[4];
-    if (const int rc = sweep_check(sweep, "pcx_simulate_sweep_f64", tot, cnt, lds, nullptr)) return rc;
+    if (const int rc = sweep_check(sweep, who, tot, cnt, lds, nullptr)) return rc;
+    if (study) {
+        if (const int rc = study_check(sweep, pair_base, who, nullptr)) return rc;
+        if (study->paired && !pair_base) return fail(PCX_EINVAL, name + ": paired needs pair_base");
+    }
     const int64_t C = sweep->n_cells, B = tot[0], T = sweep->n_timesteps;
     if (C == 0) return PCX_OK;
+    if (study && !study->stats) return fail(PCX_EINVAL, name + ": study->stats is NULL");
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     // the cells expanded into the wide ragged call's per-round shapes
@@ -1383,7 +1416,7 @@ int pcx_simulate_sweep_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_res
     try {
         shape.resize((size_t)B * 2);
     } catch (const std::bad_alloc&) {
-        return fail(PCX_ENOMEM, "pcx_simulate_sweep_f64: no host memory for the per-round shapes");
+        return fail(PCX_ENOMEM, name + ": no host memory for the per-round shapes");
     }
     int32_t* nrep = shape.data();
     int32_t* nev = nrep + B;
@@ -1394,7 +1427,12 @@ int pcx_simulate_sweep_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_res
         }
     // work buffers, pcx_simulate_f64's layout over the flat arrays
     const size_t bn = (size_t)tot[1], be = (size_t)tot[2], bne = (size_t)tot[3];
-    const size_t n_f64 = bne + 4 * be + 3 * bn + (size_t)B * PCX_SIM_NMETRICS;
+    // (a study keeps every timestep's metrics and detail for its statistics: in the workspace, behind
+    // the sweep's doubles, where the caller gives no buffer)
+    const bool all_metrics = study && !res->metrics;
+    const size_t n_metrics = (size_t)(all_metrics ? T : 1) * B * PCX_SIM_NMETRICS;
+    const size_t n_detail = study && !study->detail ? (size_t)T * B * PCX_SIM_NDETAIL : 0;
+    const size_t n_f64 = bne + 4 * be + 3 * bn + n_metrics + n_detail;
     if (const int rc = sim_reserve(ctx, std::max<size_t>(n_f64 * sizeof(double) + be + bn, 16))) return rc;
     double* p = (double*)ctx->sim_buf;
     auto take = [&p](size_t n) {
@@ -1410,17 +1448,25 @@ int pcx_simulate_sweep_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_res
     double* w_outcomes = take(be);
     double* w_old = take(bn);
     double* w_smooth[2] = {take(bn), take(bn)};
-    double* w_metrics = take((size_t)B * PCX_SIM_NMETRICS);
+    double* w_metrics = take(n_metrics);
+    double* all_detail = study ? (study->detail ? study->detail : take(n_detail)) : nullptr;
     work.scaled = (uint8_t*)p;
     work.liar = work.scaled + be;
     // every table of the call in one staging slot, uploaded once: the wide ragged call's descriptors
     // (the same every timestep: only the data pointers change), then the sweep's own
     WidePlan plan;
+    const bool pairs = study && study->paired;
     if (const int rc = wide_tables(ctx, B, nrep, nev, sweep->algorithm, false, cnt, lds, false,
-                                   sweep_table_bytes(sweep), &plan))
+                                   sweep_table_bytes(sweep) + (pairs ? pair_base_bytes(sweep) : 0), &plan))
         return rc;
     const pcx::SweepTables tab = sweep_tables_fill(sweep, static_cast<char*>(plan.slot->pin) + plan.off_x,
                                                    static_cast<char*>(plan.slot->dev) + plan.off_x);
+    const int32_t* dev_base = nullptr;  // pair_base rides behind the sweep's tables
+    if (pairs) {
+        const size_t at = plan.off_x + sweep_table_bytes(sweep);
+        std::memcpy(static_cast<char*>(plan.slot->pin) + at, pair_base, (size_t)C * sizeof(int32_t));
+        dev_base = reinterpret_cast<const int32_t*>(static_cast<char*>(plan.slot->dev) + at);
+    }
     e = ragged_slot_upload(ctx, *plan.slot, plan.bytes);
     if (e != hipSuccess) return hip_fail(e, "sweep: table upload");
     const double* rep = sweep->reputation0;
@@ -1461,8 +1507,10 @@ int pcx_simulate_sweep_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_res
         a.B = B;
         e = wide_launch(ctx, plan, a);
         if (e != hipSuccess) return hip_fail(e, "sweep: ragged wide launch");
-        if (res->metrics || res->summary) {
-            double* m = res->metrics ? res->metrics + (size_t)t * B * PCX_SIM_NMETRICS : w_metrics;
+        if (res->metrics || res->summary || study) {
+            double* m = res->metrics   ? res->metrics + (size_t)t * B * PCX_SIM_NMETRICS
+                        : all_metrics ? w_metrics + (size_t)t * B * PCX_SIM_NMETRICS
+                                      : w_metrics;
             e = pcx::launch_sim_sweep_metrics(tab, sweep->scaled_tol, r, o.old_rep, o.smooth_rep, o.outcomes_final, m,
                                               ctx->stream);
             if (e == hipSuccess && res->summary)
@@ -1470,15 +1518,155 @@ int pcx_simulate_sweep_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_res
                                                   ctx->stream);
             if (e != hipSuccess) return hip_fail(e, "k_sim_sweep_metrics / k_sim_sweep_summary launch");
         }
+        if (study) {
+            e = pcx::launch_sim_study_detail(tab, 0, 0, sweep->scaled_tol, r, o.old_rep, o.smooth_rep, o.outcomes_final,
+                                             all_detail + (size_t)t * B * PCX_SIM_NDETAIL, ctx->stream);
+            if (e != hipSuccess) return hip_fail(e, "k_sim_study_detail launch");
+        }
         rep = o.smooth_rep;  // the next timestep's reputation
+    }
+    if (study) {
+        e = pcx::launch_sim_study_stats(tab, T, res->metrics ? res->metrics : w_metrics, all_detail, dev_base,
+                                        study->stats, pairs ? study->paired : nullptr, ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "k_sim_study_stats launch");
     }
     e = hipEventRecord(plan.slot->kern_ev, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "sweep: hipEventRecord");
     if (res->reputation && bn) {
         e = hipMemcpyAsync(res->reputation, rep, bn * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
-        if (e != hipSuccess) return hip_fail(e, "pcx_simulate_sweep_f64: reputation copy");
+        if (e != hipSuccess) return hip_fail(e, (name + ": reputation copy").c_str());
     }
     return PCX_OK;
+}
+
+int pcx_simulate_sweep_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* res) {
+    if (!ctx || !sweep || !res) return fail(PCX_EINVAL, "pcx_simulate_sweep_f64: null argument");
+    return sweep_run(ctx, sweep, res, nullptr, nullptr, "pcx_simulate_sweep_f64");
+}
+
+// ---------------------------------------------------------------- simulator studies
+int pcx_simulate_study_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const int32_t* pair_base, pcx_sim_result* res,
+                           pcx_sim_study_result* study) {
+    if (!ctx || !sweep || !res || !study) return fail(PCX_EINVAL, "pcx_simulate_study_f64: null argument");
+    return sweep_run(ctx, sweep, res, pair_base, study, "pcx_simulate_study_f64");
+}
+
+int pcx_sim_study_check(const pcx_sim_sweep* sweep, const int32_t* pair_base, int64_t* bad_cell) {
+    if (!sweep) return fail(PCX_EINVAL, "pcx_sim_study_check: null argument");
+    if (const int rc = sweep_check(sweep, "pcx_sim_study_check", nullptr, nullptr, nullptr, bad_cell)) return rc;
+    return study_check(sweep, pair_base, "pcx_sim_study_check", bad_cell);
+}
+
+static bool detail_args(const pcx_sim_rounds* r, const double* old_rep, const double* smooth_rep,
+                        const double* outcomes_final, const double* detail) {
+    return r->scaled && r->lo && r->hi && r->truth && r->liar && old_rep && smooth_rep && outcomes_final && detail;
+}
+
+int pcx_sim_detail_host(const pcx_sim* sim, const pcx_sim_rounds* rounds, const double* old_rep,
+                        const double* smooth_rep, const double* outcomes_final, double* detail) {
+    if (!sim || !rounds) return fail(PCX_EINVAL, "pcx_sim_detail_host: null argument");
+    if (const int rc = sim_check(sim, "pcx_sim_detail_host")) return rc;
+    if (!detail_args(rounds, old_rep, smooth_rep, outcomes_final, detail))
+        return fail(PCX_EINVAL, "pcx_sim_detail_host: null argument (rounds needs scaled, lo, hi, truth and liar)");
+    pcx::sim_study_detail_host(nullptr, 0, sim->n_rounds, (int32_t)sim->n_reporters, (int32_t)sim->n_events,
+                               sim->scaled_tol, *rounds, old_rep, smooth_rep, outcomes_final, detail);
+    return PCX_OK;
+}
+
+int pcx_sim_detail_f64(pcx_ctx* ctx, const pcx_sim* sim, const pcx_sim_rounds* rounds, const double* old_rep,
+                       const double* smooth_rep, const double* outcomes_final, double* detail) {
+    if (!ctx || !sim || !rounds) return fail(PCX_EINVAL, "pcx_sim_detail_f64: null argument");
+    if (const int rc = sim_check(sim, "pcx_sim_detail_f64")) return rc;
+    if (!detail_args(rounds, old_rep, smooth_rep, outcomes_final, detail))
+        return fail(PCX_EINVAL, "pcx_sim_detail_f64: null argument (rounds needs scaled, lo, hi, truth and liar)");
+    if (sim->n_reporters > 0x7fffffff || sim->n_events > 0x7fffffff)
+        return fail(PCX_EINVAL, "pcx_sim_detail_f64: n_reporters and n_events must be below 2^31");
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    pcx::SweepTables tab{nullptr, nullptr, 0, sim->n_rounds};
+    e = pcx::launch_sim_study_detail(tab, (int32_t)sim->n_reporters, (int32_t)sim->n_events, sim->scaled_tol, *rounds,
+                                     old_rep, smooth_rep, outcomes_final, detail, ctx->stream);
+    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_sim_study_detail launch");
+}
+
+int pcx_sim_sweep_detail_host(const pcx_sim_sweep* sweep, const pcx_sim_rounds* rounds, const double* old_rep,
+                              const double* smooth_rep, const double* outcomes_final, double* detail) {
+    if (!sweep || !rounds) return fail(PCX_EINVAL, "pcx_sim_sweep_detail_host: null argument");
+    if (const int rc = sweep_check(sweep, "pcx_sim_sweep_detail_host", nullptr, nullptr, nullptr, nullptr)) return rc;
+    if (sweep->n_cells == 0) return PCX_OK;
+    if (!detail_args(rounds, old_rep, smooth_rep, outcomes_final, detail))
+        return fail(PCX_EINVAL, "pcx_sim_sweep_detail_host: null argument (rounds needs scaled, lo, hi, truth and liar)");
+    std::vector<char> tab(sweep_table_bytes(sweep));
+    const pcx::SweepTables t = sweep_tables_fill(sweep, tab.data(), tab.data());
+    pcx::sim_study_detail_host(t.cells, t.C, t.B, 0, 0, sweep->scaled_tol, *rounds, old_rep, smooth_rep, outcomes_final,
+                               detail);
+    return PCX_OK;
+}
+
+int pcx_sim_sweep_detail_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const pcx_sim_rounds* rounds,
+                             const double* old_rep, const double* smooth_rep, const double* outcomes_final,
+                             double* detail) {
+    if (!ctx || !sweep || !rounds) return fail(PCX_EINVAL, "pcx_sim_sweep_detail_f64: null argument");
+    if (const int rc = sweep_check(sweep, "pcx_sim_sweep_detail_f64", nullptr, nullptr, nullptr, nullptr)) return rc;
+    if (sweep->n_cells == 0) return PCX_OK;
+    if (!detail_args(rounds, old_rep, smooth_rep, outcomes_final, detail))
+        return fail(PCX_EINVAL, "pcx_sim_sweep_detail_f64: null argument (rounds needs scaled, lo, hi, truth and liar)");
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    pcx_ctx::RaggedSlot* slot = nullptr;
+    pcx::SweepTables tab;
+    if (const int rc = sweep_tables_upload(ctx, sweep, &slot, &tab)) return rc;
+    e = pcx::launch_sim_study_detail(tab, 0, 0, sweep->scaled_tol, *rounds, old_rep, smooth_rep, outcomes_final, detail,
+                                     ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(slot->kern_ev, ctx->stream);
+    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_sim_study_detail launch");
+}
+
+// what the two statistics entries check alike
+static int stats_check(const pcx_sim_sweep* sweep, const double* metrics, const double* detail,
+                       const int32_t* pair_base, const double* stats, const double* paired, const char* who) {
+    if (const int rc = sweep_check(sweep, who, nullptr, nullptr, nullptr, nullptr)) return rc;
+    if (const int rc = study_check(sweep, pair_base, who, nullptr)) return rc;
+    if (paired && !pair_base) return fail(PCX_EINVAL, std::string(who) + ": paired needs pair_base");
+    if (sweep->n_cells > 0 && (!metrics || !detail || !stats)) return fail(PCX_EINVAL, std::string(who) + ": null argument");
+    return PCX_OK;
+}
+
+int pcx_sim_sweep_stats_host(const pcx_sim_sweep* sweep, const double* metrics, const double* detail,
+                             const int32_t* pair_base, double* stats, double* paired) {
+    if (!sweep) return fail(PCX_EINVAL, "pcx_sim_sweep_stats_host: null argument");
+    if (const int rc = stats_check(sweep, metrics, detail, pair_base, stats, paired, "pcx_sim_sweep_stats_host"))
+        return rc;
+    if (sweep->n_cells == 0) return PCX_OK;
+    std::vector<char> tab(sweep_table_bytes(sweep));
+    const pcx::SweepTables t = sweep_tables_fill(sweep, tab.data(), tab.data());
+    pcx::sim_study_stats_host(t.cells, t.C, t.B, sweep->n_timesteps, metrics, detail, pair_base, stats, paired);
+    return PCX_OK;
+}
+
+int pcx_sim_sweep_stats_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const double* metrics, const double* detail,
+                            const int32_t* pair_base, double* stats, double* paired) {
+    if (!ctx || !sweep) return fail(PCX_EINVAL, "pcx_sim_sweep_stats_f64: null argument");
+    if (const int rc = stats_check(sweep, metrics, detail, pair_base, stats, paired, "pcx_sim_sweep_stats_f64"))
+        return rc;
+    if (sweep->n_cells == 0) return PCX_OK;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    // the sweep's tables and, behind them, pair_base in one staging slot
+    const size_t bytes = sweep_table_bytes(sweep), all = bytes + (paired ? pair_base_bytes(sweep) : 0);
+    pcx_ctx::RaggedSlot* slot = nullptr;
+    if (const int rc = ragged_slot_take(ctx, all, &slot)) return rc;
+    const pcx::SweepTables tab = sweep_tables_fill(sweep, slot->pin, slot->dev);
+    const int32_t* dev_base = nullptr;
+    if (paired) {
+        std::memcpy(static_cast<char*>(slot->pin) + bytes, pair_base, (size_t)sweep->n_cells * sizeof(int32_t));
+        dev_base = reinterpret_cast<const int32_t*>(static_cast<char*>(slot->dev) + bytes);
+    }
+    e = ragged_slot_upload(ctx, *slot, all);
+    if (e != hipSuccess) return hip_fail(e, "study: table upload");
+    e = pcx::launch_sim_study_stats(tab, sweep->n_timesteps, metrics, detail, dev_base, stats, paired, ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(slot->kern_ev, ctx->stream);
+    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_sim_study_stats launch");
 }
 
 }  // extern "C"

@@ -33,6 +33,19 @@ struct SweepTables {
     int64_t B;
 };
 
+// the cell of round b: the largest c with prefix[c] <= b (prefix[0] = 0 <= b < B = prefix[C])
+__device__ __forceinline__ int sweep_cell_of(const int64_t* __restrict__ prefix, int C, int64_t b) {
+    int lo = 0, hi = C;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (prefix[mid] <= b)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
 // one timestep's rounds of every cell, flat layout (any pointer of `out` may be NULL)
 hipError_t launch_sim_sweep_generate(const SweepTables& s, uint32_t t, const pcx_sim_rounds& out, hipStream_t st);
 // the same on the host: `cells` is a HOST table

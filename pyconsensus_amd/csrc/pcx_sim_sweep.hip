@@ -48,19 +48,6 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// the cell of round b: the largest c with prefix[c] <= b (prefix[0] = 0 <= b < B = prefix[C])
-__device__ __forceinline__ int cell_of(const int64_t* __restrict__ prefix, int C, int64_t b) {
-    int lo = 0, hi = C;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (prefix[mid] <= b)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(SW_TB) void k_sim_sweep_generate(const SweepTables s, const uint32_t t,
                                                               const pcx_sim_rounds out) {
     __shared__ double s_lo[SW_WAVES][SW_MAXE], s_hi[SW_WAVES][SW_MAXE], s_truth[SW_WAVES][SW_MAXE],
@@ -70,7 +57,7 @@ __global__ __launch_bounds__(SW_TB) void k_sim_sweep_generate(const SweepTables 
     const int w = suniform32(threadIdx.x / SW_WAVE);
     const int64_t step = (int64_t)gridDim.x * SW_WAVES;
     for (int64_t b = (int64_t)blockIdx.x * SW_WAVES + w; b < s.B; b += step) {
-        const SweepCell* cp = s.cells + suniform32(cell_of(s.prefix, s.C, b));
+        const SweepCell* cp = s.cells + suniform32(sweep_cell_of(s.prefix, s.C, b));
         const int N = suniform32(cp->N), E = suniform32(cp->E);
         const int64_t rb = b - suniform64(cp->round0);  // the round inside its cell: the draws' counter
         const int64_t row = suniform64(cp->row0) + rb * N, ev = suniform64(cp->ev0) + rb * E;
@@ -138,7 +125,7 @@ __global__ __launch_bounds__(SW_TB) void k_sim_sweep_metrics(const SweepTables s
                                                              double* __restrict__ metrics) {
     const int64_t b = (int64_t)blockIdx.x * SW_TB + threadIdx.x;
     if (b >= s.B) return;
-    const SweepCell* cp = s.cells + cell_of(s.prefix, s.C, b);
+    const SweepCell* cp = s.cells + sweep_cell_of(s.prefix, s.C, b);
     const int64_t N = cp->N, E = cp->E, rb = b - cp->round0;
     const int64_t row = cp->row0 + rb * N, ev = cp->ev0 + rb * E;
     int64_t ok = 0;

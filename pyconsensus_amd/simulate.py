@@ -15,6 +15,12 @@ A study is a curve or a grid, not a point: :func:`sweep` runs cells of different
 seeds in one call (``pcx_simulate_sweep_f64``), each cell byte for byte its own
 :func:`simulate`, and :func:`grid` builds the cell list of a cartesian product.  On the command
 line a comma list for a shape or a rate (``--liars 0.1,0.2,0.3 --reporters 20,50``) runs the grid.
+
+A study's result has error bars: :func:`study` is :func:`sweep` plus the twelve :data:`DETAIL` metrics
+of every round and timestep (did the consensus punish the liars? what kind of wrong was a wrong
+outcome?), every value's per-cell ``{n, mean, var, min, max}`` and, against a base cell, the paired
+differences in which common random numbers pay off (``pcx_simulate_study_f64``).
+``--stats`` and ``--paired`` print them.
 """
 from __future__ import annotations
 
@@ -26,6 +32,11 @@ from . import _abi, _device, _lib
 from .batched import clusterfeck_threshold
 
 METRICS = ("correct", "liar_rep_before", "liar_rep_after", "liars_bonus", "beats", "n_liars")
+DETAIL = ("correct_binary", "correct_scaled", "indeterminate", "flipped", "nan_outcomes", "scaled_err",
+          "tp", "fn", "fp", "tn", "mcc", "colluder_rep_after")
+VALUES = METRICS + DETAIL
+STATS = ("n", "mean", "var", "min", "max")
+PAIRED = ("n", "mean", "var")
 ROUND_FIELDS = tuple(name for name, _, _ in _abi.SIM_ROUNDS)
 
 _NP = {"f8": np.float64, "u1": np.uint8, "i4": np.int32}
@@ -328,6 +339,14 @@ def sweep(cells, T=1, scaled_tol=0.1, algorithm="PCA", catch_tolerance=0.1, alph
     Asynchronous on torch's current stream, with no host wait between the timesteps.  A sweep runs
     the generic ragged kernels: a study of ONE shape belongs on :func:`simulate`, whose compiled
     equal-shape kernel is faster."""
+    return _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_components, variance_threshold,
+                      hierarchy_threshold, cluster_threshold, reputation, keep_rounds, keep_outputs, device)
+
+
+def _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_components, variance_threshold,
+               hierarchy_threshold, cluster_threshold, reputation, keep_rounds, keep_outputs, device,
+               with_study=False, pair_with=None, keep_detail=False):
+    """:func:`sweep` (``pcx_simulate_sweep_f64``) or, ``with_study``, :func:`study` (``pcx_simulate_study_f64``)."""
     tc = _device.require_gpu()
     dev = tc.device(device) if device is not None else tc.device("cuda", tc.cuda.current_device())
     rep = _device.as_device(reputation, tc.float64, dev)
@@ -355,10 +374,251 @@ def sweep(cells, T=1, scaled_tol=0.1, algorithm="PCA", catch_tolerance=0.1, alph
             outs[name] = tc.empty(_abi.ragged_out_len(kind, B, totals), dtype=_torch_dtype(tc, dt), device=dev)
             setattr(res.last_out, name, outs[name].data_ptr())
         out["outputs"] = outs
+    if with_study:
+        base = study_check(norm, pair_with, T, algorithm=algorithm, scaled_tol=scaled_tol,
+                           max_components=max_components)  # refuses by cell
+        st = _abi.SimStudyResult()
+        out["stats"] = tc.empty((T, Cn, _abi.SIM_NVALUES, _abi.SIM_NSTATS), dtype=tc.float64, device=dev)
+        st.stats = out["stats"].data_ptr()
+        if base is not None:
+            out["paired"] = tc.empty((T, Cn, _abi.SIM_NVALUES, _abi.SIM_NPAIRED), dtype=tc.float64, device=dev)
+            out["pair_base"] = base
+            st.paired = out["paired"].data_ptr()
+        if keep_detail:
+            out["detail"] = tc.empty((T, B, _abi.SIM_NDETAIL), dtype=tc.float64, device=dev)
+            st.detail = out["detail"].data_ptr()
     h = _lib.bind_stream(dev.index, _device.current_stream_handle(dev))
-    _lib.check(_lib.lib().pcx_simulate_sweep_f64(h, C.byref(s), C.byref(res)))
+    if with_study:
+        _lib.check(_lib.lib().pcx_simulate_study_f64(h, C.byref(s), None if base is None else base.ctypes.data,
+                                                     C.byref(res), C.byref(st)))
+    else:
+        _lib.check(_lib.lib().pcx_simulate_sweep_f64(h, C.byref(s), C.byref(res)))
     out["_inputs"] = (rep,)  # alive until the caller syncs
     return out
+
+
+# ---------------------------------------------------------------- studies
+def pair_base(cells, pair_with):
+    """``pair_with`` as the library's ``pair_base``: an int32 array [C] (-1: no base) or None.
+    ``"first"`` pairs each cell with the first cell of the list that has its shape, rounds and seed
+    (that first cell itself gets -1); a sequence gives the base indices."""
+    if pair_with is None:
+        return None
+    norm = _cells(cells)[0]
+    if isinstance(pair_with, str):
+        if pair_with != "first":
+            raise ValueError("pair_with is a list of base cells or 'first', not %r" % (pair_with,))
+        first, base = {}, []
+        for c, d in enumerate(norm):
+            key = (int(d["reporters"]), int(d["events"]), int(d["rounds"]), int(d["seed"]) & 0xFFFFFFFFFFFFFFFF)
+            base.append(first.setdefault(key, c))
+        return np.array([-1 if b == c else b for c, b in enumerate(base)], dtype=np.int32)
+    base = np.array([int(b) for b in pair_with], dtype=np.int64)
+    if base.shape != (len(norm),):
+        raise ValueError("pair_with needs one base per cell (%d), got %d" % (len(norm), base.size))
+    if base.size and (base.min() < -(1 << 31) or base.max() >= (1 << 31)):
+        raise ValueError("pair_with: a base is no int32")
+    return base.astype(np.int32)
+
+
+def study_check(cells, pair_with=None, T=1, algorithm="PCA", **params):
+    """Validate a study without a device (``pcx_sim_study_check``): what :func:`sweep_plan` refuses, then
+    a base outside the cell list, a cell that is its own base, a base with another number of rounds.
+    Raises with the cell's index; returns the ``pair_base`` array (or None)."""
+    s, arr, _, _ = _sweep(cells, T, algorithm=algorithm, **params)
+    base = pair_base(cells, pair_with)
+    bad = C.c_int64(-2)
+    _lib.check(_lib.lib().pcx_sim_study_check(C.byref(s), None if base is None else base.ctypes.data, C.byref(bad)))
+    return base
+
+
+def _host_rounds(rounds, offsets=None, shape=None):
+    """The pcx_sim_rounds of numpy arrays (everything but ``reports``), checked against the flat
+    lengths of ``offsets`` or the equal shape (B, N, E)."""
+    c, keep = _abi.SimRounds(), []
+    for name, kind, dt in _abi.SIM_ROUNDS:
+        if name == "reports":
+            continue
+        a = np.ascontiguousarray(rounds[name], dtype=_NP[dt])
+        want = (_flat_len(kind, offsets),) if offsets is not None else _abi.out_shape(kind, *shape)
+        if tuple(a.shape) != tuple(want):
+            raise ValueError("rounds[%r] must have shape %s" % (name, tuple(want)))
+        keep.append(a)
+        setattr(c, name, a.ctypes.data)
+    return c, keep
+
+
+def detail_host(rounds, old_rep, smooth_rep, outcomes_final, scaled_tol=0.1):
+    """The twelve :data:`DETAIL` metrics of B equal-shape rounds on the CPU (``pcx_sim_detail_host``; no
+    GPU needed): numpy in, ``(B, 12)`` out -- bit for bit what :func:`detail` gives on the device."""
+    old, smooth, outc = (np.ascontiguousarray(x, dtype=np.float64) for x in (old_rep, smooth_rep, outcomes_final))
+    if old.ndim != 2 or outc.ndim != 2 or smooth.shape != old.shape or outc.shape[0] != old.shape[0]:
+        raise ValueError("old_rep / smooth_rep must be (B, N) and outcomes_final (B, E)")
+    (B, N), E = old.shape, outc.shape[1]
+    c, keep = _host_rounds(rounds, shape=(B, N, E))
+    s = _sim(B, N, E, 1, 0, 0.0, 0.0, 0.0, 0.0, 0.0, scaled_tol=scaled_tol)
+    d = np.empty((B, _abi.SIM_NDETAIL), dtype=np.float64)
+    _lib.check(_lib.lib().pcx_sim_detail_host(C.byref(s), C.byref(c), old.ctypes.data, smooth.ctypes.data,
+                                              outc.ctypes.data, d.ctypes.data))
+    return d
+
+
+def detail(rounds, old_rep, smooth_rep, outcomes_final, scaled_tol=0.1, device=None):
+    """:func:`detail_host` on the device (``pcx_sim_detail_f64``): a ``(B, 12)`` tensor.  Asynchronous."""
+    tc = _device.require_gpu()
+    dev = tc.device(device) if device is not None else tc.device("cuda", tc.cuda.current_device())
+    c, keep = _abi.SimRounds(), []
+    for name, _, dt in _abi.SIM_ROUNDS:
+        if name != "reports":
+            x = _device.as_device(rounds[name], _torch_dtype(tc, dt), dev)
+            keep.append(x)
+            setattr(c, name, x.data_ptr())
+    B, N = keep[-1].shape
+    E = keep[0].shape[1]
+    old, smooth, outc = (_device.as_device(x, tc.float64, dev) for x in (old_rep, smooth_rep, outcomes_final))
+    if tuple(old.shape) != (B, N) or tuple(smooth.shape) != (B, N) or tuple(outc.shape) != (B, E):
+        raise ValueError("old_rep / smooth_rep must be (B, N) and outcomes_final (B, E)")
+    for x in keep[:-1]:
+        if tuple(x.shape) != (B, E):
+            raise ValueError("the event arrays of rounds must be (B, E)")
+    s = _sim(B, N, E, 1, 0, 0.0, 0.0, 0.0, 0.0, 0.0, scaled_tol=scaled_tol)
+    d = tc.empty((B, _abi.SIM_NDETAIL), dtype=tc.float64, device=dev)
+    h = _lib.bind_stream(dev.index, _device.current_stream_handle(dev))
+    _lib.check(_lib.lib().pcx_sim_detail_f64(h, C.byref(s), C.byref(c), old.data_ptr(), smooth.data_ptr(),
+                                             outc.data_ptr(), d.data_ptr()))
+    d._pcx_inputs = (keep, old, smooth, outc)  # alive until the caller syncs
+    return d
+
+
+def sweep_detail_host(cells, rounds, old_rep, smooth_rep, outcomes_final, scaled_tol=0.1):
+    """The :data:`DETAIL` metrics of a sweep's flat rounds on the CPU (``pcx_sim_sweep_detail_host``; no
+    GPU needed): numpy in, ``(B, 12)`` out in the flat round order of ``metrics``."""
+    s, arr, norm, offsets = _sweep(cells, 1, scaled_tol=scaled_tol)
+    sweep_plan(cells, 1, scaled_tol=scaled_tol)  # refuses by cell before any array is read
+    c, keep = _host_rounds(rounds, offsets=offsets)
+    old, smooth, outc = (np.ascontiguousarray(x, dtype=np.float64) for x in (old_rep, smooth_rep, outcomes_final))
+    tn, te = _flat_len("N", offsets), _flat_len("E", offsets)
+    if old.shape != (tn,) or smooth.shape != (tn,) or outc.shape != (te,):
+        raise ValueError("old_rep / smooth_rep must be flat [sum R N] and outcomes_final flat [sum R E]")
+    d = np.empty((int(offsets["rounds"][-1]), _abi.SIM_NDETAIL), dtype=np.float64)
+    _lib.check(_lib.lib().pcx_sim_sweep_detail_host(C.byref(s), C.byref(c), old.ctypes.data, smooth.ctypes.data,
+                                                    outc.ctypes.data, d.ctypes.data))
+    return d
+
+
+def sweep_detail(cells, rounds, old_rep, smooth_rep, outcomes_final, scaled_tol=0.1, device=None):
+    """:func:`sweep_detail_host` on the device (``pcx_sim_sweep_detail_f64``): a ``(B, 12)`` tensor.
+    Asynchronous on torch's current stream."""
+    tc = _device.require_gpu()
+    dev = tc.device(device) if device is not None else tc.device("cuda", tc.cuda.current_device())
+    s, arr, norm, offsets = _sweep(cells, 1, scaled_tol=scaled_tol)
+    sweep_plan(cells, 1, scaled_tol=scaled_tol)
+    c, keep = _abi.SimRounds(), []
+    for name, kind, dt in _abi.SIM_ROUNDS:
+        if name != "reports":
+            x = _device.as_device(rounds[name], _torch_dtype(tc, dt), dev)
+            if tuple(x.shape) != (_flat_len(kind, offsets),):
+                raise ValueError("rounds[%r] must be flat, %d long" % (name, _flat_len(kind, offsets)))
+            keep.append(x)
+            setattr(c, name, x.data_ptr())
+    old, smooth, outc = (_device.as_device(x, tc.float64, dev) for x in (old_rep, smooth_rep, outcomes_final))
+    tn, te = _flat_len("N", offsets), _flat_len("E", offsets)
+    if tuple(old.shape) != (tn,) or tuple(smooth.shape) != (tn,) or tuple(outc.shape) != (te,):
+        raise ValueError("old_rep / smooth_rep must be flat [sum R N] and outcomes_final flat [sum R E]")
+    d = tc.empty((int(offsets["rounds"][-1]), _abi.SIM_NDETAIL), dtype=tc.float64, device=dev)
+    h = _lib.bind_stream(dev.index, _device.current_stream_handle(dev))
+    _lib.check(_lib.lib().pcx_sim_sweep_detail_f64(h, C.byref(s), C.byref(c), old.data_ptr(), smooth.data_ptr(),
+                                                   outc.data_ptr(), d.data_ptr()))
+    d._pcx_inputs = (keep, old, smooth, outc)  # alive until the caller syncs
+    return d
+
+
+def _stats_shapes(cells, metrics_shape, detail_shape):
+    norm, _, offsets = _cells(cells)
+    B = int(offsets["rounds"][-1])
+    if len(metrics_shape) != 3 or tuple(metrics_shape[1:]) != (B, _abi.SIM_NMETRICS):
+        raise ValueError("metrics must be (T, %d, %d)" % (B, _abi.SIM_NMETRICS))
+    T = int(metrics_shape[0])
+    if tuple(detail_shape) != (T, B, _abi.SIM_NDETAIL):
+        raise ValueError("detail must be (%d, %d, %d)" % (T, B, _abi.SIM_NDETAIL))
+    if T < 1:
+        raise ValueError("metrics and detail need at least one timestep")
+    return T, len(norm)
+
+
+def sweep_stats_host(cells, metrics, detail, pair_with=None):
+    """Per-cell statistics on the CPU (``pcx_sim_sweep_stats_host``; no GPU needed) of ``metrics (T,B,6)``
+    and ``detail (T,B,12)``: a dict with ``stats (T,C,18,5)`` (:data:`VALUES` x :data:`STATS`) and, with
+    ``pair_with`` (see :func:`study`), ``paired (T,C,18,3)`` and ``pair_base``.  The library's summation
+    order replayed in a loop: bit for bit :func:`sweep_stats`."""
+    m, d = (np.ascontiguousarray(x, dtype=np.float64) for x in (metrics, detail))
+    T, Cn = _stats_shapes(cells, m.shape, d.shape)
+    base = study_check(cells, pair_with, T)
+    s, arr, _, _ = _sweep(cells, T)
+    out = {"stats": np.empty((T, Cn, _abi.SIM_NVALUES, _abi.SIM_NSTATS), dtype=np.float64)}
+    if base is not None:
+        out["paired"] = np.empty((T, Cn, _abi.SIM_NVALUES, _abi.SIM_NPAIRED), dtype=np.float64)
+        out["pair_base"] = base
+    _lib.check(_lib.lib().pcx_sim_sweep_stats_host(
+        C.byref(s), m.ctypes.data, d.ctypes.data, None if base is None else base.ctypes.data,
+        out["stats"].ctypes.data, out["paired"].ctypes.data if base is not None else None))
+    return out
+
+
+def sweep_stats(cells, metrics, detail, pair_with=None, device=None):
+    """:func:`sweep_stats_host` on the device (``pcx_sim_sweep_stats_f64``), device tensors in and out.
+    One launch for all timesteps, asynchronous on torch's current stream."""
+    tc = _device.require_gpu()
+    dev = tc.device(device) if device is not None else tc.device("cuda", tc.cuda.current_device())
+    m, d = (_device.as_device(x, tc.float64, dev) for x in (metrics, detail))
+    T, Cn = _stats_shapes(cells, tuple(m.shape), tuple(d.shape))
+    base = study_check(cells, pair_with, T)
+    s, arr, _, _ = _sweep(cells, T)
+    out = {"stats": tc.empty((T, Cn, _abi.SIM_NVALUES, _abi.SIM_NSTATS), dtype=tc.float64, device=dev)}
+    if base is not None:
+        out["paired"] = tc.empty((T, Cn, _abi.SIM_NVALUES, _abi.SIM_NPAIRED), dtype=tc.float64, device=dev)
+        out["pair_base"] = base
+    h = _lib.bind_stream(dev.index, _device.current_stream_handle(dev))
+    _lib.check(_lib.lib().pcx_sim_sweep_stats_f64(
+        h, C.byref(s), m.data_ptr(), d.data_ptr(), None if base is None else base.ctypes.data,
+        out["stats"].data_ptr(), out["paired"].data_ptr() if base is not None else None))
+    out["_inputs"] = (m, d)  # alive until the caller syncs
+    return out
+
+
+def study(cells, T=1, pair_with=None, keep_detail=False, scaled_tol=0.1, algorithm="PCA", catch_tolerance=0.1,
+          alpha=0.1, max_components=5, variance_threshold=0.9, hierarchy_threshold=0.5, cluster_threshold=None,
+          reputation=None, keep_rounds=False, keep_outputs=False, device=None):
+    """:func:`sweep` with a study's result (``pcx_simulate_study_f64``): every key of
+    :func:`sweep`'s dict, byte for byte, plus
+
+    * ``stats (T,C,18,5)``: per timestep, cell and value (:data:`VALUES`: the six :data:`METRICS`, then
+      the twelve :data:`DETAIL` metrics) ``{n, mean, var, min, max}`` (:data:`STATS`) over the cell's
+      rounds whose value is not NaN.  ``mean`` of a metric without NaNs is ``summary``'s bytes;
+      :func:`stderr` turns ``var`` and ``n`` into a standard error;
+    * with ``pair_with``, ``paired (T,C,18,3)``: ``{n, mean, var}`` of ``value_c[b] - value_base[b]``,
+      round by round, and ``pair_base``, the int32 base per cell.  ``pair_with`` is a list of base cell
+      indices (-1: none; a base has its cell's number of rounds) or ``"first"``: each cell is paired with
+      the first cell of the list that has its shape, rounds and seed (that first cell gets -1).  Cells
+      that share a seed see common random numbers, so the paired standard error along a parameter
+      curve is far below the difference of two independent cells';
+    * with ``keep_detail``, ``detail (T,B,12)``, the per-round :data:`DETAIL` metrics.
+
+    The detail metrics are written on the device inside the loop (one more launch per timestep), the
+    statistics by one launch after the last timestep; the call stays asynchronous on torch's current
+    stream with no host wait.  Refusals are :func:`sweep`'s and :func:`study_check`'s."""
+    return _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_components, variance_threshold,
+                      hierarchy_threshold, cluster_threshold, reputation, keep_rounds, keep_outputs, device,
+                      with_study=True, pair_with=pair_with, keep_detail=keep_detail)
+
+
+def stderr(stats_or_paired):
+    """Standard errors ``sqrt(var / n)`` of a ``stats`` or ``paired`` array (``[..., 0]`` is n and
+    ``[..., 2]`` var in both), on the host: numpy, NaN where n < 2."""
+    x = stats_or_paired
+    x = x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.sqrt(x[..., 2] / x[..., 0])
 
 
 _GRID_AXES = ("reporters", "events", "liar_frac", "collude_frac", "distort", "na_frac", "scaled_frac")
@@ -408,9 +668,17 @@ def main(argv=None):
     ap.add_argument("--scaled", type=flt, default=[0.25], help="scaled_frac (or a comma list)")
     ap.add_argument("--scaled-tol", type=float, default=0.1)
     ap.add_argument("--algorithm", default="PCA")
+    ap.add_argument("--stats", action="store_true",
+                    help="run a study: every timestep gains 'detail' (the means of the detail metrics) and "
+                         "'stderr' (the standard errors of all eighteen values)")
+    ap.add_argument("--paired", action="store_true",
+                    help="(implies --stats) pair each cell with the first of its shape: 'vs_first', "
+                         "{name: [mean, stderr]} of the round-by-round differences")
     a = ap.parse_args(argv)
     lists = {"reporters": a.reporters, "events": a.events, "liar_frac": a.liars, "collude_frac": a.collude,
              "distort": a.distort, "na_frac": a.missing, "scaled_frac": a.scaled}
+    if a.stats or a.paired:
+        return _main_study(a, lists)
     if any(len(v) > 1 for v in lists.values()):  # a grid: --rounds per cell, one shared seed
         cells = grid(a.rounds, seed=a.seed, **lists)
         r = sweep(cells, a.timesteps, scaled_tol=a.scaled_tol, algorithm=a.algorithm)
@@ -430,6 +698,38 @@ def main(argv=None):
                       "algorithm": a.algorithm,
                       "summary": [dict(zip(METRICS, (float(v) for v in row)), timestep=t)
                                   for t, row in enumerate(summary)]}))
+    return 0
+
+
+def _main_study(a, lists):
+    """--stats / --paired: the same objects as without the flags, every timestep's dict extended."""
+    import json
+
+    cells = grid(a.rounds, seed=a.seed, **lists)
+    r = study(cells, a.timesteps, pair_with="first" if a.paired else None, scaled_tol=a.scaled_tol,
+              algorithm=a.algorithm)
+    summary, stats = r["summary"].cpu().numpy(), r["stats"].cpu().numpy()  # (the copies synchronise)
+    se = stderr(stats)
+    if a.paired:
+        paired, pse, base = r["paired"].cpu().numpy(), stderr(r["paired"]), r["pair_base"]
+
+    def timestep(c, t):
+        d = dict(zip(METRICS, (float(v) for v in summary[t, c])), timestep=t)
+        d["detail"] = dict(zip(DETAIL, (float(v) for v in stats[t, c, len(METRICS):, 1])))
+        d["stderr"] = dict(zip(VALUES, (float(v) for v in se[t, c])))
+        if a.paired and base[c] >= 0:
+            d["vs_first"] = {k: [float(paired[t, c, v, 1]), float(pse[t, c, v])] for v, k in enumerate(VALUES)}
+        return d
+
+    if any(len(v) > 1 for v in lists.values()):
+        print(json.dumps({"rounds": a.rounds, "seed": a.seed, "algorithm": a.algorithm,
+                          "cells": [dict({k: v for k, v in cell.items() if k not in ("rounds", "seed")},
+                                         summary=[timestep(c, t) for t in range(a.timesteps)])
+                                    for c, cell in enumerate(cells)]}))
+    else:  # one cell: the equal-shape call's object
+        print(json.dumps({"rounds": a.rounds, "reporters": lists["reporters"][0], "events": lists["events"][0],
+                          "seed": a.seed, "algorithm": a.algorithm,
+                          "summary": [timestep(0, t) for t in range(a.timesteps)]}))
     return 0
 
 
