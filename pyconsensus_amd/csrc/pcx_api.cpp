@@ -384,8 +384,14 @@ static void print_wave_stamps(const std::vector<long long>& h, int64_t B) {
         fast += (double)h[b * 32 + 22];
         slow += (double)h[b * 32 + 23];
     }
-    fprintf(stderr, " median_sort:%.0f median_walk:%.0f outcome_shortcut:%.4f outcome_sorted:%.4f\n", sort / (double)B,
+    double iscr = 0, isort = 0;  // 24, 25: interpolation medians decided by the prescreen / sorted
+    for (int64_t b = 0; b < B; b++) {
+        iscr += (double)h[b * 32 + 24];
+        isort += (double)h[b * 32 + 25];
+    }
+    fprintf(stderr, " median_sort:%.0f median_walk:%.0f outcome_shortcut:%.4f outcome_sorted:%.4f", sort / (double)B,
             walk / (double)B, fast / (double)B, slow / (double)B);
+    fprintf(stderr, " interp_screened:%.4f interp_sorted:%.4f\n", iscr / (double)B, isort / (double)B);
 }
 
 // PCX_STAMPS, workgroup kernel: stamps 0..15 in program order (pcx_medium.hip MSTAMP(k))

@@ -629,6 +629,71 @@ __device__ PCX_OUTLINE double wave_wmedian_rank(double x, double w, bool sel, in
     return ox[k - 1];
 }
 
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+    v = max(v, xor_lane32<1>(v));
+    v = max(v, xor_lane32<2>(v));
+    v = max(v, xor_lane32<4>(v));
+    v = max(v, xor_lane32<8>(v));
+    const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)v, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
+    const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)v, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+    return max(max(r0, r1), max(r2, r3));
+}
+
+// The prescreen of an interpolation median: the weighted median of the present
+// values x under the weights rep / T, decided from 32-bit keys and single-precision sums of the
+// unnormalised reputations, with no sort, no division and one LDS store.  Lane l holds row l's
+// (x, rep, present); T is the SPEC's sequential total of the present reputations; wf[m] = (float)
+// rep_m for every row (written once per round by the caller, every rep_m >= 0); kx: NR keys of
+// scratch.  Returns true with the median in `med`, or false: the column takes wave_wmedian_rank.
+//   bl_l = sum of wf[m] over the rows whose key is below lane l's (a missing row holds the largest
+// key and is below nothing, so wf needs no per-column mask).  It is within 2^-17 T of the exact sum
+// of those reputations, and the SPEC's own sums of rep / T and its mid within 2^-44 of that sum / T
+// and of 1/2: against the margin M = 2^-16 T a lane with bl < T / 2 - M has the SPEC's running sum
+// before its value group at or below mid, and a lane with bl > T / 2 + M above it.  No lane lies
+// between (else: refused), the sums are monotone, so the SPEC's crossing element lies in the group
+// of the largest key with bl < T / 2 - M, all of whose rows hold one value v (else: refused, a
+// collision in the top 32 bits).  First of its group, its `before` is far under mid and the result
+// is v; later in the group the half test may pass and the mean is (v + v) / 2 = v.  The SPEC's
+// earlier exit (a weight above half the total) and everything near it stay with the sort, as do
+// totals outside [2^-100, 2^100] (single precision would lose the small reputations), v = +-0
+// (the group may mix the two) and |v| >= 2^1023 (v + v overflows).
+template <int NR>
+__device__ PCX_OUTLINE bool wave_wmedian_screen(double x, double rep, bool present, double T, int N, uint32_t* kx,
+                                                const float* wf, double& med) {
+    const int l = lane_id();
+    const double half = 0.5 * T, M = 0x1p-16 * T, lo = half - M;
+    const uint32_t key = present ? key_hi32(x) : 0xffffffffu;
+    wsync();  // (the previous column's reads of kx)
+    constexpr int KP = (NR + 3) & ~3;
+    if (l < KP) kx[l] = key;  // (the lanes past the last row hold the largest key)
+    wsync();
+    // two rows per 8-byte LDS read (the scratch is 8-byte aligned in every layout), every read
+    // unconditional: written as `kx[m] < key ? wf[m] : 0.f` the weight's read is sunk under the
+    // compare, one dependent LDS round trip per row
+    const uint2* const kx2 = reinterpret_cast<const uint2*>(kx);
+    const float2* const wf2 = reinterpret_cast<const float2*>(wf);
+    float bl = 0.f;
+#pragma unroll
+    for (int m = 0; m < (NR + 1) / 2; m++) {
+        if (NR == 64 && 2 * m >= N) break;
+        const uint2 k = kx2[m];
+        const float2 w = wf2[m];
+        bl += k.x < key ? w.x : 0.f;
+        bl += k.y < key ? w.y : 0.f;
+    }
+    const double b = (double)bl;
+    const bool range = T >= 0x1p-100 && T <= 0x1p100;  // (a NaN total fails)
+    if (ballot(!range || (present && (rep >= lo || fabs(b - half) <= M)))) return false;
+    const uint32_t vk = wave_max_u32(present && b < lo ? key : 0u);  // (no present value's key is 0)
+    const uint64_t at = ballot(present && key == vk);
+    if (!at) return false;
+    const double v = bcast(x, __builtin_ctzll(at));
+    if (ballot(present && key == vk && x != v)) return false;
+    if (!(v != 0.0 && fabs(v) < 0x1p1023)) return false;
+    med = v;
+    return true;
+}
+
 
 // the N x E round in LDS (row pitch ES) -> dst [N][E] row-major, lane-contiguous: each store
 // instruction covers 64 consecutive elements (16-byte pairs when N * E is even and the

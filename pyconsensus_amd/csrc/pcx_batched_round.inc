@@ -224,7 +224,36 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
             if (a.int_dtype) g = trunc(g);
             if (l == 0) S.guess[j] = g;
         };
-        // one median at a time: the scratch lives in M, dead until the covariance
+        // The prescreen (wave_wmedian_screen, DESIGN.md 5.2) first, over every such column: keys and
+        // single-precision reputations in the head of the median scratch, which the sorts below
+        // overwrite only afterwards.  A round with a negative or NaN reputation does not prescreen
+        // (its sums are not monotone), nor one of equal reputations (reputation == nullptr): with an even
+        // count of present rows a running sum lies exactly on half, every such column is refused after
+        // the prescreen's work, and the batch measured slower than with the sort alone (DESIGN.md 5.2).
+        constexpr int NRS = NT > 0 ? NT : 64, KP = (NRS + 3) & ~3;
+        const uint64_t all_j = todo;
+        if (todo && a.reputation && !ballot(row && !(rep >= 0.0))) {
+            uint32_t* const kx = reinterpret_cast<uint32_t*>(S.M);
+            float* const wf = reinterpret_cast<float*>(S.M) + KP;
+            if (l < KP) wf[l] = row ? (float)rep : 0.f;
+            for (uint64_t t = todo; t; t &= t - 1) {
+                const int j = __builtin_ctzll(t);
+                const uint64_t mj = S.miss[j];
+                const bool present = row && !((mj >> l) & 1);
+                const double x0 = row ? S.F[l * ES + j] : 0.0;
+                double g;
+                if (wave_wmedian_screen<NRS>(x0, rep, present, S.tot[j], N, kx, wf, g)) {
+                    finish(j, g);
+                    todo &= ~(1ull << j);
+                }
+            }
+            wsync();
+        }
+        if (a.stamps && l == 0) {  // diagnostic counters: plain stores, no clock read
+            a.stamps[b * 32 + 24] = popc(all_j) - popc(todo);
+            a.stamps[b * 32 + 25] = popc(todo);
+        }
+        // the rest one median at a time: the scratch lives in M, dead until the covariance
         while (todo) {
             const int j = __builtin_ctzll(todo);
             todo &= todo - 1;
