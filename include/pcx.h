@@ -214,6 +214,46 @@ int pcx_ragged_plan_wide(int64_t n_rounds, const int32_t* n_reporters, const int
  * in one launch at the largest round's LDS. */
 int pcx_consensus_ragged_wide_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_result* out);
 
+/* Per-round consensus parameters (added under ABI 9; detect by symbol): a wide ragged batch whose
+ * rounds each take one of P parameter sets -- the algorithm and the six options that the entries
+ * above share over the batch.  DESIGN.md 5.4.3 is the contract: round b's results are byte for byte
+ * those of pcx_consensus_ragged_wide_f64 over the same batch with params[param_of[b]] shared.  The
+ * kernels are the two ragged kernels' texts under new names, which read the round's set from a
+ * device table; a launch holds the rounds of one instantiation group (one-wave: PCA / absolute /
+ * cokurtosis, big-five / fixed-variance, hierarchical / clusterfeck; workgroup: the clusterings, the
+ * rest, each by launch class), so the number of launches does not depend on P. */
+typedef struct {
+    int32_t algorithm;            /* enum pcx_algorithm; k-means is refused                    */
+    int32_t max_components;       /* big-five (>= 1; capped at E_b on the device)              */
+    double  catch_tolerance;
+    double  alpha;
+    double  variance_threshold;   /* fixed-variance                                            */
+    double  hierarchy_threshold;  /* hierarchical                                              */
+    double  cluster_threshold;    /* clusterfeck (<= 0: the log10(E_b)/1.77 rule per round)    */
+} pcx_round_params;               /* 48 bytes */
+
+/* Pure (no context, no device): validates the shapes (pcx_ragged_plan_wide's limits and words), the
+ * P sets (HOST [P]) and param_of (HOST int32 [B], round b's set).  totals as pcx_ragged_plan;
+ * *n_launches = the kernel launches the call makes with nothing chunked (at most 3 one-wave and
+ * 2 x 3 workgroup launches).  On refusal returns PCX_EINVAL, pcx_last_error names the round or the
+ * set: *bad_round = the first offending round (a shape, or param_of[b] outside [0, P)), else -1;
+ * *bad_param = the first offending set of the table, used or not (an algorithm outside 0..7,
+ * k-means, a non-finite alpha or catch_tolerance, big-five with max_components < 1, a NaN
+ * hierarchy_threshold or a non-finite variance_threshold where the set's algorithm reads it), else
+ * -1; the sets are checked before the rounds; n_params < 1 with n_rounds > 0 leaves both -1.  Any
+ * output may be NULL. */
+int pcx_ragged_plan_params(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
+                           const pcx_round_params* params, const int32_t* param_of, int64_t totals[3],
+                           int64_t* n_launches, int64_t* bad_round, int64_t* bad_param);
+/* pcx_consensus_ragged_wide_f64 with params (HOST [P]) and param_of (HOST [B]) in place of in's own
+ * seven parameter fields, which are not read.  in->aux_scores (DEVICE [sum N_b]) is required if and
+ * only if some round's set is cokurtosis, and is read for those rounds only.  Refuses what
+ * pcx_ragged_plan_params refuses.  Asynchronous on the context's stream, no host wait of its own: the
+ * parameter table rides in the call's staging slot behind the descriptors, in the one upload.
+ * n_rounds == 0 succeeds and launches nothing. */
+int pcx_consensus_ragged_params_f64(pcx_ctx* ctx, const pcx_ragged* in, int64_t n_params,
+                                    const pcx_round_params* params, const int32_t* param_of, pcx_batch_result* out);
+
 /* ------------------------------------------------------------------------ */
 /* Monte Carlo simulator (ABI >= 9): the Simulator.jl-style driver of the       */
 /* batched regime (README.rst:52-56) on the device.  It draws random rounds     */
@@ -411,6 +451,25 @@ int pcx_sim_sweep_stats_host(const pcx_sim_sweep* sweep, const double* metrics, 
  * Refuses what pcx_sim_study_check refuses before it launches anything; C = 0 launches nothing. */
 int pcx_simulate_study_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const int32_t* pair_base,
                            pcx_sim_result* result, pcx_sim_study_result* study);
+
+/* Studies with per-cell consensus parameters (added under ABI 9; detect by symbol):
+ * cell c's rounds take cell_params[c] (HOST [C]) in place of the sweep's seven shared parameter
+ * fields, which are then not read.  Cell c's slice of every output is byte for byte what
+ * pcx_simulate_study_f64 gives for that cell alone with cell_params[c] as the shared parameters; a
+ * cell pairs (pair_base) with any cell of as many rounds, so the same drawn rounds under two
+ * parameter sets give a paired difference on common random numbers.  cell_params NULL: the entries
+ * above, the same bytes.
+ *
+ * pcx_sim_study_params_check is pure: what pcx_sim_study_check refuses (the shared parameters
+ * unchecked when cell_params is given), and per cell what pcx_ragged_plan_params refuses of a set,
+ * plus cokurtosis (as k-means, not simulated), with *bad_cell = the cell. */
+int pcx_sim_study_params_check(const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,
+                               const int32_t* pair_base, int64_t* bad_cell);
+/* study NULL: the sweep alone (pcx_simulate_sweep_f64's outputs; pair_base is not read).
+ * Asynchronous on the context's stream with no host wait of its own; the parameter table rides in
+ * the call's one upload.  Per timestep: the launches of pcx_consensus_ragged_params_f64. */
+int pcx_simulate_study_params_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,
+                                  const int32_t* pair_base, pcx_sim_result* result, pcx_sim_study_result* study);
 
 /* ------------------------------------------------------------------------ */
 /* Single-matrix regime: one N x E report matrix, optionally sharded by        */

@@ -144,6 +144,32 @@ class SimSweep(C.Structure):
         ("cluster_threshold", C.c_double), ("reputation0", C.c_void_p)]
 
 
+class RoundParams(C.Structure):
+    """pcx_round_params: one consensus parameter set (48 bytes), per round of a ragged batch
+    (pcx_consensus_ragged_params_f64) or per cell of a study (pcx_simulate_study_params_f64)."""
+    _fields_ = [
+        ("algorithm", C.c_int32), ("max_components", C.c_int32), ("catch_tolerance", C.c_double),
+        ("alpha", C.c_double), ("variance_threshold", C.c_double), ("hierarchy_threshold", C.c_double),
+        ("cluster_threshold", C.c_double)]
+
+
+# the keys of a parameter set, in the order of consensus_ragged's / sweep's keywords
+PARAM_KEYS = ("algorithm", "catch_tolerance", "alpha", "max_components", "variance_threshold",
+              "hierarchy_threshold", "cluster_threshold")
+
+
+def round_params(values):
+    """A RoundParams of a full dict over PARAM_KEYS (algorithm by name; cluster_threshold None = the
+    device's per-round rule)."""
+    alg = ALGORITHMS.get(values["algorithm"])
+    if alg is None:
+        raise NotImplementedError("algorithm %r is not on the GPU path" % (values["algorithm"],))
+    ct = values["cluster_threshold"]
+    return RoundParams(alg, int(values["max_components"]), float(values["catch_tolerance"]), float(values["alpha"]),
+                       float(values["variance_threshold"]), float(values["hierarchy_threshold"]),
+                       0.0 if ct is None else float(ct))
+
+
 # simulator studies: the detail metrics, the per-cell statistics and the paired differences
 SIM_NDETAIL = 12                 # PCX_SIM_NDETAIL
 SIM_NVALUES = SIM_NMETRICS + SIM_NDETAIL  # PCX_SIM_NVALUES

@@ -99,6 +99,13 @@ def _declare(lib):
         ("pcx_sim_sweep_stats_host", i32, [C.POINTER(_abi.SimSweep), vp, vp, vp, vp, vp]),
         ("pcx_simulate_study_f64", i32, [vp, C.POINTER(_abi.SimSweep), vp, C.POINTER(_abi.SimResult),
                                          C.POINTER(_abi.SimStudyResult)]),
+        ("pcx_ragged_plan_params", i32, [i64, vp, vp, i64, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64),
+                                         C.POINTER(i64)]),
+        ("pcx_consensus_ragged_params_f64", i32, [vp, C.POINTER(_abi.Ragged), i64, vp, vp,
+                                                  C.POINTER(_abi.BatchResult)]),
+        ("pcx_sim_study_params_check", i32, [C.POINTER(_abi.SimSweep), vp, vp, C.POINTER(i64)]),
+        ("pcx_simulate_study_params_f64", i32, [vp, C.POINTER(_abi.SimSweep), vp, vp, C.POINTER(_abi.SimResult),
+                                                C.POINTER(_abi.SimStudyResult)]),
     ]:
         if (name in ("pcx_batched_lds_bytes", "pcx_medium_lds_bytes", "pcx_batched_route", "pcx_ragged_plan",
                      "pcx_consensus_ragged_f64", "pcx_ragged_plan_wide", "pcx_consensus_ragged_wide_f64",
@@ -106,7 +113,9 @@ def _declare(lib):
                      "pcx_sim_sweep_generate_f64", "pcx_sim_sweep_metrics_f64", "pcx_simulate_sweep_f64",
                      "pcx_sim_detail_f64", "pcx_sim_detail_host", "pcx_sim_sweep_detail_f64",
                      "pcx_sim_sweep_detail_host", "pcx_sim_study_check", "pcx_sim_sweep_stats_f64",
-                     "pcx_sim_sweep_stats_host", "pcx_simulate_study_f64")
+                     "pcx_sim_sweep_stats_host", "pcx_simulate_study_f64", "pcx_ragged_plan_params",
+                     "pcx_consensus_ragged_params_f64", "pcx_sim_study_params_check",
+                     "pcx_simulate_study_params_f64")
                 and os.environ.get("PCX_LIB") and not hasattr(lib, name)):
             continue  # an A/B build of a revision before these queries (tools/ab_build.sh)
         f = getattr(lib, name)

@@ -261,10 +261,49 @@ def ragged_plan(shapes, algorithm="PCA", wide=False):
     return tuple(int(x) for x in totals), int(lds.value)
 
 
+def param_sets(entries, defaults, what):
+    """De-duplicate per-round (or per-cell) parameter dicts into parameter sets: ``entries`` is a
+    sequence of dicts over ``_abi.PARAM_KEYS`` (or None), a missing key takes ``defaults[key]``.
+    Returns (the sets as full dicts, in order of first use; int32 index of each entry's set)."""
+    sets, index, of = [], {}, np.zeros(len(entries), dtype=np.int32)
+    for b, d in enumerate(entries):
+        d = {} if d is None else dict(d)
+        unknown = sorted(set(d) - set(_abi.PARAM_KEYS))
+        if unknown:
+            raise ValueError("%s[%d]: unknown parameter(s) %s (allowed: %s)"
+                             % (what, b, ", ".join(unknown), ", ".join(_abi.PARAM_KEYS)))
+        full = dict(defaults, **d)
+        key = tuple(full[k] for k in _abi.PARAM_KEYS)
+        if key not in index:
+            index[key] = len(sets)
+            sets.append(full)
+        of[b] = index[key]
+    return sets, of
+
+
+def _params_array(sets):
+    return (_abi.RoundParams * max(len(sets), 1))(*[_abi.round_params(q) for q in sets])
+
+
+def ragged_plan_params(shapes, sets, param_of):
+    """(totals, n_launches) of a ragged batch of ``shapes`` whose round b takes ``sets[param_of[b]]``
+    (full dicts over ``_abi.PARAM_KEYS``; pcx_ragged_plan_params, wide limits).  Needs no GPU; raises
+    PcxError naming the first offending round or parameter set."""
+    sh = np.ascontiguousarray(np.asarray(shapes, dtype=np.int32).reshape(-1, 2))
+    n, e = np.ascontiguousarray(sh[:, 0]), np.ascontiguousarray(sh[:, 1])
+    of = np.ascontiguousarray(param_of, dtype=np.int32)
+    arr = _params_array(sets)
+    totals, nl, bad_r, bad_p = (C.c_int64 * 3)(), C.c_int64(0), C.c_int64(-1), C.c_int64(-1)
+    _lib.check(_lib.lib().pcx_ragged_plan_params(len(sh), n.ctypes.data, e.ctypes.data, len(sets),
+                                                 C.cast(arr, C.c_void_p), of.ctypes.data, totals, C.byref(nl),
+                                                 C.byref(bad_r), C.byref(bad_p)))
+    return tuple(int(x) for x in totals), int(nl.value)
+
+
 def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *, catch_tolerance=0.1, alpha=0.1,
                      int_dtype=False, algorithm="PCA", outputs=None, device=None, filled=False, original=False,
                      max_components=5, variance_threshold=0.9, aux_scores=None, hierarchy_threshold=0.5,
-                     cluster_threshold=None, wide=False):
+                     cluster_threshold=None, wide=False, per_round=None):
     """Run B rounds of DIFFERENT shapes in one launch of the one-wave round kernel.
 
     reports:    a sequence of B arrays, round b an (N_b, E_b) matrix with N_b <= 64, E_b <= 32
@@ -276,6 +315,13 @@ def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *,
     reputation: a sequence of B vectors (N_b,) or None (uniform in every round)
     scaled/lo/hi: sequences of B vectors (E_b,) or None (every event binary)
     aux_scores: cokurtosis: a sequence of B vectors (N_b,)
+    per_round:  a sequence of B dicts (or None) over "algorithm", "catch_tolerance", "alpha",
+                "max_components", "variance_threshold", "hierarchy_threshold", "cluster_threshold":
+                round b's own consensus parameters, a missing key taking the call's keyword value
+                (pcx_consensus_ragged_params_f64: still one call, and no more launches for more
+                sets).  Round b equals round b of the same call with its set as the keywords.
+                ``aux_scores`` is needed if some round's algorithm is cokurtosis (an entry of a
+                round that is not may be None).  ``wide=False`` keeps the 64 x 32 limit
     algorithm:  as :func:`consensus_batched` but "k-means" (its code-book size depends on N_b);
                 "big-five" caps max_components at E_b per round, "clusterfeck" takes the reference's
                 log10(E_b)/1.77 cut per round unless cluster_threshold is given
@@ -306,12 +352,30 @@ def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *,
     alg = _abi.ALGORITHMS.get(algorithm)
     if alg is None:
         raise NotImplementedError("algorithm %r is not on the GPU path" % (algorithm,))
+    sets = param_of = None
+    if per_round is not None:
+        if len(per_round) != B:
+            raise ValueError("per_round must hold one entry per round (%d), got %d" % (B, len(per_round)))
+        sets, param_of = param_sets(per_round, dict(
+            algorithm=algorithm, catch_tolerance=catch_tolerance, alpha=alpha, max_components=max_components,
+            variance_threshold=variance_threshold, hierarchy_threshold=hierarchy_threshold,
+            cluster_threshold=cluster_threshold), "per_round")
     aux = None
-    if alg == _abi.ALG_COKURTOSIS:
+    if alg == _abi.ALG_COKURTOSIS if sets is None else any(q["algorithm"] == "cokurtosis" for q in sets):
         if aux_scores is None:
             raise ValueError("cokurtosis needs aux_scores (aux['cokurt'] of every round)")
+        if sets is not None:  # read for the cokurtosis rounds only
+            if len(aux_scores) != B:
+                raise ValueError("aux_scores must hold one vector per round (%d), got %d" % (B, len(aux_scores)))
+            aux_scores = [np.zeros(n) if v is None and sets[param_of[b]]["algorithm"] != "cokurtosis" else v
+                          for b, (v, n) in enumerate(zip(aux_scores, ns))]
         aux = _ragged_vectors(aux_scores, ns, np.float64, "aux_scores")
-    totals = ragged_plan(shapes, algorithm, wide=wide)[0]  # refuses k-means and rounds past the limits, by index
+    if sets is None:
+        totals = ragged_plan(shapes, algorithm, wide=wide)[0]  # refuses k-means and rounds past the limits, by index
+    else:
+        if not wide:
+            ragged_plan(shapes, "PCA", wide=False)  # the one-wave limits, by index
+        totals = ragged_plan_params(shapes, sets, param_of)[0]  # refuses by round or by parameter set
     t = _device.require_gpu()
     dev = t.device(device) if device is not None else t.device("cuda", t.cuda.current_device())
     flat = np.concatenate([m.reshape(-1) for m in mats]) if B else np.zeros(0)
@@ -339,8 +403,14 @@ def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *,
         outs[name] = x
         setattr(res, name, x.data_ptr())
     h = _lib.bind_stream(dev.index, _device.current_stream_handle(dev))
-    entry = _lib.lib().pcx_consensus_ragged_wide_f64 if wide else _lib.lib().pcx_consensus_ragged_f64
-    _lib.check(entry(h, C.byref(inp), C.byref(res)))
+    if sets is None:
+        entry = _lib.lib().pcx_consensus_ragged_wide_f64 if wide else _lib.lib().pcx_consensus_ragged_f64
+        _lib.check(entry(h, C.byref(inp), C.byref(res)))
+    else:
+        arr = _params_array(sets)
+        _lib.check(_lib.lib().pcx_consensus_ragged_params_f64(h, C.byref(inp), len(sets), C.cast(arr, C.c_void_p),
+                                                              param_of.ctypes.data, C.byref(res)))
+        outs["_param_sets"], outs["_param_of"] = sets, param_of
     zero = np.zeros(1, dtype=np.int64)
     outs["_packed"] = buf
     outs["_layout"] = layout

@@ -805,6 +805,216 @@ int pcx_consensus_ragged_wide_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_
     return e == hipSuccess ? PCX_OK : hip_fail(e, "ragged wide launch");
 }
 
+// ---------------------------------------------------------------- per-round parameters
+static_assert(sizeof(pcx_round_params) == sizeof(pcx::RoundParams), "pcx_round_params is the device entry");
+
+// why a parameter set is refused (the words of check_options / sweep_check), or NULL.  sim: a
+// simulator cell's set, where k-means and cokurtosis are not simulated.
+static const char* params_set_refusal(const pcx_round_params& q, bool sim) {
+    if (q.algorithm < PCX_ALG_PCA || q.algorithm > PCX_ALG_CLUSTERFECK)
+        return "algorithm must be an enum pcx_algorithm value (0..7)";
+    if (q.algorithm == PCX_ALG_KMEANS)
+        return sim ? "k-means is not simulated (its code books are drawn on the host)"
+                   : "k-means is not supported (its code-book size depends on each round's N)";
+    if (sim && q.algorithm == PCX_ALG_COKURTOSIS) return "cokurtosis is not simulated (it needs the caller's scores)";
+    // (max_components is capped at E_b per round on the device)
+    if (q.algorithm == PCX_ALG_BIG_FIVE && q.max_components < 1) return "big-five needs max_components >= 1";
+    if (q.algorithm == PCX_ALG_HIERARCHICAL && std::isnan(q.hierarchy_threshold)) return "hierarchy_threshold is NaN";
+    if (q.algorithm == PCX_ALG_FIXED_VARIANCE && !std::isfinite(q.variance_threshold))
+        return "variance_threshold must be finite";
+    if (!std::isfinite(q.catch_tolerance) || !std::isfinite(q.alpha)) return "catch_tolerance/alpha must be finite";
+    return nullptr;
+}
+
+// The launches of a call with per-round parameters: nine segments of one descriptor table
+// (MediumDesc, every round's), each one launch (the workgroup ones times the scratch chunks).
+// 0..2: the one-wave kernel's instantiation groups (pcx::params_wave_group); 3..5: the workgroup
+// kernel's plain instantiation, launch classes 3, 2, 1; 6..8: its CLUS instantiation likewise.
+constexpr int PARAMS_SEGMENTS = 9;
+static int params_segment(int N, int E, int algorithm) {
+    if (N <= 64 && E <= 32) return pcx::params_wave_group(algorithm);
+    const int k = pcx::medium_launch_class(pcx::medium_lds_bytes(N, E, algorithm));
+    return 3 + (algorithm >= PCX_ALG_KMEANS ? 3 : 0) + (3 - k);
+}
+
+// a round's segment and dynamic LDS, remembered over a run of equal rounds (a simulator cell's: the
+// host passes over a sweep's 10^4..10^5 rounds lie between the call and its first launch)
+struct SegmentOf {
+    int N = 0, E = 0, alg = -1, seg = 0;
+    int64_t lds = 0;
+    bool fresh = false;  // the last at() computed (a new run)
+    int at(int n, int e, int a) {
+        fresh = n != N || e != E || a != alg;
+        if (fresh) {
+            N = n, E = e, alg = a;
+            seg = params_segment(n, e, a);
+            lds = (int64_t)(seg < 3 ? pcx::ragged_lds_bytes(n, e, a) : pcx::medium_lds_bytes(n, e, a));
+        }
+        return seg;
+    }
+};
+
+struct ParamsPlan {
+    pcx_ctx::RaggedSlot* slot = nullptr;
+    int64_t B = 0, P = 0, nm = 0, chunk = 0;
+    int64_t cnt[PARAMS_SEGMENTS] = {}, lds[PARAMS_SEGMENTS] = {}, first[PARAMS_SEGMENTS] = {};
+    int64_t stride[3] = {0, 0, 0};
+    // slot offsets: the parameter table, the caller's `extra` bytes; `bytes` are uploaded
+    size_t off_p = 0, off_x = 0, bytes = 0;
+    bool filled = false;
+};
+
+// a segment's count and dynamic LDS (the largest round's own, by its own algorithm) and the
+// workgroup rounds' slot strides, of rounds that the caller has checked
+static void params_count(int64_t B, const int32_t* n_reporters, const int32_t* n_events, const pcx_round_params* params,
+                         const int32_t* param_of, ParamsPlan* plan) {
+    ParamsPlan& p = *plan;
+    p.B = B;
+    SegmentOf run;
+    for (int64_t b = 0; b < B; b++) {
+        const int N = n_reporters[b], E = n_events[b], alg = params[param_of[b]].algorithm;
+        const int s = run.at(N, E, alg);
+        p.cnt[s]++;
+        if (s >= 3) p.nm++;
+        if (!run.fresh) continue;
+        p.lds[s] = std::max(p.lds[s], run.lds);
+        if (s >= 3) pcx::medium_slot_strides(N, E, alg, p.stride);
+    }
+    for (int s = 1; s < PARAMS_SEGMENTS; s++) p.first[s] = p.first[s - 1] + p.cnt[s - 1];
+}
+
+static int params_plan_check(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
+                             const pcx_round_params* params, const int32_t* param_of, int64_t totals[3],
+                             int64_t* bad_round, int64_t* bad_param) {
+    if (bad_round) *bad_round = -1;
+    if (bad_param) *bad_param = -1;
+    if (n_rounds < 0 || n_rounds > 0x7fffffff) return fail(PCX_EINVAL, "ragged: n_rounds must be in [0, 2^31)");
+    if (n_rounds > 0 && (!n_reporters || !n_events)) return fail(PCX_EINVAL, "ragged: n_reporters / n_events is NULL");
+    if (n_rounds > 0 && n_params < 1) return fail(PCX_EINVAL, "ragged: n_params must be >= 1 (a parameter set per round)");
+    if (n_params > 0x7fffffff) return fail(PCX_EINVAL, "ragged: n_params must be below 2^31");
+    if (n_params > 0 && !params) return fail(PCX_EINVAL, "ragged: params is NULL");
+    if (n_rounds > 0 && !param_of) return fail(PCX_EINVAL, "ragged: param_of is NULL");
+    for (int64_t q = 0; q < n_params; q++)
+        if (const char* why = params_set_refusal(params[q], false)) {
+            if (bad_param) *bad_param = q;
+            return fail(PCX_EINVAL, "ragged: parameter set " + std::to_string(q) + ": " + why);
+        }
+    int64_t tot[3] = {0, 0, 0};
+    for (int64_t b = 0; b < n_rounds; b++) {
+        const int32_t N = n_reporters[b], E = n_events[b];
+        if (N < 1 || N > 256 || E < 1 || E > 64) return ragged_bad_round(b, N, E, 256, 64, bad_round);
+        if (param_of[b] < 0 || param_of[b] >= n_params) {
+            if (bad_round) *bad_round = b;
+            return fail(PCX_EINVAL, "ragged: round " + std::to_string(b) + " has param_of " + std::to_string(param_of[b]) +
+                                        ", outside [0, " + std::to_string(n_params) + ")");
+        }
+        tot[0] += N;
+        tot[1] += E;
+        tot[2] += (int64_t)N * E;
+    }
+    for (int k = 0; k < 3 && totals; k++) totals[k] = tot[k];
+    return PCX_OK;
+}
+
+int pcx_ragged_plan_params(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
+                           const pcx_round_params* params, const int32_t* param_of, int64_t totals[3],
+                           int64_t* n_launches, int64_t* bad_round, int64_t* bad_param) {
+    if (const int rc = params_plan_check(n_rounds, n_reporters, n_events, n_params, params, param_of, totals, bad_round,
+                                         bad_param))
+        return rc;
+    if (n_launches) {
+        ParamsPlan p;
+        params_count(n_rounds, n_reporters, n_events, params, param_of, &p);
+        *n_launches = 0;
+        for (int s = 0; s < PARAMS_SEGMENTS; s++) *n_launches += p.cnt[s] > 0;
+    }
+    return PCX_OK;
+}
+
+// A counted plan's tables into a staging slot taken here: every round's descriptor, segment after
+// segment (a segment's rounds in their order), then the P parameter entries, then `extra` bytes (a
+// multiple of 8) of the caller's at off_x; the workgroup scratch reserved.  One slot, one upload.
+static int params_tables(pcx_ctx* ctx, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
+                         const pcx_round_params* params, const int32_t* param_of, bool filled, size_t extra,
+                         ParamsPlan* plan) {
+    ParamsPlan& p = *plan;
+    p.P = n_params;
+    p.filled = filled;
+    p.off_p = (size_t)p.B * sizeof(pcx::MediumDesc);
+    p.off_x = p.off_p + (size_t)n_params * sizeof(pcx::RoundParams);
+    p.bytes = p.off_x + extra;
+    if (const int rc = ragged_slot_take(ctx, p.bytes, &p.slot)) return rc;
+    char* pin = static_cast<char*>(p.slot->pin);
+    pcx::MediumDesc* d = reinterpret_cast<pcx::MediumDesc*>(pin);
+    int64_t at[PARAMS_SEGMENTS];
+    for (int s = 0; s < PARAMS_SEGMENTS; s++) at[s] = p.first[s];
+    int64_t cell = 0, row = 0, ev = 0;
+    SegmentOf run;
+    for (int64_t b = 0; b < p.B; b++) {
+        const int32_t N = n_reporters[b], E = n_events[b];
+        const int s = run.at(N, E, params[param_of[b]].algorithm);
+        d[at[s]++] = pcx::MediumDesc{cell, row, ev, N, E, (int32_t)b, param_of[b]};
+        cell += (int64_t)N * E;
+        row += N;
+        ev += E;
+    }
+    std::memcpy(pin + p.off_p, params, (size_t)n_params * sizeof(pcx::RoundParams));
+    if (p.nm == 0) return PCX_OK;
+    // the workgroup scratch: slot strides of the call's largest round, chunks that fit the cap
+    const size_t cap = ctx->test_scratch_cap > 0 ? (size_t)ctx->test_scratch_cap : MEDIUM_SCRATCH_CAP;
+    const size_t per = (size_t)((filled ? 0 : p.stride[0]) + p.stride[1] + p.stride[2]) * sizeof(double);
+    p.chunk = std::min<int64_t>(std::max<int64_t>((int64_t)(cap / per), 1), p.nm);
+    return medium_scratch_reserve(ctx, per * (size_t)p.chunk);
+}
+
+// the launches over uploaded tables, with these inputs and outputs (a's parameter fields are not read)
+static hipError_t params_launch(pcx_ctx* ctx, const ParamsPlan& p, const pcx::BatchArgs& a) {
+    char* dev = static_cast<char*>(p.slot->dev);
+    const pcx::MediumDesc* d = reinterpret_cast<const pcx::MediumDesc*>(dev);
+    const pcx::RoundParams* tab = reinterpret_cast<const pcx::RoundParams*>(dev + p.off_p);
+    hipError_t e = hipSuccess;
+    for (int g = 0; g < 3 && e == hipSuccess; g++)
+        e = pcx::launch_ragged_params(a, d + p.first[g], tab, p.cnt[g], g, (size_t)p.lds[g], ctx->stream);
+    if (p.nm == 0) return e;
+    double* Fscr = (double*)ctx->mscr;
+    double* Cscr = Fscr + (p.filled ? 0 : (size_t)p.chunk * p.stride[0]);
+    double* Xscr = Cscr + (size_t)p.chunk * p.stride[1];
+    for (int s = 3; s < PARAMS_SEGMENTS && e == hipSuccess; s++)
+        for (int64_t b0 = 0; b0 < p.cnt[s] && e == hipSuccess; b0 += p.chunk)
+            e = pcx::launch_ragged_medium_params(a, d + p.first[s] + b0, tab, std::min<int64_t>(p.chunk, p.cnt[s] - b0),
+                                                 s >= 6, (size_t)p.lds[s], p.stride, Fscr, Cscr, Xscr, ctx->stream);
+    return e;
+}
+
+int pcx_consensus_ragged_params_f64(pcx_ctx* ctx, const pcx_ragged* in, int64_t n_params,
+                                    const pcx_round_params* params, const int32_t* param_of, pcx_batch_result* out) {
+    if (!ctx || !in || !out) return fail(PCX_EINVAL, "pcx_consensus_ragged_params_f64: null argument");
+    if (const int rc = params_plan_check(in->n_rounds, in->n_reporters, in->n_events, n_params, params, param_of,
+                                         nullptr, nullptr, nullptr))
+        return rc;
+    if (in->n_rounds == 0) return PCX_OK;
+    if (!in->reports) return fail(PCX_EINVAL, "ragged: reports is NULL");
+    if (in->scaled && (!in->lo || !in->hi)) return fail(PCX_EINVAL, "ragged: scaled given without lo/hi");
+    for (int64_t b = 0; b < in->n_rounds && !in->aux_scores; b++)
+        if (params[param_of[b]].algorithm == PCX_ALG_COKURTOSIS)
+            return fail(PCX_EINVAL, "ragged: parameter set " + std::to_string(param_of[b]) +
+                                        ": cokurtosis needs aux_scores (aux[\"cokurt\"])");
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    ParamsPlan p;
+    params_count(in->n_rounds, in->n_reporters, in->n_events, params, param_of, &p);
+    if (const int rc = params_tables(ctx, in->n_reporters, in->n_events, n_params, params, param_of,
+                                     out->filled != nullptr, 0, &p))
+        return rc;
+    e = ragged_slot_upload(ctx, *p.slot, p.bytes);
+    if (e != hipSuccess) return hip_fail(e, "ragged: descriptor upload");
+    pcx::BatchArgs a = shared_args(in, out);
+    a.B = in->n_rounds;
+    e = params_launch(ctx, p, a);
+    if (e == hipSuccess) e = hipEventRecord(p.slot->kern_ev, ctx->stream);
+    return e == hipSuccess ? PCX_OK : hip_fail(e, "ragged params launch");
+}
+
 namespace {
 // pcx_create_devices context: shard the host matrix's rows over the devices, one
 // worker thread per device running the rank's consensus (collective over the ranks)
@@ -1209,8 +1419,10 @@ int sweep_fail(int64_t* bad_cell, int64_t c, const char* who, const std::string&
 
 // The checks every sweep entry shares (pure): the shared parameters as sim_check checks them
 // (*bad_cell = -1), then cell after cell.  Fills what pcx_sim_sweep_plan reports; 0 = ok.
+// cp: per-cell parameter sets [C] (NULL: the shared parameters) -- the shared ones are then neither
+// read nor checked, each cell's set is checked with the cell, and its rounds count by its algorithm.
 int sweep_check(const pcx_sim_sweep* s, const char* who, int64_t totals[4], int64_t counts[4], int64_t lds_bytes[4],
-                int64_t* bad_cell) {
+                int64_t* bad_cell, const pcx_round_params* cp = nullptr) {
     if (bad_cell) *bad_cell = -1;
     if (s->n_cells < 0) return sweep_fail(bad_cell, -1, who, "n_cells must be >= 0");
     if (s->n_cells > 0 && !s->cells) return sweep_fail(bad_cell, -1, who, "cells is NULL");
@@ -1218,20 +1430,22 @@ int sweep_check(const pcx_sim_sweep* s, const char* who, int64_t totals[4], int6
         return sweep_fail(bad_cell, -1, who, "n_timesteps must be in [1, 2^24)");
     if (!(s->scaled_tol >= 0.0) || !std::isfinite(s->scaled_tol))
         return sweep_fail(bad_cell, -1, who, "scaled_tol must be finite and >= 0");
-    if (s->algorithm < PCX_ALG_PCA || s->algorithm > PCX_ALG_CLUSTERFECK)
+    if (cp) {
+        // (each cell's own set, below)
+    } else if (s->algorithm < PCX_ALG_PCA || s->algorithm > PCX_ALG_CLUSTERFECK)
         return sweep_fail(bad_cell, -1, who, "algorithm must be an enum pcx_algorithm value (0..7)");
-    if (s->algorithm == PCX_ALG_KMEANS)
+    else if (s->algorithm == PCX_ALG_KMEANS)
         return sweep_fail(bad_cell, -1, who, "k-means is not simulated (its code books are drawn on the host)");
-    if (s->algorithm == PCX_ALG_COKURTOSIS)
+    else if (s->algorithm == PCX_ALG_COKURTOSIS)
         return sweep_fail(bad_cell, -1, who, "cokurtosis is not simulated (it needs the caller's scores)");
-    if (s->algorithm == PCX_ALG_HIERARCHICAL && std::isnan(s->hierarchy_threshold))
+    else if (s->algorithm == PCX_ALG_HIERARCHICAL && std::isnan(s->hierarchy_threshold))
         return sweep_fail(bad_cell, -1, who, "hierarchy_threshold is NaN");
     // (max_components is capped at E_c per round on the device)
-    if (s->algorithm == PCX_ALG_BIG_FIVE && s->max_components < 1)
+    else if (s->algorithm == PCX_ALG_BIG_FIVE && s->max_components < 1)
         return sweep_fail(bad_cell, -1, who, "big-five needs max_components >= 1");
-    if (s->algorithm == PCX_ALG_FIXED_VARIANCE && !std::isfinite(s->variance_threshold))
+    else if (s->algorithm == PCX_ALG_FIXED_VARIANCE && !std::isfinite(s->variance_threshold))
         return sweep_fail(bad_cell, -1, who, "variance_threshold must be finite");
-    if (!std::isfinite(s->catch_tolerance) || !std::isfinite(s->alpha))
+    else if (!std::isfinite(s->catch_tolerance) || !std::isfinite(s->alpha))
         return sweep_fail(bad_cell, -1, who, "catch_tolerance/alpha must be finite");
     int64_t tot[4] = {0, 0, 0, 0}, cnt[4] = {0, 0, 0, 0};
     size_t lds[4] = {0, 0, 0, 0};
@@ -1251,6 +1465,9 @@ int sweep_check(const pcx_sim_sweep* s, const char* who, int64_t totals[4], int6
         for (const auto& q : probs)
             if (!(q.p >= 0.0 && q.p <= 1.0))  // false for NaN too
                 return sweep_fail(bad_cell, c, who, std::string(q.name) + " must be a probability in [0, 1]");
+        if (cp)
+            if (const char* why = params_set_refusal(cp[c], true)) return sweep_fail(bad_cell, c, who, why);
+        const int algorithm = cp ? cp[c].algorithm : s->algorithm;
         const int64_t R = k.n_rounds, N = k.n_reporters, E = k.n_events;
         tot[0] += R;
         if (tot[0] > 0x7fffffff)
@@ -1258,10 +1475,10 @@ int sweep_check(const pcx_sim_sweep* s, const char* who, int64_t totals[4], int6
         tot[1] += R * N;
         tot[2] += R * E;
         tot[3] += R * N * E;
-        const int slot = wide_slot((int)N, (int)E, s->algorithm, false);
+        const int slot = wide_slot((int)N, (int)E, algorithm, false);
         cnt[slot] += R;
-        lds[slot] = std::max(lds[slot], slot ? pcx::medium_lds_bytes((int)N, (int)E, s->algorithm)
-                                             : pcx::ragged_lds_bytes((int)N, (int)E, s->algorithm));
+        lds[slot] = std::max(lds[slot], slot ? pcx::medium_lds_bytes((int)N, (int)E, algorithm)
+                                             : pcx::ragged_lds_bytes((int)N, (int)E, algorithm));
     }
     for (int k = 0; k < 4 && totals; k++) totals[k] = tot[k];
     for (int k = 0; k < 4 && counts; k++) counts[k] = cnt[k];
@@ -1400,14 +1617,16 @@ static int study_check(const pcx_sim_sweep* s, const int32_t* pair_base, const c
     return PCX_OK;
 }
 
-// The loop of pcx_simulate_sweep_f64 and pcx_simulate_study_f64 (`who`).  study NULL: the sweep.
-// Otherwise every timestep's metrics launch is followed by the detail launch, and one statistics
-// launch follows the last timestep.
+// The loop of pcx_simulate_sweep_f64, pcx_simulate_study_f64 and pcx_simulate_study_params_f64
+// (`who`).  study NULL: the sweep.  Otherwise every timestep's metrics launch is followed by the
+// detail launch, and one statistics launch follows the last timestep.  cp: per-cell parameter sets
+// [C] (NULL: the sweep's shared ones) -- the consensus launches are then those of
+// pcx_consensus_ragged_params_f64, round b of cell c on set c.
 static int sweep_run(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* res, const int32_t* pair_base,
-                     const pcx_sim_study_result* study, const char* who) {
+                     const pcx_sim_study_result* study, const char* who, const pcx_round_params* cp = nullptr) {
     const std::string name(who);
     int64_t tot[4], cnt[4], lds[4];
-    if (const int rc = sweep_check(sweep, who, tot, cnt, lds, nullptr)) return rc;
+    if (const int rc = sweep_check(sweep, who, tot, cnt, lds, nullptr, cp)) return rc;
     if (study) {
         if (const int rc = study_check(sweep, pair_base, who, nullptr)) return rc;
         if (study->paired && !pair_base) return fail(PCX_EINVAL, name + ": paired needs pair_base");
@@ -1420,16 +1639,18 @@ static int sweep_run(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* r
     // the cells expanded into the wide ragged call's per-round shapes
     std::vector<int32_t> shape;
     try {
-        shape.resize((size_t)B * 2);
+        shape.resize((size_t)B * (cp ? 3 : 2));
     } catch (const std::bad_alloc&) {
         return fail(PCX_ENOMEM, name + ": no host memory for the per-round shapes");
     }
     int32_t* nrep = shape.data();
     int32_t* nev = nrep + B;
+    int32_t* pof = cp ? nev + B : nullptr;  // round b's parameter set: its cell
     for (int64_t c = 0, b = 0; c < C; c++)
         for (int64_t r = 0; r < sweep->cells[c].n_rounds; r++, b++) {
             nrep[b] = sweep->cells[c].n_reporters;
             nev[b] = sweep->cells[c].n_events;
+            if (pof) pof[b] = (int32_t)c;
         }
     // work buffers, pcx_simulate_f64's layout over the flat arrays
     const size_t bn = (size_t)tot[1], be = (size_t)tot[2], bne = (size_t)tot[3];
@@ -1461,19 +1682,26 @@ static int sweep_run(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* r
     // every table of the call in one staging slot, uploaded once: the wide ragged call's descriptors
     // (the same every timestep: only the data pointers change), then the sweep's own
     WidePlan plan;
+    ParamsPlan pplan;
     const bool pairs = study && study->paired;
-    if (const int rc = wide_tables(ctx, B, nrep, nev, sweep->algorithm, false, cnt, lds, false,
-                                   sweep_table_bytes(sweep) + (pairs ? pair_base_bytes(sweep) : 0), &plan))
+    const size_t extra = sweep_table_bytes(sweep) + (pairs ? pair_base_bytes(sweep) : 0);
+    if (cp) {
+        params_count(B, nrep, nev, cp, pof, &pplan);
+        if (const int rc = params_tables(ctx, nrep, nev, C, cp, pof, false, extra, &pplan)) return rc;
+    } else if (const int rc = wide_tables(ctx, B, nrep, nev, sweep->algorithm, false, cnt, lds, false, extra, &plan)) {
         return rc;
-    const pcx::SweepTables tab = sweep_tables_fill(sweep, static_cast<char*>(plan.slot->pin) + plan.off_x,
-                                                   static_cast<char*>(plan.slot->dev) + plan.off_x);
+    }
+    pcx_ctx::RaggedSlot* const slot = cp ? pplan.slot : plan.slot;
+    const size_t off_x = cp ? pplan.off_x : plan.off_x, up_bytes = cp ? pplan.bytes : plan.bytes;
+    const pcx::SweepTables tab = sweep_tables_fill(sweep, static_cast<char*>(slot->pin) + off_x,
+                                                   static_cast<char*>(slot->dev) + off_x);
     const int32_t* dev_base = nullptr;  // pair_base rides behind the sweep's tables
     if (pairs) {
-        const size_t at = plan.off_x + sweep_table_bytes(sweep);
-        std::memcpy(static_cast<char*>(plan.slot->pin) + at, pair_base, (size_t)C * sizeof(int32_t));
-        dev_base = reinterpret_cast<const int32_t*>(static_cast<char*>(plan.slot->dev) + at);
+        const size_t at = off_x + sweep_table_bytes(sweep);
+        std::memcpy(static_cast<char*>(slot->pin) + at, pair_base, (size_t)C * sizeof(int32_t));
+        dev_base = reinterpret_cast<const int32_t*>(static_cast<char*>(slot->dev) + at);
     }
-    e = ragged_slot_upload(ctx, *plan.slot, plan.bytes);
+    e = ragged_slot_upload(ctx, *slot, up_bytes);
     if (e != hipSuccess) return hip_fail(e, "sweep: table upload");
     const double* rep = sweep->reputation0;
     for (int64_t t = 0; t < T; t++) {  // launches only: no host wait in this loop
@@ -1511,7 +1739,7 @@ static int sweep_run(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* r
         in.cluster_threshold = sweep->cluster_threshold;
         pcx::BatchArgs a = shared_args(&in, &o);
         a.B = B;
-        e = wide_launch(ctx, plan, a);
+        e = cp ? params_launch(ctx, pplan, a) : wide_launch(ctx, plan, a);
         if (e != hipSuccess) return hip_fail(e, "sweep: ragged wide launch");
         if (res->metrics || res->summary || study) {
             double* m = res->metrics   ? res->metrics + (size_t)t * B * PCX_SIM_NMETRICS
@@ -1536,7 +1764,7 @@ static int sweep_run(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* r
                                         study->stats, pairs ? study->paired : nullptr, ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "k_sim_study_stats launch");
     }
-    e = hipEventRecord(plan.slot->kern_ev, ctx->stream);
+    e = hipEventRecord(slot->kern_ev, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "sweep: hipEventRecord");
     if (res->reputation && bn) {
         e = hipMemcpyAsync(res->reputation, rep, bn * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
@@ -1555,6 +1783,22 @@ int pcx_simulate_study_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const int32
                            pcx_sim_study_result* study) {
     if (!ctx || !sweep || !res || !study) return fail(PCX_EINVAL, "pcx_simulate_study_f64: null argument");
     return sweep_run(ctx, sweep, res, pair_base, study, "pcx_simulate_study_f64");
+}
+
+int pcx_sim_study_params_check(const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,
+                               const int32_t* pair_base, int64_t* bad_cell) {
+    if (!sweep) return fail(PCX_EINVAL, "pcx_sim_study_params_check: null argument");
+    if (const int rc = sweep_check(sweep, "pcx_sim_study_params_check", nullptr, nullptr, nullptr, bad_cell, cell_params))
+        return rc;
+    return study_check(sweep, pair_base, "pcx_sim_study_params_check", bad_cell);
+}
+
+int pcx_simulate_study_params_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,
+                                  const int32_t* pair_base, pcx_sim_result* res, pcx_sim_study_result* study) {
+    if (!ctx || !sweep || !res) return fail(PCX_EINVAL, "pcx_simulate_study_params_f64: null argument");
+    if (!cell_params)  // the existing entries, the same bytes
+        return study ? pcx_simulate_study_f64(ctx, sweep, pair_base, res, study) : pcx_simulate_sweep_f64(ctx, sweep, res);
+    return sweep_run(ctx, sweep, res, study ? pair_base : nullptr, study, "pcx_simulate_study_params_f64", cell_params);
 }
 
 int pcx_sim_study_check(const pcx_sim_sweep* sweep, const int32_t* pair_base, int64_t* bad_cell) {

@@ -1557,6 +1557,9 @@ __device__ __forceinline__ int64_t uniform64(int64_t v) {
     return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
+// (pcx_batched_params.hip includes this file for the helpers above alone: the per-round-parameter
+// kernel is a translation unit of its own, so that this unit's kernels keep the code they have)
+#ifndef PCX_BATCHED_HELPERS_ONLY
 // the round kernel, under its two names (see pcx_batched_round.inc)
 #define PCX_ROUND_RAGGED 0
 #include "pcx_batched_round.inc"
@@ -1635,5 +1638,6 @@ hipError_t launch_ragged(const BatchArgs& a, const RaggedDesc* desc, size_t lds,
     }
     return hipGetLastError();
 }
+#endif  // PCX_BATCHED_HELPERS_ONLY
 
 }  // namespace pcx

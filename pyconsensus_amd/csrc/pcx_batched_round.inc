@@ -1,6 +1,7 @@
 // pcx_batched_round.inc -- the round kernel's text, included twice by pcx_batched.hip: as
 // batched_round_kernel (PCX_ROUND_RAGGED 0: B rounds of one shape) and as ragged_round_kernel
-// (PCX_ROUND_RAGGED 1: a shape per round).  One text under two kernel names keeps the equal-shape
+// (PCX_ROUND_RAGGED 1: a shape per round), and once by pcx_batched_params.hip (PCX_ROUND_RAGGED 2,
+// below).  One text under two kernel names keeps the equal-shape
 // instantiations' code exactly what it was (a shared __device__ body, inlined, compiled the 50 x 20
 // kernels to different register and scratch counts), and the two cannot drift apart.
 //
@@ -15,10 +16,42 @@
 // (readfirstlane), so the loop bounds and branches on N and E stay on the scalar unit as they do for
 // the kernel arguments.  The round carves its LDS from its own N, E and ES = E | 1 and never reaches
 // past that carve; the launch allocates the largest round's.  The [B] outputs stay at b.
-#if PCX_ROUND_RAGGED
+//
+// Per-round parameters (PCX_ROUND_RAGGED 2, pcx_batched_params.hip: ragged_params_round_kernel,
+// DESIGN.md 5.4.3): the ragged form over MediumDesc, whose `param` picks the round's entry of a
+// device table RoundParams[P] and whose `round` is where the six [B] outputs go (a launch holds the
+// rounds of one instantiation group, in any subset and order).  The entry is wave-uniform like the
+// descriptor: read once, held in scalar registers, written over the seven parameter fields of a
+// local copy `a` of the kernel argument `ka`, which the text below reads as it reads the argument in
+// the other two forms.  (out_args() still reads the output pointers from the argument itself.)
+#if PCX_ROUND_RAGGED == 2
 #define PCX_ROUND_CELL0 rcell
 #define PCX_ROUND_ROW0 rrow
 #define PCX_ROUND_EV0 rev
+#define PCX_ROUND_B rround
+template <int NT, int ET, bool CLUS, bool PK>
+__global__ void __launch_bounds__(64, 3) ragged_params_round_kernel(BatchArgs ka, const MediumDesc* __restrict__ rag,
+                                                                    const RoundParams* __restrict__ ptab) {
+    static_assert(NT == 0 && ET == 0, "a ragged launch has no compiled shape");
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const MediumDesc* const rd = rag + blockIdx.x;
+    const int N = __builtin_amdgcn_readfirstlane(rd->N), E = __builtin_amdgcn_readfirstlane(rd->E), ES = E | 1;
+    const int64_t rcell = uniform64(rd->cell), rrow = uniform64(rd->row), rev = uniform64(rd->ev);
+    const int64_t rround = __builtin_amdgcn_readfirstlane(rd->round);
+    const RoundParams* const rp = ptab + __builtin_amdgcn_readfirstlane(rd->param);
+    BatchArgs a = ka;
+    a.algorithm = __builtin_amdgcn_readfirstlane(rp->algorithm);
+    a.max_components = __builtin_amdgcn_readfirstlane(rp->max_components);
+    a.catch_tol = uniform_f64(rp->catch_tol);
+    a.alpha = uniform_f64(rp->alpha);
+    a.variance_threshold = uniform_f64(rp->variance_threshold);
+    a.hierarchy_threshold = uniform_f64(rp->hierarchy_threshold);
+    a.cluster_threshold = uniform_f64(rp->cluster_threshold);
+#elif PCX_ROUND_RAGGED
+#define PCX_ROUND_CELL0 rcell
+#define PCX_ROUND_ROW0 rrow
+#define PCX_ROUND_EV0 rev
+#define PCX_ROUND_B blockIdx.x
 template <int NT, int ET, bool CLUS, bool PK>
 __global__ void __launch_bounds__(64, 3) ragged_round_kernel(BatchArgs a, const RaggedDesc* __restrict__ rag) {
     static_assert(NT == 0 && ET == 0, "a ragged launch has no compiled shape");
@@ -30,13 +63,14 @@ __global__ void __launch_bounds__(64, 3) ragged_round_kernel(BatchArgs a, const 
 #define PCX_ROUND_CELL0 (b * (int64_t)N * E)
 #define PCX_ROUND_ROW0 (b * N)
 #define PCX_ROUND_EV0 (b * E)
+#define PCX_ROUND_B blockIdx.x
 template <int NT, int ET, bool CLUS, bool PK>
 __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched_round_kernel(BatchArgs a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int N = NT > 0 ? NT : a.N, E = ET > 0 ? ET : a.E, ES = ET > 0 ? compiled_es(ET) : a.ES;
 #endif
     const int l = lane_id();
-    const int64_t b = blockIdx.x;
+    const int64_t b = PCX_ROUND_B;
     constexpr int NRM = NT > 0 ? NT : 64;  // median scratch rows
     Smem S = carve(smem, N, E, ES, NRM, PK);
     const bool row = l < N, col = l < E;
@@ -856,3 +890,4 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
 #undef PCX_ROUND_CELL0
 #undef PCX_ROUND_ROW0
 #undef PCX_ROUND_EV0
+#undef PCX_ROUND_B

@@ -242,7 +242,7 @@ struct MediumDesc {
     int64_t cell, row, ev;
     int32_t N, E;
     int32_t round;
-    int32_t pad_;
+    int32_t param;  // the round's entry of RoundParams[P] (the per-round-parameter kernels; else 0, unread)
 };
 static_assert(sizeof(MediumDesc) == 40, "ragged workgroup descriptor");
 // static LDS of the workgroup kernel's four instantiations (sh, scal, the scaled-event list, the
@@ -274,6 +274,27 @@ inline WaveTmp ragged_wave_tmp(void* base, int64_t n) {
     return t;
 }
 hipError_t launch_ragged_scatter(const BatchArgs& a, const int32_t* idx, int64_t n, void* tmp, hipStream_t st);
+
+// Per-round consensus parameters (pcx_consensus_ragged_params_f64, pcx_simulate_study_params_f64;
+// DESIGN.md 5.4.3): one entry of the device table a round's MediumDesc::param indexes -- the layout of
+// the public pcx_round_params.  Both ragged kernels have a form that reads it in place of the seven
+// parameter fields of BatchArgs (ragged_params_round_kernel, ragged_params_medium_kernel).
+struct RoundParams {
+    int32_t algorithm, max_components;
+    double catch_tol, alpha, variance_threshold, hierarchy_threshold, cluster_threshold;
+};
+static_assert(sizeof(RoundParams) == 48, "per-round parameter entry");
+// the one-wave kernel's instantiation group of an algorithm: 0 packed (PCA, absolute, cokurtosis),
+// 1 eigen (big-five, fixed-variance), 2 clustering (hierarchical, clusterfeck)
+inline int params_wave_group(int algorithm) { return algorithm >= 5 ? 2 : (algorithm == 2 || algorithm == 3) ? 1 : 0; }
+// `nb` one-wave rounds desc[0 .. nb) of one group, every [B] output written at the round's index;
+// lds = the largest ragged_lds_bytes(N_b, E_b, algorithm_b)
+hipError_t launch_ragged_params(const BatchArgs& a, const MediumDesc* desc, const RoundParams* params, int64_t nb,
+                                int group, size_t lds, hipStream_t st);
+// launch_ragged_medium with the table; clus: the launch holds clustering rounds (the CLUS instantiation)
+hipError_t launch_ragged_medium_params(const BatchArgs& a, const MediumDesc* desc, const RoundParams* params, int64_t nb,
+                                       bool clus, size_t lds, const int64_t s[3], double* Fscr, double* Cscr,
+                                       double* Xscr, hipStream_t st);
 
 // ---------------------------------------------------------------- Monte Carlo simulator (pcx_sim.hip)
 // one timestep's rounds on the device / on the host (the same inline generator, pcx_sim.h)

@@ -16,6 +16,12 @@
 //
 // CLUS: the instantiation that also holds the clusterings (their code and registers stay out of
 // the other one); Xscr is their per-round N x E scratch
+//
+// Per-round parameters (PCX_MEDIUM_RAGGED 2, pcx_medium_params.hip: ragged_params_medium_kernel,
+// DESIGN.md 5.4.3): the ragged form with the round's entry rag[blockIdx.x].param of a device table
+// RoundParams[P] written over the seven parameter fields of a local copy `a` of the kernel argument
+// `ka` (workgroup-uniform, scalar registers, like the descriptor).  Everything below reads `a`: the
+// LDS carve, the work region, the scratch slots and the layout follow the round's own algorithm.
 #if PCX_MEDIUM_RAGGED
 #define PCX_MROUND_CELL0 rcell
 #define PCX_MROUND_ROW0 rrow
@@ -26,9 +32,15 @@
 #define PCX_MROUND_XSLOT ((int64_t)blockIdx.x * sX)
 #define PCX_MROUND_ARGS ar
 template <bool CLUS>
+#if PCX_MEDIUM_RAGGED == 2
+__global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) ragged_params_medium_kernel(
+    BatchArgs ka, const MediumDesc* __restrict__ rag, const RoundParams* __restrict__ ptab, int64_t sF, int64_t sC,
+    int64_t sX, double* Fscr, double* Cscr, double* Xscr) {
+#else
 __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) ragged_medium_kernel(BatchArgs a, const MediumDesc* __restrict__ rag,
                                                                              int64_t sF, int64_t sC, int64_t sX,
                                                                              double* Fscr, double* Cscr, double* Xscr) {
+#endif
     extern __shared__ __attribute__((aligned(16))) double mlds[];
     __shared__ double sh[MT];
     __shared__ double scal[16];
@@ -36,6 +48,17 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) ragged_medium_kernel(Bat
     const int N = __builtin_amdgcn_readfirstlane(rd->N), E = __builtin_amdgcn_readfirstlane(rd->E), ES = E + 1;
     const int64_t b = __builtin_amdgcn_readfirstlane(rd->round);  // round; scratch slot blockIdx.x
     const int64_t rcell = muniform64(rd->cell), rrow = muniform64(rd->row), rev = muniform64(rd->ev);
+#if PCX_MEDIUM_RAGGED == 2
+    const RoundParams* const rp = ptab + __builtin_amdgcn_readfirstlane(rd->param);
+    BatchArgs a = ka;
+    a.algorithm = __builtin_amdgcn_readfirstlane(rp->algorithm);
+    a.max_components = __builtin_amdgcn_readfirstlane(rp->max_components);
+    a.catch_tol = muniform_f64(rp->catch_tol);
+    a.alpha = muniform_f64(rp->alpha);
+    a.variance_threshold = muniform_f64(rp->variance_threshold);
+    a.hierarchy_threshold = muniform_f64(rp->hierarchy_threshold);
+    a.cluster_threshold = muniform_f64(rp->cluster_threshold);
+#endif
     BatchArgs ar = a;  // what component_scores reads: the round's shape, max_components capped (:134-137)
     ar.N = N;
     ar.E = E;

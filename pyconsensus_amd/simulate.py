@@ -196,7 +196,7 @@ def _cells(cells):
             if not 1 <= len(cell) <= len(CELL_FIELDS):
                 raise ValueError("cell %d: a tuple cell is (%s), from the left" % (c, ", ".join(CELL_FIELDS)))
             cell = dict(zip(CELL_FIELDS, cell))
-        unknown = set(cell) - set(CELL_FIELDS)
+        unknown = set(cell) - set(CELL_FIELDS) - set(_abi.PARAM_KEYS)  # (a dict cell may carry its own parameters)
         if unknown:
             raise ValueError("cell %d: unknown field(s) %s" % (c, sorted(unknown)))
         if "rounds" not in cell:
@@ -230,15 +230,40 @@ def _sweep(cells, T=1, scaled_tol=0.1, algorithm="PCA", catch_tolerance=0.1, alp
     return s, arr, norm, offsets
 
 
+def _cell_params(norm, algorithm="PCA", catch_tolerance=0.1, alpha=0.1, max_components=5, variance_threshold=0.9,
+                 hierarchy_threshold=0.5, cluster_threshold=None, **_):
+    """The pcx_round_params array [C] of cells that carry parameters of their own (a missing key takes
+    the call's keyword value), or None when no cell does: then the existing entries run, unchanged."""
+    if not any(k in d for d in norm for k in _abi.PARAM_KEYS):
+        return None
+    shared = dict(algorithm=algorithm, catch_tolerance=catch_tolerance, alpha=alpha, max_components=max_components,
+                  variance_threshold=variance_threshold, hierarchy_threshold=hierarchy_threshold,
+                  cluster_threshold=cluster_threshold)
+    sets = [dict(shared, **{k: d[k] for k in _abi.PARAM_KEYS if k in d}) for d in norm]
+    return (_abi.RoundParams * len(sets))(*[_abi.round_params(q) for q in sets])
+
+
 def sweep_plan(cells, T=1, algorithm="PCA", **params):
     """Validate a sweep without a device (``pcx_sim_sweep_plan``): ``(totals, counts, lds_bytes)`` as int64
     arrays of four: totals = (B, sum R N, sum R E, sum R N E); counts / lds_bytes are
-    ``ragged_plan(wide=True)``'s for the sweep's rounds.  Raises with the cell's index on refusal."""
-    s, arr, _, _ = _sweep(cells, T, algorithm=algorithm, **params)
+    ``ragged_plan(wide=True)``'s for the sweep's rounds.  Raises with the cell's index on refusal.
+    With cells that carry parameters of their own (``pcx_sim_study_params_check``) counts / lds_bytes
+    are summed / the maximum over the cells, each by its own algorithm."""
+    s, arr, norm, _ = _sweep(cells, T, algorithm=algorithm, **params)
     out = [(C.c_int64 * 4)() for _ in range(3)]
     bad = C.c_int64(-2)
-    _lib.check(_lib.lib().pcx_sim_sweep_plan(C.byref(s), out[0], out[1], out[2], C.byref(bad)))
-    return tuple(np.array(list(x), dtype=np.int64) for x in out)
+    cp = _cell_params(norm, algorithm=algorithm, **params)
+    if cp is None:
+        _lib.check(_lib.lib().pcx_sim_sweep_plan(C.byref(s), out[0], out[1], out[2], C.byref(bad)))
+        return tuple(np.array(list(x), dtype=np.int64) for x in out)
+    _lib.check(_lib.lib().pcx_sim_study_params_check(C.byref(s), C.cast(cp, C.c_void_p), None, C.byref(bad)))
+    totals, counts, lds = (np.zeros(4, dtype=np.int64) for _ in range(3))
+    names = {v: k for k, v in _abi.ALGORITHMS.items()}
+    for alg in sorted({q.algorithm for q in cp}):  # the cells of one algorithm, as a sweep that shares it
+        part = [{k: v for k, v in d.items() if k not in _abi.PARAM_KEYS} for d, q in zip(norm, cp) if q.algorithm == alg]
+        t, c, l = sweep_plan(part, T, algorithm=names[alg])
+        totals, counts, lds = totals + t, counts + c, np.maximum(lds, l)
+    return totals, counts, lds
 
 
 def _flat_len(kind, offsets):
@@ -319,8 +344,12 @@ def sweep(cells, T=1, scaled_tol=0.1, algorithm="PCA", catch_tolerance=0.1, alph
 
     ``cells`` is a list of dicts (or tuples, from the left) with ``rounds``, ``reporters``, ``events``,
     ``seed``, ``liar_frac``, ``collude_frac``, ``distort``, ``na_frac``, ``scaled_frac``; what a dict
-    leaves out is :func:`simulate`'s default.  Shapes go up to 256 x 64.  The timesteps, ``scaled_tol``
-    and the consensus parameters are shared.  The rounds of all cells lie end to end in cell order
+    leaves out is :func:`simulate`'s default.  Shapes go up to 256 x 64.  The timesteps and ``scaled_tol``
+    are shared.  A dict cell may also carry consensus parameters of its own (``algorithm``,
+    ``catch_tolerance``, ``alpha``, ``max_components``, ``variance_threshold``, ``hierarchy_threshold``,
+    ``cluster_threshold``; a missing key takes the call's keyword value): the call then goes through
+    ``pcx_simulate_study_params_f64``, still one wide ragged batch per timestep with no more launches
+    for more parameter sets.  The rounds of all cells lie end to end in cell order
     in :func:`consensus_ragged`'s flat layout and run as one wide ragged batch per timestep.
 
     Cell c's slice of every output is byte for byte ``simulate(R_c, N_c, E_c, T, seed_c, ...)``: the
@@ -352,9 +381,18 @@ def _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_comp
     rep = _device.as_device(reputation, tc.float64, dev)
     s, arr, norm, offsets = _sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_components,
                                    variance_threshold, hierarchy_threshold, cluster_threshold, _device.ptr(rep))
-    sweep_plan(cells, T, algorithm=algorithm, scaled_tol=scaled_tol, catch_tolerance=catch_tolerance, alpha=alpha,
-               max_components=max_components, variance_threshold=variance_threshold,
-               hierarchy_threshold=hierarchy_threshold, cluster_threshold=cluster_threshold)  # refuses by cell
+    shared = dict(algorithm=algorithm, catch_tolerance=catch_tolerance, alpha=alpha, max_components=max_components,
+                  variance_threshold=variance_threshold, hierarchy_threshold=hierarchy_threshold,
+                  cluster_threshold=cluster_threshold)
+    cp = _cell_params(norm, **shared)  # None: no cell has parameters of its own
+    st = base = None
+    if cp is None:
+        sweep_plan(cells, T, scaled_tol=scaled_tol, **shared)  # refuses by cell
+    else:  # one check of the cells, their parameter sets and the pairing
+        base = pair_base(norm, pair_with) if with_study else None
+        _lib.check(_lib.lib().pcx_sim_study_params_check(C.byref(s), C.cast(cp, C.c_void_p),
+                                                         None if base is None else base.ctypes.data,
+                                                         C.byref(C.c_int64(-2))))
     T, Cn, B, tn = int(T), len(norm), int(offsets["rounds"][-1]), _flat_len("N", offsets)
     if rep is not None and tuple(rep.shape) != (tn,):
         raise ValueError("reputation must be flat, sum R_c N_c = %d long" % tn)
@@ -375,8 +413,9 @@ def _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_comp
             setattr(res.last_out, name, outs[name].data_ptr())
         out["outputs"] = outs
     if with_study:
-        base = study_check(norm, pair_with, T, algorithm=algorithm, scaled_tol=scaled_tol,
-                           max_components=max_components)  # refuses by cell
+        if cp is None:
+            base = study_check(norm, pair_with, T, algorithm=algorithm, scaled_tol=scaled_tol,
+                               max_components=max_components)  # refuses by cell
         st = _abi.SimStudyResult()
         out["stats"] = tc.empty((T, Cn, _abi.SIM_NVALUES, _abi.SIM_NSTATS), dtype=tc.float64, device=dev)
         st.stats = out["stats"].data_ptr()
@@ -388,7 +427,11 @@ def _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_comp
             out["detail"] = tc.empty((T, B, _abi.SIM_NDETAIL), dtype=tc.float64, device=dev)
             st.detail = out["detail"].data_ptr()
     h = _lib.bind_stream(dev.index, _device.current_stream_handle(dev))
-    if with_study:
+    if cp is not None:
+        _lib.check(_lib.lib().pcx_simulate_study_params_f64(
+            h, C.byref(s), C.cast(cp, C.c_void_p), None if base is None else base.ctypes.data, C.byref(res),
+            None if st is None else C.byref(st)))
+    elif with_study:
         _lib.check(_lib.lib().pcx_simulate_study_f64(h, C.byref(s), None if base is None else base.ctypes.data,
                                                      C.byref(res), C.byref(st)))
     else:
@@ -425,10 +468,15 @@ def study_check(cells, pair_with=None, T=1, algorithm="PCA", **params):
     """Validate a study without a device (``pcx_sim_study_check``): what :func:`sweep_plan` refuses, then
     a base outside the cell list, a cell that is its own base, a base with another number of rounds.
     Raises with the cell's index; returns the ``pair_base`` array (or None)."""
-    s, arr, _, _ = _sweep(cells, T, algorithm=algorithm, **params)
+    s, arr, norm, _ = _sweep(cells, T, algorithm=algorithm, **params)
     base = pair_base(cells, pair_with)
     bad = C.c_int64(-2)
-    _lib.check(_lib.lib().pcx_sim_study_check(C.byref(s), None if base is None else base.ctypes.data, C.byref(bad)))
+    cp = _cell_params(norm, algorithm=algorithm, **params)
+    if cp is None:
+        _lib.check(_lib.lib().pcx_sim_study_check(C.byref(s), None if base is None else base.ctypes.data, C.byref(bad)))
+    else:  # cells with parameters of their own
+        _lib.check(_lib.lib().pcx_sim_study_params_check(C.byref(s), C.cast(cp, C.c_void_p),
+                                                         None if base is None else base.ctypes.data, C.byref(bad)))
     return base
 
 
@@ -621,14 +669,17 @@ def stderr(stats_or_paired):
         return np.sqrt(x[..., 2] / x[..., 0])
 
 
-_GRID_AXES = ("reporters", "events", "liar_frac", "collude_frac", "distort", "na_frac", "scaled_frac")
+_GRID_AXES = ("reporters", "events", "liar_frac", "collude_frac", "distort", "na_frac", "scaled_frac") + _abi.PARAM_KEYS
 
 
 def grid(rounds, seed=0, independent=False, **axes):
     """The cell list of a cartesian product: every axis (``reporters``, ``events``, ``liar_frac``,
-    ``collude_frac``, ``distort``, ``na_frac``, ``scaled_frac``) a value or a sequence of values, the
+    ``collude_frac``, ``distort``, ``na_frac``, ``scaled_frac``, and the consensus parameters
+    ``algorithm``, ``catch_tolerance``, ``alpha``, ``max_components``, ``variance_threshold``,
+    ``hierarchy_threshold``, ``cluster_threshold``) a value or a sequence of values, the
     first axis given varying slowest; ``rounds`` per cell.  All cells share ``seed`` (common random
-    numbers along every axis) unless ``independent``: then cell k has ``seed + k``."""
+    numbers along every axis) unless ``independent``: then cell k has ``seed + k``.  Along a parameter
+    axis the cells draw the same rounds: ``study(pair_with="first")`` pairs them."""
     import itertools
 
     unknown = set(axes) - set(_GRID_AXES)
@@ -667,7 +718,10 @@ def main(argv=None):
     ap.add_argument("--missing", type=flt, default=[0.1], help="na_frac (or a comma list)")
     ap.add_argument("--scaled", type=flt, default=[0.25], help="scaled_frac (or a comma list)")
     ap.add_argument("--scaled-tol", type=float, default=0.1)
-    ap.add_argument("--algorithm", default="PCA")
+    ap.add_argument("--algorithm", type=_comma_list(str), default=["PCA"],
+                    help="a comma list runs every cell under each algorithm, in one call")
+    ap.add_argument("--alpha", type=flt, default=None, help="the reputation smoothing (or a comma list)")
+    ap.add_argument("--catch", type=flt, default=None, help="catch_tolerance (or a comma list)")
     ap.add_argument("--stats", action="store_true",
                     help="run a study: every timestep gains 'detail' (the means of the detail metrics) and "
                          "'stderr' (the standard errors of all eighteen values)")
@@ -677,11 +731,20 @@ def main(argv=None):
     a = ap.parse_args(argv)
     lists = {"reporters": a.reporters, "events": a.events, "liar_frac": a.liars, "collude_frac": a.collude,
              "distort": a.distort, "na_frac": a.missing, "scaled_frac": a.scaled}
+    # the consensus parameters: a single value is the call's keyword, a list an axis of the grid (its
+    # cells carry the key, and their JSON objects show it)
+    a.shared = {}
+    for key, values in (("algorithm", a.algorithm), ("alpha", a.alpha), ("catch_tolerance", a.catch)):
+        if values is not None and len(values) > 1:
+            lists[key] = values
+        elif values is not None:
+            a.shared[key] = values[0]
+    a.algorithm = ",".join(a.algorithm)
     if a.stats or a.paired:
         return _main_study(a, lists)
     if any(len(v) > 1 for v in lists.values()):  # a grid: --rounds per cell, one shared seed
         cells = grid(a.rounds, seed=a.seed, **lists)
-        r = sweep(cells, a.timesteps, scaled_tol=a.scaled_tol, algorithm=a.algorithm)
+        r = sweep(cells, a.timesteps, scaled_tol=a.scaled_tol, **a.shared)
         summary = r["summary"].cpu().numpy()  # (the copy synchronises)
         print(json.dumps({"rounds": a.rounds, "seed": a.seed, "algorithm": a.algorithm,
                           "cells": [dict({k: v for k, v in cell.items() if k not in ("rounds", "seed")},
@@ -692,7 +755,7 @@ def main(argv=None):
     a.reporters, a.events, a.liars, a.collude, a.distort, a.missing, a.scaled = (v[0] for v in lists.values())
     r = simulate(a.rounds, a.reporters, a.events, a.timesteps, seed=a.seed, liar_frac=a.liars,
                  collude_frac=a.collude, distort=a.distort, na_frac=a.missing, scaled_frac=a.scaled,
-                 scaled_tol=a.scaled_tol, algorithm=a.algorithm)
+                 scaled_tol=a.scaled_tol, **a.shared)
     summary = r["summary"].cpu().numpy()  # (the copy synchronises)
     print(json.dumps({"rounds": a.rounds, "reporters": a.reporters, "events": a.events, "seed": a.seed,
                       "algorithm": a.algorithm,
@@ -706,8 +769,7 @@ def _main_study(a, lists):
     import json
 
     cells = grid(a.rounds, seed=a.seed, **lists)
-    r = study(cells, a.timesteps, pair_with="first" if a.paired else None, scaled_tol=a.scaled_tol,
-              algorithm=a.algorithm)
+    r = study(cells, a.timesteps, pair_with="first" if a.paired else None, scaled_tol=a.scaled_tol, **a.shared)
     summary, stats = r["summary"].cpu().numpy(), r["stats"].cpu().numpy()  # (the copies synchronise)
     se = stderr(stats)
     if a.paired:
