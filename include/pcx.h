@@ -254,6 +254,55 @@ int pcx_ragged_plan_params(int64_t n_rounds, const int32_t* n_reporters, const i
 int pcx_consensus_ragged_params_f64(pcx_ctx* ctx, const pcx_ragged* in, int64_t n_params,
                                     const pcx_round_params* params, const int32_t* param_of, pcx_batch_result* out);
 
+/* k-means in ragged batches (added under ABI 9; detect by symbol).  The entries
+ * above keep their refusals; these take k-means as one more clustering algorithm of a parameter set.
+ *
+ * Code books: round b's books are restarts x k_b int32 rows of [0, N_b) -- the rows of the round's
+ * observations that start each restart (pcx_batch.kmeans_init of one round) -- at offsets[b] of one
+ * flat DEVICE array, rounds end to end, nothing padded.  restarts is one value per call (>= 1).  k_b
+ * is the reference's int(ceil(sqrt(N_b))) (:396), or the caller's: in [1, min(N_b, 8)] for a round
+ * within 64 x 32 (the one-wave kernel's code-book rows), in [1, min(N_b, 16)] above that (the
+ * workgroup kernel's). */
+typedef struct {
+    int32_t restarts;             /* >= 1, shared by the call's rounds                          */
+    const int32_t* k;             /* HOST [B] code-book sizes, or NULL: the ceil(sqrt(N_b)) rule */
+    const int32_t* init;          /* DEVICE, flat: round b's [restarts][k_b] rows at offsets[b]  */
+} pcx_kmeans_books;
+
+/* Pure (no context, no device): the layout of the flat book array when every round is k-means.
+ * offsets [B + 1] int64 (or NULL): offsets[b] = sum over earlier rounds of restarts * k_b,
+ * offsets[B] the array's length.  k HOST [B] or NULL (the rule).  Refuses (PCX_EINVAL,
+ * pcx_last_error names the round) restarts < 1 (*bad_round = -1), a round outside [1, 256] x [1, 64]
+ * and a k_b outside the bounds above, with *bad_round = the first such round.  n_rounds == 0
+ * succeeds with offsets[0] = 0. */
+int pcx_kmeans_plan(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, const int32_t* k,
+                    int32_t restarts, int64_t* offsets, int64_t* bad_round);
+
+/* pcx_ragged_plan_params with k-means allowed in a parameter set (pure).  books->restarts and
+ * books->k are read (books->init is not) if some round's set is k-means, and then books must not be
+ * NULL; k[b] is read for the k-means rounds only.  offsets [B + 1] int64 (or NULL) counts ONLY the
+ * k-means rounds' books: a round of another algorithm has offsets[b + 1] == offsets[b].  Refuses
+ * what pcx_ragged_plan_params refuses but k-means, in its order and words, then what
+ * pcx_kmeans_plan refuses of the k-means rounds (*bad_round). */
+int pcx_ragged_plan_kmeans(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
+                           const pcx_round_params* params, const int32_t* param_of, const pcx_kmeans_books* books,
+                           int64_t totals[3], int64_t* n_launches, int64_t* offsets, int64_t* bad_round,
+                           int64_t* bad_param);
+/* pcx_consensus_ragged_params_f64 with PCX_ALG_KMEANS accepted in a parameter set: round b's results
+ * are byte for byte those of pcx_consensus_batched_f64 on its shape with kmeans_k = k_b,
+ * kmeans_restarts = books->restarts and kmeans_init = books->init + offsets[b] (offsets as
+ * pcx_ragged_plan_kmeans lays them out: only the k-means rounds' books are in the array); a row
+ * outside [0, N_b) is clamped as there.  The k-means rounds are clustering rounds: they join the
+ * hierarchical and clusterfeck rounds' launches (one-wave group 2, the workgroup kernel's CLUS
+ * launches by launch class), so a call still makes at most 3 + 2 x 3 launches.  The clustering
+ * launches run the round kernels' texts in a further form that reads {offset, k_b} from a per-round
+ * device table, which rides in the call's one upload; the other launches are
+ * pcx_consensus_ragged_params_f64's own.  Refuses what pcx_ragged_plan_kmeans refuses, and NULL
+ * books->init with a k-means round, before it launches anything.  Asynchronous. */
+int pcx_consensus_ragged_kmeans_f64(pcx_ctx* ctx, const pcx_ragged* in, int64_t n_params,
+                                    const pcx_round_params* params, const int32_t* param_of,
+                                    const pcx_kmeans_books* books, pcx_batch_result* out);
+
 /* ------------------------------------------------------------------------ */
 /* Monte Carlo simulator (ABI >= 9): the Simulator.jl-style driver of the       */
 /* batched regime (README.rst:52-56) on the device.  It draws random rounds     */
@@ -470,6 +519,43 @@ int pcx_sim_study_params_check(const pcx_sim_sweep* sweep, const pcx_round_param
  * the call's one upload.  Per timestep: the launches of pcx_consensus_ragged_params_f64. */
 int pcx_simulate_study_params_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,
                                   const int32_t* pair_base, pcx_sim_result* result, pcx_sim_study_result* study);
+
+/* k-means in the simulator (added under ABI 9; detect by symbol).  The entries above
+ * keep their refusals.  The initial code books are drawn on the device from a further stream of the
+ * generator (KMEANS = 5; streams 0..4 and their bits are unchanged): for round b (its index inside
+ * its cell), restart r, timestep t and c = 0 .. k - 1, with j = N - k + c,
+ *     w = Philox4x32-10((c, r, b, 5 << 24 | t), key).w0,   v = (w * (j + 1)) >> 32,
+ *     book[c] = v if v is not among book[0 .. c), else j
+ * (Floyd's sampling: k distinct rows of [0, N); integers only, so the host twins agree bit for bit).
+ * k is the reference's int(ceil(sqrt(N))); the key is the simulation's / the cell's seed, so cells
+ * that share seed, shape and rounds draw the same books.  The books of a timestep are materialised
+ * once, in the context's workspace, and the round kernels read them; restarts is one value per call.
+ *
+ * pcx_sim_kmeans_books_*: books [B][restarts][k] int32 of one timestep of `sim` (whose algorithm need
+ * not be k-means).  The sweep pair: every round of the sweep, laid out by pcx_kmeans_plan's offsets
+ * over the sweep's rounds (the rule's k).  _host: HOST pointer, no context. */
+int pcx_sim_kmeans_books_host(const pcx_sim* sim, int32_t restarts, int timestep, int32_t* books);
+int pcx_sim_kmeans_books_f64(pcx_ctx* ctx, const pcx_sim* sim, int32_t restarts, int timestep, int32_t* books);
+int pcx_sim_sweep_kmeans_books_host(const pcx_sim_sweep* sweep, int32_t restarts, int timestep, int32_t* books);
+int pcx_sim_sweep_kmeans_books_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, int32_t restarts, int timestep,
+                                   int32_t* books);
+/* pcx_simulate_f64 with k-means accepted (restarts >= 1): per timestep the generator, the books
+ * kernel, pcx_consensus_batched_f64 with kmeans_init = the books, the metrics.  Timestep t's outputs
+ * are those of pcx_consensus_batched_f64 on pcx_sim_generate_f64's rounds with
+ * pcx_sim_kmeans_books_f64's books.  Another algorithm: pcx_simulate_f64's bytes.  Asynchronous where
+ * pcx_simulate_f64 is. */
+int pcx_simulate_kmeans_f64(pcx_ctx* ctx, const pcx_sim* sim, int32_t restarts, pcx_sim_result* result);
+/* pcx_simulate_study_params_f64 with k-means accepted, shared (cell_params NULL) or in a cell's set:
+ * per timestep the generator, the books kernel over the k-means cells' rounds, the launches of
+ * pcx_consensus_ragged_kmeans_f64, the metrics.  study NULL: the sweep.  Cell c's slice of every
+ * output is byte for byte what pcx_simulate_kmeans_f64 gives for that cell alone.  Cokurtosis stays
+ * refused.  pcx_sim_study_kmeans_check is pure: what the call refuses (restarts < 1 with
+ * *bad_cell = -1). */
+int pcx_sim_study_kmeans_check(const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,
+                               const int32_t* pair_base, int32_t restarts, int64_t* bad_cell);
+int pcx_simulate_study_kmeans_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,
+                                  const int32_t* pair_base, int32_t restarts, pcx_sim_result* result,
+                                  pcx_sim_study_result* study);
 
 /* ------------------------------------------------------------------------ */
 /* Single-matrix regime: one N x E report matrix, optionally sharded by        */

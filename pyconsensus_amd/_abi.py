@@ -170,6 +170,12 @@ def round_params(values):
                        0.0 if ct is None else float(ct))
 
 
+class KmeansBooks(C.Structure):
+    """pcx_kmeans_books: the code books of a ragged batch's k-means rounds (restarts, HOST k[B] or
+    NULL for the ceil(sqrt(N_b)) rule, the flat DEVICE array of initial rows)."""
+    _fields_ = [("restarts", C.c_int32), ("k", C.c_void_p), ("init", C.c_void_p)]
+
+
 # simulator studies: the detail metrics, the per-cell statistics and the paired differences
 SIM_NDETAIL = 12                 # PCX_SIM_NDETAIL
 SIM_NVALUES = SIM_NMETRICS + SIM_NDETAIL  # PCX_SIM_NVALUES

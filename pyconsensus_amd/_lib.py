@@ -106,6 +106,19 @@ def _declare(lib):
         ("pcx_sim_study_params_check", i32, [C.POINTER(_abi.SimSweep), vp, vp, C.POINTER(i64)]),
         ("pcx_simulate_study_params_f64", i32, [vp, C.POINTER(_abi.SimSweep), vp, vp, C.POINTER(_abi.SimResult),
                                                 C.POINTER(_abi.SimStudyResult)]),
+        ("pcx_kmeans_plan", i32, [i64, vp, vp, vp, C.c_int32, vp, C.POINTER(i64)]),
+        ("pcx_ragged_plan_kmeans", i32, [i64, vp, vp, i64, vp, vp, C.POINTER(_abi.KmeansBooks), C.POINTER(i64),
+                                         C.POINTER(i64), vp, C.POINTER(i64), C.POINTER(i64)]),
+        ("pcx_consensus_ragged_kmeans_f64", i32, [vp, C.POINTER(_abi.Ragged), i64, vp, vp,
+                                                  C.POINTER(_abi.KmeansBooks), C.POINTER(_abi.BatchResult)]),
+        ("pcx_sim_kmeans_books_host", i32, [C.POINTER(_abi.Sim), C.c_int32, i32, vp]),
+        ("pcx_sim_kmeans_books_f64", i32, [vp, C.POINTER(_abi.Sim), C.c_int32, i32, vp]),
+        ("pcx_sim_sweep_kmeans_books_host", i32, [C.POINTER(_abi.SimSweep), C.c_int32, i32, vp]),
+        ("pcx_sim_sweep_kmeans_books_f64", i32, [vp, C.POINTER(_abi.SimSweep), C.c_int32, i32, vp]),
+        ("pcx_simulate_kmeans_f64", i32, [vp, C.POINTER(_abi.Sim), C.c_int32, C.POINTER(_abi.SimResult)]),
+        ("pcx_sim_study_kmeans_check", i32, [C.POINTER(_abi.SimSweep), vp, vp, C.c_int32, C.POINTER(i64)]),
+        ("pcx_simulate_study_kmeans_f64", i32, [vp, C.POINTER(_abi.SimSweep), vp, vp, C.c_int32,
+                                                C.POINTER(_abi.SimResult), C.POINTER(_abi.SimStudyResult)]),
     ]:
         if (name in ("pcx_batched_lds_bytes", "pcx_medium_lds_bytes", "pcx_batched_route", "pcx_ragged_plan",
                      "pcx_consensus_ragged_f64", "pcx_ragged_plan_wide", "pcx_consensus_ragged_wide_f64",
@@ -115,7 +128,10 @@ def _declare(lib):
                      "pcx_sim_sweep_detail_host", "pcx_sim_study_check", "pcx_sim_sweep_stats_f64",
                      "pcx_sim_sweep_stats_host", "pcx_simulate_study_f64", "pcx_ragged_plan_params",
                      "pcx_consensus_ragged_params_f64", "pcx_sim_study_params_check",
-                     "pcx_simulate_study_params_f64")
+                     "pcx_simulate_study_params_f64", "pcx_kmeans_plan", "pcx_ragged_plan_kmeans",
+                     "pcx_consensus_ragged_kmeans_f64", "pcx_sim_kmeans_books_host", "pcx_sim_kmeans_books_f64",
+                     "pcx_sim_sweep_kmeans_books_host", "pcx_sim_sweep_kmeans_books_f64", "pcx_simulate_kmeans_f64",
+                     "pcx_sim_study_kmeans_check", "pcx_simulate_study_kmeans_f64")
                 and os.environ.get("PCX_LIB") and not hasattr(lib, name)):
             continue  # an A/B build of a revision before these queries (tools/ab_build.sh)
         f = getattr(lib, name)

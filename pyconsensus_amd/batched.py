@@ -50,6 +50,39 @@ def kmeans_draws(B, N, restarts=_abi.KMEANS_RESTARTS, random_state=None):
     return out
 
 
+def kmeans_draws_ragged(n_reporters, restarts=_abi.KMEANS_RESTARTS, random_state=None, k=None):
+    """Initial code-book rows of k-means rounds of DIFFERENT sizes: a list of (restarts, k_b) int32
+    arrays, round b's drawn as ``rs.choice(N_b, size=k_b, replace=False)`` restart after restart,
+    round after round -- the RandomState (numpy's global one by default) is consumed exactly as
+    :func:`kmeans_draws` called round by round consumes it, and as sequential reference consensus()
+    calls would.  ``k``: the code-book sizes (default :func:`kmeans_k` of each N_b)."""
+    rs = np.random.mtrand._rand if random_state is None else random_state
+    out = []
+    for b, N in enumerate(n_reporters):
+        kb = kmeans_k(N) if k is None else int(k[b])
+        book = np.empty((restarts, kb), dtype=np.int32)
+        for r in range(restarts):
+            book[r] = rs.choice(int(N), size=kb, replace=False)
+        out.append(book)
+    return out
+
+
+def kmeans_plan(shapes, restarts=_abi.KMEANS_RESTARTS, k=None):
+    """The int64 [B + 1] offsets of the flat code-book array of k-means rounds of ``shapes``
+    [(N_b, E_b), ...] (pcx_kmeans_plan): round b's ``restarts x k_b`` rows start at offsets[b].
+    ``k``: the code-book sizes (default: the ceil(sqrt(N_b)) rule).  Needs no GPU; raises PcxError
+    naming the first round whose shape or code-book size is refused."""
+    sh = np.ascontiguousarray(np.asarray(shapes, dtype=np.int32).reshape(-1, 2))
+    n, e = np.ascontiguousarray(sh[:, 0]), np.ascontiguousarray(sh[:, 1])
+    kk = None if k is None else np.ascontiguousarray(k, dtype=np.int32)
+    if kk is not None and kk.shape != (len(sh),):
+        raise ValueError("k must hold one code-book size per round (%d)" % len(sh))
+    offsets, bad = np.zeros(len(sh) + 1, dtype=np.int64), C.c_int64(-1)
+    _lib.check(_lib.lib().pcx_kmeans_plan(len(sh), n.ctypes.data, e.ctypes.data, None if kk is None else kk.ctypes.data,
+                                          int(restarts), offsets.ctypes.data, C.byref(bad)))
+    return offsets
+
+
 ROUTES = ("wave", "workgroup", "scheduler")  # include/pcx.h enum pcx_route
 
 
@@ -206,7 +239,7 @@ def _upload_packed(items, dev):
         if p is not None:
             host[p[1]:p[1] + p[0].nbytes] = p[0].reshape(-1).view(np.uint8)
     d = t.from_numpy(host).to(dev)
-    tdt = {np.float64: t.float64, np.uint8: t.uint8}
+    tdt = {np.float64: t.float64, np.uint8: t.uint8, np.int32: t.int32}
     return [None if p is None else d[p[1]:p[1] + p[0].nbytes].view(tdt[dt]).view(p[0].shape)
             for p, (_, dt) in zip(parts, items)]
 
@@ -236,7 +269,7 @@ def _ragged_vectors(seq, counts, dtype, what):
     return np.concatenate(parts) if parts else np.zeros(0, dtype=dtype)
 
 
-def ragged_plan(shapes, algorithm="PCA", wide=False):
+def ragged_plan(shapes, algorithm="PCA", wide=False, kmeans_restarts=None, kmeans_k=None):
     """(totals, lds_bytes) of a ragged batch of ``shapes`` [(N_b, E_b), ...]: totals = (sum N_b,
     sum E_b, sum N_b * E_b), the flat arrays' lengths, and the launch's dynamic LDS.  Needs no GPU;
     raises PcxError naming the first round the one-wave kernel does not take (or k-means).
@@ -244,12 +277,22 @@ def ragged_plan(shapes, algorithm="PCA", wide=False):
     ``wide=True``: rounds up to 256 x 64 (pcx_ragged_plan_wide); returns (totals, counts, lds_bytes)
     with 4-tuples counts / lds_bytes: index 0 the rounds of at most 64 x 32 (the one-wave kernel's
     launch), index c = 1..3 the workgroup kernel's rounds of launch class c -- c rounds per CU by
-    their LDS -- and that launch's dynamic LDS."""
+    their LDS -- and that launch's dynamic LDS.
+
+    ``kmeans_restarts`` (an int) opts in to k-means (pcx_ragged_plan_kmeans): returns (totals,
+    n_launches, book_offsets) as :func:`ragged_plan_kmeans` for the one shared set; ``kmeans_k``
+    the code-book sizes (default: the rule).  Without it k-means is refused as before."""
     alg = _abi.ALGORITHMS.get(algorithm)
     if alg is None:
         raise NotImplementedError("algorithm %r is not on the GPU path" % (algorithm,))
     sh = np.ascontiguousarray(np.asarray(shapes, dtype=np.int32).reshape(-1, 2))
     n, e = np.ascontiguousarray(sh[:, 0]), np.ascontiguousarray(sh[:, 1])
+    if kmeans_restarts is not None:
+        if not wide:
+            ragged_plan(sh, "PCA", wide=False)  # the one-wave limits, by index
+        defaults = dict(algorithm=algorithm, catch_tolerance=0.1, alpha=0.1, max_components=5, variance_threshold=0.9,
+                        hierarchy_threshold=0.5, cluster_threshold=None)
+        return ragged_plan_kmeans(sh, [defaults], np.zeros(len(sh), dtype=np.int32), kmeans_restarts, kmeans_k)
     if wide:
         totals, counts, lds4, bad = (C.c_int64 * 3)(), (C.c_int64 * 4)(), (C.c_int64 * 4)(), C.c_int64(-1)
         _lib.check(_lib.lib().pcx_ragged_plan_wide(len(sh), n.ctypes.data, e.ctypes.data, alg, totals, counts, lds4,
@@ -300,10 +343,87 @@ def ragged_plan_params(shapes, sets, param_of):
     return tuple(int(x) for x in totals), int(nl.value)
 
 
+def ragged_plan_kmeans(shapes, sets, param_of, restarts, k=None):
+    """:func:`ragged_plan_params` with k-means allowed in a set (pcx_ragged_plan_kmeans): (totals,
+    n_launches, book_offsets).  book_offsets is int64 [B + 1] and counts only the k-means rounds'
+    ``restarts x k_b`` code-book rows (``k``: their sizes, one per round, default the
+    ceil(sqrt(N_b)) rule; an entry of a round that is not k-means is not read)."""
+    sh = np.ascontiguousarray(np.asarray(shapes, dtype=np.int32).reshape(-1, 2))
+    n, e = np.ascontiguousarray(sh[:, 0]), np.ascontiguousarray(sh[:, 1])
+    of = np.ascontiguousarray(param_of, dtype=np.int32)
+    kk = None if k is None else np.ascontiguousarray(k, dtype=np.int32)
+    if kk is not None and kk.shape != (len(sh),):
+        raise ValueError("kmeans_k must hold one code-book size per round (%d)" % len(sh))
+    arr = _params_array(sets)
+    books = _abi.KmeansBooks(int(restarts), None if kk is None else kk.ctypes.data, None)
+    totals, nl, bad_r, bad_p = (C.c_int64 * 3)(), C.c_int64(0), C.c_int64(-1), C.c_int64(-1)
+    offsets = np.zeros(len(sh) + 1, dtype=np.int64)
+    _lib.check(_lib.lib().pcx_ragged_plan_kmeans(len(sh), n.ctypes.data, e.ctypes.data, len(sets),
+                                                 C.cast(arr, C.c_void_p), of.ctypes.data, C.byref(books), totals,
+                                                 C.byref(nl), offsets.ctypes.data, C.byref(bad_r), C.byref(bad_p)))
+    return tuple(int(x) for x in totals), int(nl.value), offsets
+
+
+def _kmeans_books(kmeans_init, kmeans_restarts, kmeans_k, ns, is_km, plan):
+    """consensus_ragged's ``kmeans_init`` -> (restarts, int32 k[B] or None, the books: a flat host
+    int32 array, or the caller's device tensor).  ``plan(restarts, k)`` raises what the call refuses."""
+    B = len(ns)
+    if kmeans_k is not None:
+        kmeans_k = np.asarray(kmeans_k, dtype=np.int32)
+        if kmeans_k.shape != (B,):
+            raise ValueError("kmeans_k must hold one code-book size per round (%d)" % B)
+    if isinstance(kmeans_init, str):
+        if kmeans_init != "draw":
+            raise ValueError("kmeans_init must be None, \"draw\", a list of per-round arrays or a device tensor")
+        restarts = _abi.KMEANS_RESTARTS if kmeans_restarts is None else int(kmeans_restarts)
+        if restarts < 1:
+            raise ValueError("kmeans_restarts must be >= 1")
+        km = [b for b in range(B) if is_km[b]]
+        plan(restarts, kmeans_k)  # (what the plan refuses is refused before a draw is made)
+        drawn = kmeans_draws_ragged([ns[b] for b in km], restarts, k=None if kmeans_k is None else kmeans_k[km])
+        flat = np.concatenate([d.reshape(-1) for d in drawn]) if drawn else np.zeros(0, dtype=np.int32)
+        return restarts, kmeans_k, flat
+    if isinstance(kmeans_init, (list, tuple)):
+        if len(kmeans_init) != B:
+            raise ValueError("kmeans_init must hold one entry per round (%d), got %d" % (B, len(kmeans_init)))
+        restarts = None if kmeans_restarts is None else int(kmeans_restarts)
+        ks, parts = np.zeros(B, dtype=np.int32), []
+        for b in range(B):
+            if not is_km[b]:
+                continue
+            if kmeans_init[b] is None:
+                raise ValueError("kmeans_init[%d] is None, and round %d is k-means" % (b, b))
+            a = np.asarray(kmeans_init[b])
+            if a.ndim != 2 or a.dtype.kind not in "iu":
+                raise ValueError("kmeans_init[%d] must be an integer (restarts, k) array, got shape %s" % (b, a.shape))
+            restarts = a.shape[0] if restarts is None else restarts
+            if a.shape[0] != restarts:
+                raise ValueError("kmeans_init[%d] has %d restarts, the call %d" % (b, a.shape[0], restarts))
+            if kmeans_k is not None and a.shape[1] != kmeans_k[b]:
+                raise ValueError("kmeans_init[%d] has %d rows a book, kmeans_k[%d] = %d" % (b, a.shape[1], b, kmeans_k[b]))
+            if a.size and (int(a.min()) < 0 or int(a.max()) >= ns[b]):
+                raise ValueError("kmeans_init[%d] rows must lie in [0, %d)" % (b, ns[b]))
+            ks[b] = a.shape[1]
+            parts.append(a.astype(np.int32).reshape(-1))
+        if restarts is None:  # no k-means round: nothing is read
+            restarts = _abi.KMEANS_RESTARTS
+        flat = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
+        return restarts, ks, flat
+    t = _device.torch()
+    if not isinstance(kmeans_init, t.Tensor):
+        raise ValueError("kmeans_init must be None, \"draw\", a list of per-round arrays or a device tensor")
+    if kmeans_restarts is None:
+        raise ValueError("a device tensor of code books needs kmeans_restarts")
+    if kmeans_init.dtype != t.int32 or kmeans_init.dim() != 1 or not kmeans_init.is_contiguous() or not kmeans_init.is_cuda:
+        raise ValueError("a kmeans_init tensor must be a flat contiguous int32 device tensor")
+    return int(kmeans_restarts), kmeans_k, kmeans_init
+
+
 def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *, catch_tolerance=0.1, alpha=0.1,
                      int_dtype=False, algorithm="PCA", outputs=None, device=None, filled=False, original=False,
                      max_components=5, variance_threshold=0.9, aux_scores=None, hierarchy_threshold=0.5,
-                     cluster_threshold=None, wide=False, per_round=None):
+                     cluster_threshold=None, wide=False, per_round=None, kmeans_init=None, kmeans_restarts=None,
+                     kmeans_k=None):
     """Run B rounds of DIFFERENT shapes in one launch of the one-wave round kernel.
 
     reports:    a sequence of B arrays, round b an (N_b, E_b) matrix with N_b <= 64, E_b <= 32
@@ -322,9 +442,21 @@ def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *,
                 sets).  Round b equals round b of the same call with its set as the keywords.
                 ``aux_scores`` is needed if some round's algorithm is cokurtosis (an entry of a
                 round that is not may be None).  ``wide=False`` keeps the 64 x 32 limit
-    algorithm:  as :func:`consensus_batched` but "k-means" (its code-book size depends on N_b);
-                "big-five" caps max_components at E_b per round, "clusterfeck" takes the reference's
-                log10(E_b)/1.77 cut per round unless cluster_threshold is given
+    algorithm:  as :func:`consensus_batched`; "k-means" needs ``kmeans_init`` (below) and is refused
+                without it; "big-five" caps max_components at E_b per round, "clusterfeck" takes the
+                reference's log10(E_b)/1.77 cut per round unless cluster_threshold is given
+    kmeans_init: None (default): k-means is refused, as before.  Otherwise the call takes k-means,
+                shared or in ``per_round`` sets (pcx_consensus_ragged_kmeans_f64), with the k-means
+                rounds' initial code books from: ``"draw"`` -- :func:`kmeans_draws_ragged` on numpy's
+                global RandomState, over the k-means rounds in round order; a list of B integer
+                arrays (restarts, k_b), rows in [0, N_b) (None where the round is not k-means); or one
+                flat int32 device tensor, the k-means rounds' books end to end ([restarts][k_b] each,
+                laid out as ``out["_kmeans_offsets"]`` / :func:`ragged_plan_kmeans` tell), which is
+                read in place and needs ``kmeans_restarts``.  Round b equals ``consensus_batched`` of
+                its shape with ``kmeans_init`` = its book
+    kmeans_restarts: restarts of every k-means round (default 20 for "draw"; a list's own)
+    kmeans_k:   B code-book sizes (default: the reference's ceil(sqrt(N_b)), or a list's own): within
+                [1, min(N_b, 8)] for a round up to 64 x 32, [1, min(N_b, 16)] above
 
     Each round is exactly its own ``Oracle(...).consensus()``: nothing is padded.  The inputs travel
     to the device in one copy.  Returns flat device tensors named as in :func:`consensus_batched`,
@@ -353,10 +485,10 @@ def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *,
     if alg is None:
         raise NotImplementedError("algorithm %r is not on the GPU path" % (algorithm,))
     sets = param_of = None
-    if per_round is not None:
-        if len(per_round) != B:
+    if per_round is not None or kmeans_init is not None:  # (the k-means entry takes parameter sets)
+        if per_round is not None and len(per_round) != B:
             raise ValueError("per_round must hold one entry per round (%d), got %d" % (B, len(per_round)))
-        sets, param_of = param_sets(per_round, dict(
+        sets, param_of = param_sets([None] * B if per_round is None else per_round, dict(
             algorithm=algorithm, catch_tolerance=catch_tolerance, alpha=alpha, max_components=max_components,
             variance_threshold=variance_threshold, hierarchy_threshold=hierarchy_threshold,
             cluster_threshold=cluster_threshold), "per_round")
@@ -370,8 +502,19 @@ def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *,
             aux_scores = [np.zeros(n) if v is None and sets[param_of[b]]["algorithm"] != "cokurtosis" else v
                           for b, (v, n) in enumerate(zip(aux_scores, ns))]
         aux = _ragged_vectors(aux_scores, ns, np.float64, "aux_scores")
+    km_restarts = km_k = km_books = km_offsets = None
     if sets is None:
         totals = ragged_plan(shapes, algorithm, wide=wide)[0]  # refuses k-means and rounds past the limits, by index
+    elif kmeans_init is not None:
+        if not wide:
+            ragged_plan(shapes, "PCA", wide=False)  # the one-wave limits, by index
+        is_km = [sets[q]["algorithm"] == "k-means" for q in param_of]
+        km_restarts, km_k, km_books = _kmeans_books(kmeans_init, kmeans_restarts, kmeans_k, ns, is_km,
+                                                    lambda r, k: ragged_plan_kmeans(shapes, sets, param_of, r, k))
+        totals, _, km_offsets = ragged_plan_kmeans(shapes, sets, param_of, km_restarts, km_k)
+        if len(km_books) < int(km_offsets[-1]):
+            raise ValueError("kmeans_init holds %d rows, the k-means rounds' code books %d"
+                             % (len(km_books), int(km_offsets[-1])))
     else:
         if not wide:
             ragged_plan(shapes, "PCA", wide=False)  # the one-wave limits, by index
@@ -379,9 +522,14 @@ def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *,
     t = _device.require_gpu()
     dev = t.device(device) if device is not None else t.device("cuda", t.cuda.current_device())
     flat = np.concatenate([m.reshape(-1) for m in mats]) if B else np.zeros(0)
-    R, rep_d, sc_d, lo_d, hi_d, aux_d = _upload_packed(
+    km_host = km_books if isinstance(km_books, np.ndarray) else None  # (the host books ride in the one copy)
+    R, rep_d, sc_d, lo_d, hi_d, aux_d, km_d = _upload_packed(
         [(flat, np.float64), (rep, np.float64), (sc, np.uint8), (lo_, np.float64), (hi_, np.float64),
-         (aux, np.float64)], dev)
+         (aux, np.float64), (km_host, np.int32)], dev)
+    if km_books is not None and km_host is None:
+        if km_books.device != dev:
+            raise ValueError("the kmeans_init tensor is on %s, the call on %s" % (km_books.device, dev))
+        km_d = km_books  # read in place
     inp = _abi.Ragged(B, ns.ctypes.data, es.ctypes.data, _device.ptr(R), _device.ptr(rep_d), _device.ptr(sc_d),
                       _device.ptr(lo_d), _device.ptr(hi_d), int(bool(int_dtype)), alg, float(catch_tolerance),
                       float(alpha), int(max_components), float(variance_threshold), _device.ptr(aux_d),
@@ -406,6 +554,14 @@ def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *,
     if sets is None:
         entry = _lib.lib().pcx_consensus_ragged_wide_f64 if wide else _lib.lib().pcx_consensus_ragged_f64
         _lib.check(entry(h, C.byref(inp), C.byref(res)))
+    elif kmeans_init is not None:
+        arr = _params_array(sets)
+        # (a zero-length tensor's pointer is NULL: a batch without k-means rounds reads no book)
+        books = _abi.KmeansBooks(km_restarts, None if km_k is None else km_k.ctypes.data, _device.ptr(km_d))
+        _lib.check(_lib.lib().pcx_consensus_ragged_kmeans_f64(h, C.byref(inp), len(sets), C.cast(arr, C.c_void_p),
+                                                              param_of.ctypes.data, C.byref(books), C.byref(res)))
+        outs["_param_sets"], outs["_param_of"] = sets, param_of
+        outs["_kmeans_offsets"], outs["_kmeans_restarts"], outs["_kmeans_init"] = km_offsets, km_restarts, km_d
     else:
         arr = _params_array(sets)
         _lib.check(_lib.lib().pcx_consensus_ragged_params_f64(h, C.byref(inp), len(sets), C.cast(arr, C.c_void_p),
@@ -418,7 +574,7 @@ def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *,
     outs["_reporter_offsets"] = np.concatenate([zero, np.cumsum(ns, dtype=np.int64)])
     outs["_event_offsets"] = np.concatenate([zero, np.cumsum(es, dtype=np.int64)])
     outs["_cell_offsets"] = np.concatenate([zero, np.cumsum(ns.astype(np.int64) * es, dtype=np.int64)])
-    outs["_inputs"] = (R, rep_d, sc_d, lo_d, hi_d, aux_d)  # keep inputs alive until the caller syncs
+    outs["_inputs"] = (R, rep_d, sc_d, lo_d, hi_d, aux_d, km_d)  # keep inputs alive until the caller syncs
     return outs
 
 

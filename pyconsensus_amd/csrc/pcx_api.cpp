@@ -809,11 +809,12 @@ int pcx_consensus_ragged_wide_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_
 static_assert(sizeof(pcx_round_params) == sizeof(pcx::RoundParams), "pcx_round_params is the device entry");
 
 // why a parameter set is refused (the words of check_options / sweep_check), or NULL.  sim: a
-// simulator cell's set, where k-means and cokurtosis are not simulated.
-static const char* params_set_refusal(const pcx_round_params& q, bool sim) {
+// simulator cell's set, where k-means and cokurtosis are not simulated.  kmeans_ok: an entry that
+// takes code books (pcx_consensus_ragged_kmeans_f64).
+static const char* params_set_refusal(const pcx_round_params& q, bool sim, bool kmeans_ok = false) {
     if (q.algorithm < PCX_ALG_PCA || q.algorithm > PCX_ALG_CLUSTERFECK)
         return "algorithm must be an enum pcx_algorithm value (0..7)";
-    if (q.algorithm == PCX_ALG_KMEANS)
+    if (q.algorithm == PCX_ALG_KMEANS && !kmeans_ok)
         return sim ? "k-means is not simulated (its code books are drawn on the host)"
                    : "k-means is not supported (its code-book size depends on each round's N)";
     if (sim && q.algorithm == PCX_ALG_COKURTOSIS) return "cokurtosis is not simulated (it needs the caller's scores)";
@@ -885,7 +886,7 @@ static void params_count(int64_t B, const int32_t* n_reporters, const int32_t* n
 
 static int params_plan_check(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
                              const pcx_round_params* params, const int32_t* param_of, int64_t totals[3],
-                             int64_t* bad_round, int64_t* bad_param) {
+                             int64_t* bad_round, int64_t* bad_param, bool kmeans_ok = false) {
     if (bad_round) *bad_round = -1;
     if (bad_param) *bad_param = -1;
     if (n_rounds < 0 || n_rounds > 0x7fffffff) return fail(PCX_EINVAL, "ragged: n_rounds must be in [0, 2^31)");
@@ -895,7 +896,7 @@ static int params_plan_check(int64_t n_rounds, const int32_t* n_reporters, const
     if (n_params > 0 && !params) return fail(PCX_EINVAL, "ragged: params is NULL");
     if (n_rounds > 0 && !param_of) return fail(PCX_EINVAL, "ragged: param_of is NULL");
     for (int64_t q = 0; q < n_params; q++)
-        if (const char* why = params_set_refusal(params[q], false)) {
+        if (const char* why = params_set_refusal(params[q], false, kmeans_ok)) {
             if (bad_param) *bad_param = q;
             return fail(PCX_EINVAL, "ragged: parameter set " + std::to_string(q) + ": " + why);
         }
@@ -1013,6 +1014,158 @@ int pcx_consensus_ragged_params_f64(pcx_ctx* ctx, const pcx_ragged* in, int64_t 
     e = params_launch(ctx, p, a);
     if (e == hipSuccess) e = hipEventRecord(p.slot->kern_ev, ctx->stream);
     return e == hipSuccess ? PCX_OK : hip_fail(e, "ragged params launch");
+}
+
+// ---------------------------------------------------------------- k-means in ragged batches
+// the reference's code-book size int(ceil(sqrt(N))) (:396), in integers (N <= 256)
+static int kmeans_rule(int N) {
+    int k = 1;
+    while (k * k < N) k++;
+    return k;
+}
+
+// The flat book layout of the rounds whose set params[param_of[b]] is k-means (params NULL: every
+// round), of rounds whose
+// shapes the caller has checked: offsets[b] = the books before round b's, offsets[B] the length.
+// Refuses a k_b outside [1, min(N_b, 8)] within 64 x 32 (the one-wave kernel's code-book rows),
+// [1, min(N_b, 16)] above (the workgroup kernel's), with the round named.
+static int kmeans_layout(int64_t B, const int32_t* n_reporters, const int32_t* n_events, const int32_t* k, int restarts,
+                         const pcx_round_params* params, const int32_t* param_of, int64_t* offsets,
+                         pcx::KmeansEntry* entries, int64_t* bad_round, int64_t* total = nullptr) {
+    int64_t at = 0;
+    for (int64_t b = 0; b < B; b++) {
+        if (offsets) offsets[b] = at;
+        if (entries) entries[b] = pcx::KmeansEntry{0, 0, 0};
+        if (params && params[param_of[b]].algorithm != PCX_ALG_KMEANS) continue;
+        const int N = n_reporters[b], E = n_events[b];
+        const int kmax = std::min(N, N <= 64 && E <= 32 ? 8 : 16);
+        const int kb = k ? k[b] : kmeans_rule(N);
+        if (kb < 1 || kb > kmax) {
+            if (bad_round) *bad_round = b;
+            return fail(PCX_EINVAL, "k-means: round " + std::to_string(b) + " (" + std::to_string(N) + " x " +
+                                        std::to_string(E) + ") has a code book of " + std::to_string(kb) +
+                                        " rows; it must be within [1, " + std::to_string(kmax) + "]");
+        }
+        if (entries) entries[b] = pcx::KmeansEntry{at, kb, 0};
+        at += (int64_t)restarts * kb;
+    }
+    if (offsets) offsets[B] = at;
+    if (total) *total = at;
+    return PCX_OK;
+}
+
+int pcx_kmeans_plan(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, const int32_t* k,
+                    int32_t restarts, int64_t* offsets, int64_t* bad_round) {
+    if (bad_round) *bad_round = -1;
+    if (n_rounds < 0 || n_rounds > 0x7fffffff) return fail(PCX_EINVAL, "k-means: n_rounds must be in [0, 2^31)");
+    if (restarts < 1) return fail(PCX_EINVAL, "k-means: restarts must be >= 1");
+    if (n_rounds > 0 && (!n_reporters || !n_events)) return fail(PCX_EINVAL, "k-means: n_reporters / n_events is NULL");
+    for (int64_t b = 0; b < n_rounds; b++) {
+        const int32_t N = n_reporters[b], E = n_events[b];
+        if (N < 1 || N > 256 || E < 1 || E > 64) return ragged_bad_round(b, N, E, 256, 64, bad_round);
+    }
+    return kmeans_layout(n_rounds, n_reporters, n_events, k, restarts, nullptr, nullptr, offsets, nullptr, bad_round);
+}
+
+// pcx_ragged_plan_kmeans' checks; *any = some round's set is k-means
+static int kmeans_plan_check(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
+                             const pcx_round_params* params, const int32_t* param_of, const pcx_kmeans_books* books,
+                             int64_t totals[3], int64_t* offsets, pcx::KmeansEntry* entries, int64_t* bad_round,
+                             int64_t* bad_param, bool* any) {
+    if (const int rc = params_plan_check(n_rounds, n_reporters, n_events, n_params, params, param_of, totals, bad_round,
+                                         bad_param, true))
+        return rc;
+    bool some = false;
+    for (int64_t b = 0; b < n_rounds && !some; b++) some = params[param_of[b]].algorithm == PCX_ALG_KMEANS;
+    if (any) *any = some;
+    if (some && !books) return fail(PCX_EINVAL, "k-means: a round's set is k-means and books is NULL");
+    if (some && books->restarts < 1) return fail(PCX_EINVAL, "k-means: restarts must be >= 1");
+    return kmeans_layout(n_rounds, n_reporters, n_events, some ? books->k : nullptr, some ? books->restarts : 0, params,
+                         param_of, offsets, entries, bad_round);
+}
+
+int pcx_ragged_plan_kmeans(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
+                           const pcx_round_params* params, const int32_t* param_of, const pcx_kmeans_books* books,
+                           int64_t totals[3], int64_t* n_launches, int64_t* offsets, int64_t* bad_round,
+                           int64_t* bad_param) {
+    if (const int rc = kmeans_plan_check(n_rounds, n_reporters, n_events, n_params, params, param_of, books, totals,
+                                         offsets, nullptr, bad_round, bad_param, nullptr))
+        return rc;
+    if (n_launches) {
+        ParamsPlan p;
+        params_count(n_rounds, n_reporters, n_events, params, param_of, &p);
+        *n_launches = 0;
+        for (int s = 0; s < PARAMS_SEGMENTS; s++) *n_launches += p.cnt[s] > 0;
+    }
+    return PCX_OK;
+}
+
+// params_launch with the clustering segments (one-wave group 2, workgroup 6..8) on the k-means form
+// (books: the per-round book table on the device, somewhere in the slot's `extra` bytes)
+static hipError_t kmeans_launch(pcx_ctx* ctx, const ParamsPlan& p, const pcx::BatchArgs& a,
+                                const pcx::KmeansEntry* books) {
+    char* dev = static_cast<char*>(p.slot->dev);
+    const pcx::MediumDesc* d = reinterpret_cast<const pcx::MediumDesc*>(dev);
+    const pcx::RoundParams* tab = reinterpret_cast<const pcx::RoundParams*>(dev + p.off_p);
+    hipError_t e = hipSuccess;
+    for (int g = 0; g < 2 && e == hipSuccess; g++)
+        e = pcx::launch_ragged_params(a, d + p.first[g], tab, p.cnt[g], g, (size_t)p.lds[g], ctx->stream);
+    if (e == hipSuccess)
+        e = pcx::launch_ragged_kmeans(a, d + p.first[2], tab, books, p.cnt[2], (size_t)p.lds[2], ctx->stream);
+    if (p.nm == 0) return e;
+    double* Fscr = (double*)ctx->mscr;
+    double* Cscr = Fscr + (p.filled ? 0 : (size_t)p.chunk * p.stride[0]);
+    double* Xscr = Cscr + (size_t)p.chunk * p.stride[1];
+    for (int s = 3; s < PARAMS_SEGMENTS && e == hipSuccess; s++)
+        for (int64_t b0 = 0; b0 < p.cnt[s] && e == hipSuccess; b0 += p.chunk) {
+            const int64_t nb = std::min<int64_t>(p.chunk, p.cnt[s] - b0);
+            e = s >= 6 ? pcx::launch_ragged_medium_kmeans(a, d + p.first[s] + b0, tab, books, nb, (size_t)p.lds[s], p.stride,
+                                                          Fscr, Cscr, Xscr, ctx->stream)
+                       : pcx::launch_ragged_medium_params(a, d + p.first[s] + b0, tab, nb, false, (size_t)p.lds[s],
+                                                          p.stride, Fscr, Cscr, Xscr, ctx->stream);
+        }
+    return e;
+}
+
+int pcx_consensus_ragged_kmeans_f64(pcx_ctx* ctx, const pcx_ragged* in, int64_t n_params,
+                                    const pcx_round_params* params, const int32_t* param_of,
+                                    const pcx_kmeans_books* books, pcx_batch_result* out) {
+    if (!ctx || !in || !out) return fail(PCX_EINVAL, "pcx_consensus_ragged_kmeans_f64: null argument");
+    const int64_t B = in->n_rounds;
+    bool any = false;
+    // (the checks first, without a table: a refusal takes no staging slot)
+    if (const int rc = kmeans_plan_check(B, in->n_reporters, in->n_events, n_params, params, param_of, books, nullptr,
+                                         nullptr, nullptr, nullptr, nullptr, &any))
+        return rc;
+    if (B == 0) return PCX_OK;
+    if (!in->reports) return fail(PCX_EINVAL, "ragged: reports is NULL");
+    if (in->scaled && (!in->lo || !in->hi)) return fail(PCX_EINVAL, "ragged: scaled given without lo/hi");
+    if (any && !books->init) return fail(PCX_EINVAL, "k-means: books->init is NULL");
+    for (int64_t b = 0; b < B && !in->aux_scores; b++)
+        if (params[param_of[b]].algorithm == PCX_ALG_COKURTOSIS)
+            return fail(PCX_EINVAL, "ragged: parameter set " + std::to_string(param_of[b]) +
+                                        ": cokurtosis needs aux_scores (aux[\"cokurt\"])");
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    ParamsPlan p;
+    params_count(B, in->n_reporters, in->n_events, params, param_of, &p);
+    if (const int rc = params_tables(ctx, in->n_reporters, in->n_events, n_params, params, param_of,
+                                     out->filled != nullptr, (size_t)B * sizeof(pcx::KmeansEntry), &p))
+        return rc;
+    // the per-round book table, behind the parameter entries in the one upload
+    pcx::KmeansEntry* entries = reinterpret_cast<pcx::KmeansEntry*>(static_cast<char*>(p.slot->pin) + p.off_x);
+    if (const int rc = kmeans_layout(B, in->n_reporters, in->n_events, any ? books->k : nullptr, any ? books->restarts : 0,
+                                     params, param_of, nullptr, entries, nullptr))
+        return rc;
+    e = ragged_slot_upload(ctx, *p.slot, p.bytes);
+    if (e != hipSuccess) return hip_fail(e, "ragged: descriptor upload");
+    pcx::BatchArgs a = shared_args(in, out);
+    a.B = B;
+    a.kmeans_restarts = any ? books->restarts : 0;
+    a.kmeans_init = any ? books->init : nullptr;
+    e = kmeans_launch(ctx, p, a, reinterpret_cast<const pcx::KmeansEntry*>(static_cast<char*>(p.slot->dev) + p.off_x));
+    if (e == hipSuccess) e = hipEventRecord(p.slot->kern_ev, ctx->stream);
+    return e == hipSuccess ? PCX_OK : hip_fail(e, "ragged k-means launch");
 }
 
 namespace {
@@ -1215,7 +1368,8 @@ int pcx_test_inject_enomem(pcx_ctx* ctx, int worker) {
 // ---------------------------------------------------------------- Monte Carlo simulator
 namespace {
 // the argument checks every simulator entry shares (no device needed); 0 = ok
-int sim_check(const pcx_sim* s, const char* who) {
+// (kmeans_ok: an entry that draws the code books on the device)
+int sim_check(const pcx_sim* s, const char* who, bool kmeans_ok = false) {
     const std::string w = std::string(who) + ": ";
     if (s->n_rounds < 0 || s->n_rounds > 0x7fffffff) return fail(PCX_EINVAL, w + "n_rounds must be in [0, 2^31)");
     if (s->n_reporters < 1 || s->n_reporters > 0x7fffffff)
@@ -1235,7 +1389,7 @@ int sim_check(const pcx_sim* s, const char* who) {
         return fail(PCX_EINVAL, w + "scaled_tol must be finite and >= 0");
     if (s->algorithm < PCX_ALG_PCA || s->algorithm > PCX_ALG_CLUSTERFECK)
         return fail(PCX_EINVAL, w + "algorithm must be an enum pcx_algorithm value (0..7)");
-    if (s->algorithm == PCX_ALG_KMEANS)
+    if (s->algorithm == PCX_ALG_KMEANS && !kmeans_ok)
         return fail(PCX_EINVAL, w + "k-means is not simulated (its code books are drawn on the host)");
     if (s->algorithm == PCX_ALG_COKURTOSIS)
         return fail(PCX_EINVAL, w + "cokurtosis is not simulated (it needs the caller's scores)");
@@ -1326,9 +1480,30 @@ int pcx_sim_metrics_f64(pcx_ctx* ctx, const pcx_sim* sim, const pcx_sim_rounds* 
     return e == hipSuccess ? PCX_OK : hip_fail(e, "k_sim_metrics / k_sim_summary launch");
 }
 
-int pcx_simulate_f64(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* res) {
-    if (!ctx || !sim || !res) return fail(PCX_EINVAL, "pcx_simulate_f64: null argument");
-    if (const int rc = sim_check(sim, "pcx_simulate_f64")) return rc;
+// the reference's code-book size int(ceil(sqrt(N))) (:396) for any N, in integers
+static int64_t sim_kmeans_rule(int64_t N) {
+    int64_t k = 1;
+    while (k * k < N) k++;
+    return k;
+}
+
+// restarts / (rounds x restarts) that the books kernels take: one thread each, at most 2^31 - 1 workgroups
+static int sim_books_check(int64_t B, int restarts, const std::string& who) {
+    if (restarts < 1) return fail(PCX_EINVAL, who + ": k-means restarts must be >= 1");
+    if ((B * (int64_t)restarts + 255) / 256 > 0x7fffffff)
+        return fail(PCX_EINVAL, who + ": rounds x restarts is too large for one books launch");
+    return PCX_OK;
+}
+
+// The loop of pcx_simulate_f64 and pcx_simulate_kmeans_f64 (`who`).  restarts > 0: the latter, under
+// k-means -- every timestep's books are drawn into the workspace between the generator and the
+// batched launch, which reads them as kmeans_init.
+static int simulate_run(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* res, int restarts, const char* who) {
+    if (const int rc = sim_check(sim, who, restarts > 0)) return rc;
+    const bool km = restarts > 0 && sim->algorithm == PCX_ALG_KMEANS;
+    const int64_t kk = km ? sim_kmeans_rule(sim->n_reporters) : 0;
+    if (km)
+        if (const int rc = sim_books_check(sim->n_rounds, restarts, who)) return rc;
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     const int64_t B = sim->n_rounds, N = sim->n_reporters, E = sim->n_events, T = sim->n_timesteps;
@@ -1337,7 +1512,11 @@ int pcx_simulate_f64(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* res) {
     // (ping-pong: a timestep reads one as its reputation and writes the other), metrics; then
     // the bytes scaled and liar
     const size_t n_f64 = bn * E + 4 * be + 3 * bn + (size_t)B * PCX_SIM_NMETRICS;
-    if (const int rc = sim_reserve(ctx, std::max<size_t>(n_f64 * sizeof(double) + be + bn, 16))) return rc;
+    // (k-means: the books [B][restarts][k] int32 behind the bytes, on a 4-byte boundary)
+    const size_t off_books = (n_f64 * sizeof(double) + be + bn + 3) / 4 * 4;
+    const size_t n_books = km ? (size_t)B * restarts * kk : 0;
+    if (const int rc = sim_reserve(ctx, std::max<size_t>(off_books + n_books * sizeof(int32_t), 16))) return rc;
+    int32_t* const w_books = reinterpret_cast<int32_t*>(static_cast<char*>(ctx->sim_buf) + off_books);
     double* p = (double*)ctx->sim_buf;
     auto take = [&p](size_t n) {
         double* q = p;
@@ -1392,6 +1571,13 @@ int pcx_simulate_f64(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* res) {
         in.variance_threshold = sim->variance_threshold;
         in.hierarchy_threshold = sim->hierarchy_threshold;
         in.cluster_threshold = sim->cluster_threshold;
+        if (km) {
+            e = pcx::launch_sim_kmeans_books(g, B, (int)N, (int)kk, restarts, (uint32_t)t, w_books, ctx->stream);
+            if (e != hipSuccess) return hip_fail(e, "k_kmeans_books launch");
+            in.kmeans_k = (int32_t)kk;
+            in.kmeans_restarts = restarts;
+            in.kmeans_init = w_books;
+        }
         if (const int rc = pcx_consensus_batched_f64(ctx, &in, &o)) return rc;
         if (res->metrics || res->summary) {
             double* m = res->metrics ? res->metrics + (size_t)t * B * PCX_SIM_NMETRICS : w_metrics;
@@ -1410,6 +1596,42 @@ int pcx_simulate_f64(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* res) {
     return PCX_OK;
 }
 
+int pcx_simulate_f64(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* res) {
+    if (!ctx || !sim || !res) return fail(PCX_EINVAL, "pcx_simulate_f64: null argument");
+    return simulate_run(ctx, sim, res, 0, "pcx_simulate_f64");
+}
+
+int pcx_simulate_kmeans_f64(pcx_ctx* ctx, const pcx_sim* sim, int32_t restarts, pcx_sim_result* res) {
+    if (!ctx || !sim || !res) return fail(PCX_EINVAL, "pcx_simulate_kmeans_f64: null argument");
+    if (restarts < 1) return fail(PCX_EINVAL, "pcx_simulate_kmeans_f64: k-means restarts must be >= 1");
+    return simulate_run(ctx, sim, res, restarts, "pcx_simulate_kmeans_f64");
+}
+
+int pcx_sim_kmeans_books_host(const pcx_sim* sim, int32_t restarts, int timestep, int32_t* books) {
+    const char* who = "pcx_sim_kmeans_books_host";
+    if (!sim || !books) return fail(PCX_EINVAL, std::string(who) + ": null argument");
+    if (const int rc = sim_check(sim, who, true)) return rc;
+    if (const int rc = sim_check_timestep(timestep, who)) return rc;
+    if (const int rc = sim_books_check(sim->n_rounds, restarts, who)) return rc;
+    pcx::sim_kmeans_books_host(sim_gen(sim), sim->n_rounds, (int)sim->n_reporters, (int)sim_kmeans_rule(sim->n_reporters),
+                               restarts, (uint32_t)timestep, books);
+    return PCX_OK;
+}
+
+int pcx_sim_kmeans_books_f64(pcx_ctx* ctx, const pcx_sim* sim, int32_t restarts, int timestep, int32_t* books) {
+    const char* who = "pcx_sim_kmeans_books_f64";
+    if (!ctx || !sim || !books) return fail(PCX_EINVAL, std::string(who) + ": null argument");
+    if (const int rc = sim_check(sim, who, true)) return rc;
+    if (const int rc = sim_check_timestep(timestep, who)) return rc;
+    if (const int rc = sim_books_check(sim->n_rounds, restarts, who)) return rc;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    e = pcx::launch_sim_kmeans_books(sim_gen(sim), sim->n_rounds, (int)sim->n_reporters,
+                                     (int)sim_kmeans_rule(sim->n_reporters), restarts, (uint32_t)timestep, books,
+                                     ctx->stream);
+    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_kmeans_books launch");
+}
+
 // ---------------------------------------------------------------- simulator sweeps
 namespace {
 int sweep_fail(int64_t* bad_cell, int64_t c, const char* who, const std::string& why) {
@@ -1421,8 +1643,9 @@ int sweep_fail(int64_t* bad_cell, int64_t c, const char* who, const std::string&
 // (*bad_cell = -1), then cell after cell.  Fills what pcx_sim_sweep_plan reports; 0 = ok.
 // cp: per-cell parameter sets [C] (NULL: the shared parameters) -- the shared ones are then neither
 // read nor checked, each cell's set is checked with the cell, and its rounds count by its algorithm.
+// kmeans_ok: an entry that draws the code books on the device -- k-means passes, shared or in a set.
 int sweep_check(const pcx_sim_sweep* s, const char* who, int64_t totals[4], int64_t counts[4], int64_t lds_bytes[4],
-                int64_t* bad_cell, const pcx_round_params* cp = nullptr) {
+                int64_t* bad_cell, const pcx_round_params* cp = nullptr, bool kmeans_ok = false) {
     if (bad_cell) *bad_cell = -1;
     if (s->n_cells < 0) return sweep_fail(bad_cell, -1, who, "n_cells must be >= 0");
     if (s->n_cells > 0 && !s->cells) return sweep_fail(bad_cell, -1, who, "cells is NULL");
@@ -1434,7 +1657,7 @@ int sweep_check(const pcx_sim_sweep* s, const char* who, int64_t totals[4], int6
         // (each cell's own set, below)
     } else if (s->algorithm < PCX_ALG_PCA || s->algorithm > PCX_ALG_CLUSTERFECK)
         return sweep_fail(bad_cell, -1, who, "algorithm must be an enum pcx_algorithm value (0..7)");
-    else if (s->algorithm == PCX_ALG_KMEANS)
+    else if (s->algorithm == PCX_ALG_KMEANS && !kmeans_ok)
         return sweep_fail(bad_cell, -1, who, "k-means is not simulated (its code books are drawn on the host)");
     else if (s->algorithm == PCX_ALG_COKURTOSIS)
         return sweep_fail(bad_cell, -1, who, "cokurtosis is not simulated (it needs the caller's scores)");
@@ -1466,7 +1689,7 @@ int sweep_check(const pcx_sim_sweep* s, const char* who, int64_t totals[4], int6
             if (!(q.p >= 0.0 && q.p <= 1.0))  // false for NaN too
                 return sweep_fail(bad_cell, c, who, std::string(q.name) + " must be a probability in [0, 1]");
         if (cp)
-            if (const char* why = params_set_refusal(cp[c], true)) return sweep_fail(bad_cell, c, who, why);
+            if (const char* why = params_set_refusal(cp[c], true, kmeans_ok)) return sweep_fail(bad_cell, c, who, why);
         const int algorithm = cp ? cp[c].algorithm : s->algorithm;
         const int64_t R = k.n_rounds, N = k.n_reporters, E = k.n_events;
         tot[0] += R;
@@ -1622,11 +1845,26 @@ static int study_check(const pcx_sim_sweep* s, const int32_t* pair_base, const c
 // detail launch, and one statistics launch follows the last timestep.  cp: per-cell parameter sets
 // [C] (NULL: the sweep's shared ones) -- the consensus launches are then those of
 // pcx_consensus_ragged_params_f64, round b of cell c on set c.
+// restarts > 0 (pcx_simulate_study_kmeans_f64): k-means passes; the call runs on parameter sets (the
+// shared parameters as every cell's set where cp is NULL), every timestep's books of the k-means
+// cells' rounds are drawn into the workspace behind the generator, and the consensus launches are
+// those of pcx_consensus_ragged_kmeans_f64.
 static int sweep_run(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* res, const int32_t* pair_base,
-                     const pcx_sim_study_result* study, const char* who, const pcx_round_params* cp = nullptr) {
+                     const pcx_sim_study_result* study, const char* who, const pcx_round_params* cp = nullptr,
+                     int restarts = 0) {
     const std::string name(who);
     int64_t tot[4], cnt[4], lds[4];
-    if (const int rc = sweep_check(sweep, who, tot, cnt, lds, nullptr, cp)) return rc;
+    const bool km = restarts > 0;
+    if (const int rc = sweep_check(sweep, who, tot, cnt, lds, nullptr, cp, km)) return rc;
+    std::vector<pcx_round_params> own_cp;
+    if (km && !cp) {
+        own_cp.assign((size_t)sweep->n_cells,
+                      pcx_round_params{sweep->algorithm, sweep->max_components, sweep->catch_tolerance, sweep->alpha,
+                                       sweep->variance_threshold, sweep->hierarchy_threshold, sweep->cluster_threshold});
+        cp = own_cp.data();
+    }
+    if (km)
+        if (const int rc = sim_books_check(tot[0], restarts, name)) return rc;
     if (study) {
         if (const int rc = study_check(sweep, pair_base, who, nullptr)) return rc;
         if (study->paired && !pair_base) return fail(PCX_EINVAL, name + ": paired needs pair_base");
@@ -1660,7 +1898,14 @@ static int sweep_run(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* r
     const size_t n_metrics = (size_t)(all_metrics ? T : 1) * B * PCX_SIM_NMETRICS;
     const size_t n_detail = study && !study->detail ? (size_t)T * B * PCX_SIM_NDETAIL : 0;
     const size_t n_f64 = bne + 4 * be + 3 * bn + n_metrics + n_detail;
-    if (const int rc = sim_reserve(ctx, std::max<size_t>(n_f64 * sizeof(double) + be + bn, 16))) return rc;
+    // (k-means: the flat books of the k-means cells' rounds, int32, behind the bytes)
+    int64_t n_books = 0;
+    if (km)
+        if (const int rc = kmeans_layout(B, nrep, nev, nullptr, restarts, cp, pof, nullptr, nullptr, nullptr, &n_books))
+            return rc;
+    const size_t off_books = (n_f64 * sizeof(double) + be + bn + 3) / 4 * 4;
+    if (const int rc = sim_reserve(ctx, std::max<size_t>(off_books + (size_t)n_books * sizeof(int32_t), 16))) return rc;
+    int32_t* const w_books = reinterpret_cast<int32_t*>(static_cast<char*>(ctx->sim_buf) + off_books);
     double* p = (double*)ctx->sim_buf;
     auto take = [&p](size_t n) {
         double* q = p;
@@ -1684,7 +1929,8 @@ static int sweep_run(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* r
     WidePlan plan;
     ParamsPlan pplan;
     const bool pairs = study && study->paired;
-    const size_t extra = sweep_table_bytes(sweep) + (pairs ? pair_base_bytes(sweep) : 0);
+    const size_t off_ktab = sweep_table_bytes(sweep) + (pairs ? pair_base_bytes(sweep) : 0);  // inside `extra`
+    const size_t extra = off_ktab + (km ? (size_t)B * sizeof(pcx::KmeansEntry) : 0);
     if (cp) {
         params_count(B, nrep, nev, cp, pof, &pplan);
         if (const int rc = params_tables(ctx, nrep, nev, C, cp, pof, false, extra, &pplan)) return rc;
@@ -1700,6 +1946,12 @@ static int sweep_run(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* r
         const size_t at = off_x + sweep_table_bytes(sweep);
         std::memcpy(static_cast<char*>(slot->pin) + at, pair_base, (size_t)C * sizeof(int32_t));
         dev_base = reinterpret_cast<const int32_t*>(static_cast<char*>(slot->dev) + at);
+    }
+    const pcx::KmeansEntry* dev_ktab = nullptr;  // the per-round book table rides last
+    if (km) {
+        (void)kmeans_layout(B, nrep, nev, nullptr, restarts, cp, pof, nullptr,
+                            reinterpret_cast<pcx::KmeansEntry*>(static_cast<char*>(slot->pin) + off_x + off_ktab), nullptr);
+        dev_ktab = reinterpret_cast<const pcx::KmeansEntry*>(static_cast<char*>(slot->dev) + off_x + off_ktab);
     }
     e = ragged_slot_upload(ctx, *slot, up_bytes);
     if (e != hipSuccess) return hip_fail(e, "sweep: table upload");
@@ -1739,7 +1991,13 @@ static int sweep_run(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* r
         in.cluster_threshold = sweep->cluster_threshold;
         pcx::BatchArgs a = shared_args(&in, &o);
         a.B = B;
-        e = cp ? params_launch(ctx, pplan, a) : wide_launch(ctx, plan, a);
+        if (km && n_books > 0) {
+            e = pcx::launch_sim_sweep_kmeans_books(tab, dev_ktab, restarts, (uint32_t)t, w_books, ctx->stream);
+            if (e != hipSuccess) return hip_fail(e, "k_kmeans_books_sweep launch");
+            a.kmeans_restarts = restarts;
+            a.kmeans_init = w_books;
+        }
+        e = km ? kmeans_launch(ctx, pplan, a, dev_ktab) : cp ? params_launch(ctx, pplan, a) : wide_launch(ctx, plan, a);
         if (e != hipSuccess) return hip_fail(e, "sweep: ragged wide launch");
         if (res->metrics || res->summary || study) {
             double* m = res->metrics   ? res->metrics + (size_t)t * B * PCX_SIM_NMETRICS
@@ -1799,6 +2057,86 @@ int pcx_simulate_study_params_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, cons
     if (!cell_params)  // the existing entries, the same bytes
         return study ? pcx_simulate_study_f64(ctx, sweep, pair_base, res, study) : pcx_simulate_sweep_f64(ctx, sweep, res);
     return sweep_run(ctx, sweep, res, study ? pair_base : nullptr, study, "pcx_simulate_study_params_f64", cell_params);
+}
+
+int pcx_sim_study_kmeans_check(const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,
+                               const int32_t* pair_base, int32_t restarts, int64_t* bad_cell) {
+    const char* who = "pcx_sim_study_kmeans_check";
+    if (!sweep) return fail(PCX_EINVAL, std::string(who) + ": null argument");
+    if (bad_cell) *bad_cell = -1;
+    if (restarts < 1) return fail(PCX_EINVAL, std::string(who) + ": k-means restarts must be >= 1");
+    int64_t tot[4];
+    if (const int rc = sweep_check(sweep, who, tot, nullptr, nullptr, bad_cell, cell_params, true)) return rc;
+    if (const int rc = sim_books_check(tot[0], restarts, who)) return rc;
+    return study_check(sweep, pair_base, who, bad_cell);
+}
+
+int pcx_simulate_study_kmeans_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,
+                                  const int32_t* pair_base, int32_t restarts, pcx_sim_result* res,
+                                  pcx_sim_study_result* study) {
+    if (!ctx || !sweep || !res) return fail(PCX_EINVAL, "pcx_simulate_study_kmeans_f64: null argument");
+    if (restarts < 1) return fail(PCX_EINVAL, "pcx_simulate_study_kmeans_f64: k-means restarts must be >= 1");
+    return sweep_run(ctx, sweep, res, study ? pair_base : nullptr, study, "pcx_simulate_study_kmeans_f64", cell_params,
+                     restarts);
+}
+
+// the book table of a sweep whose every round is k-means under the rule (pcx_kmeans_plan's layout)
+static int sweep_books_table(const pcx_sim_sweep* sweep, int restarts, const char* who, std::vector<char>* cells,
+                             std::vector<pcx::KmeansEntry>* tab, int64_t* B) {
+    int64_t tot[4];
+    if (const int rc = sweep_check(sweep, who, tot, nullptr, nullptr, nullptr, nullptr, true)) return rc;
+    if (const int rc = sim_books_check(tot[0], restarts, who)) return rc;
+    *B = tot[0];
+    cells->resize(sweep_table_bytes(sweep));
+    sweep_tables_fill(sweep, cells->data(), cells->data());
+    tab->resize((size_t)tot[0]);
+    std::vector<int32_t> shape((size_t)tot[0] * 2);
+    for (int64_t c = 0, b = 0; c < sweep->n_cells; c++)
+        for (int64_t r = 0; r < sweep->cells[c].n_rounds; r++, b++) {
+            shape[b] = sweep->cells[c].n_reporters;
+            shape[tot[0] + b] = sweep->cells[c].n_events;
+        }
+    return kmeans_layout(tot[0], shape.data(), shape.data() + tot[0], nullptr, restarts, nullptr, nullptr, nullptr,
+                         tab->data(), nullptr);
+}
+
+int pcx_sim_sweep_kmeans_books_host(const pcx_sim_sweep* sweep, int32_t restarts, int timestep, int32_t* books) {
+    const char* who = "pcx_sim_sweep_kmeans_books_host";
+    if (!sweep || !books) return fail(PCX_EINVAL, std::string(who) + ": null argument");
+    if (const int rc = sim_check_timestep(timestep, who)) return rc;
+    std::vector<char> cells;
+    std::vector<pcx::KmeansEntry> tab;
+    int64_t B = 0;
+    if (const int rc = sweep_books_table(sweep, restarts, who, &cells, &tab, &B)) return rc;
+    pcx::sim_sweep_kmeans_books_host(reinterpret_cast<const pcx::SweepCell*>(cells.data()), sweep->n_cells, tab.data(),
+                                     restarts, (uint32_t)timestep, books);
+    return PCX_OK;
+}
+
+int pcx_sim_sweep_kmeans_books_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, int32_t restarts, int timestep,
+                                   int32_t* books) {
+    const char* who = "pcx_sim_sweep_kmeans_books_f64";
+    if (!ctx || !sweep || !books) return fail(PCX_EINVAL, std::string(who) + ": null argument");
+    if (const int rc = sim_check_timestep(timestep, who)) return rc;
+    std::vector<char> cells;
+    std::vector<pcx::KmeansEntry> tab;
+    int64_t B = 0;
+    if (const int rc = sweep_books_table(sweep, restarts, who, &cells, &tab, &B)) return rc;
+    if (B == 0) return PCX_OK;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    // the sweep's tables and the book table through one staging slot
+    const size_t tb = sweep_table_bytes(sweep), kb = (size_t)B * sizeof(pcx::KmeansEntry);
+    pcx_ctx::RaggedSlot* slot = nullptr;
+    if (const int rc = ragged_slot_take(ctx, tb + kb, &slot)) return rc;
+    const pcx::SweepTables t = sweep_tables_fill(sweep, slot->pin, slot->dev);
+    std::memcpy(static_cast<char*>(slot->pin) + tb, tab.data(), kb);
+    e = ragged_slot_upload(ctx, *slot, tb + kb);
+    if (e != hipSuccess) return hip_fail(e, "sweep: table upload");
+    e = pcx::launch_sim_sweep_kmeans_books(t, reinterpret_cast<const pcx::KmeansEntry*>(static_cast<char*>(slot->dev) + tb),
+                                           restarts, (uint32_t)timestep, books, ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(slot->kern_ev, ctx->stream);
+    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_kmeans_books_sweep launch");
 }
 
 int pcx_sim_study_check(const pcx_sim_sweep* sweep, const int32_t* pair_base, int64_t* bad_cell) {

@@ -24,14 +24,26 @@
 // descriptor: read once, held in scalar registers, written over the seven parameter fields of a
 // local copy `a` of the kernel argument `ka`, which the text below reads as it reads the argument in
 // the other two forms.  (out_args() still reads the output pointers from the argument itself.)
-#if PCX_ROUND_RAGGED == 2
+//
+// k-means (PCX_ROUND_RAGGED 3, pcx_batched_kmeans.hip: ragged_kmeans_round_kernel, DESIGN.md 5.5.2):
+// the per-round-parameter form with one more wave-uniform read, the round's entry {offset, k} of a
+// device table KmeansEntry[B] indexed by the round: the local copy's kmeans_k becomes the round's
+// code-book size and its kmeans_init the round's own books in the flat array (kmeans_restarts is the
+// call's, in the argument), so kmeans_nc reads them as it does in the equal-shape form, as round 0.
+#if PCX_ROUND_RAGGED >= 2
 #define PCX_ROUND_CELL0 rcell
 #define PCX_ROUND_ROW0 rrow
 #define PCX_ROUND_EV0 rev
 #define PCX_ROUND_B rround
 template <int NT, int ET, bool CLUS, bool PK>
+#if PCX_ROUND_RAGGED == 3
+__global__ void __launch_bounds__(64, 3) ragged_kmeans_round_kernel(BatchArgs ka, const MediumDesc* __restrict__ rag,
+                                                                    const RoundParams* __restrict__ ptab,
+                                                                    const KmeansEntry* __restrict__ ktab) {
+#else
 __global__ void __launch_bounds__(64, 3) ragged_params_round_kernel(BatchArgs ka, const MediumDesc* __restrict__ rag,
                                                                     const RoundParams* __restrict__ ptab) {
+#endif
     static_assert(NT == 0 && ET == 0, "a ragged launch has no compiled shape");
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const MediumDesc* const rd = rag + blockIdx.x;
@@ -47,6 +59,11 @@ __global__ void __launch_bounds__(64, 3) ragged_params_round_kernel(BatchArgs ka
     a.variance_threshold = uniform_f64(rp->variance_threshold);
     a.hierarchy_threshold = uniform_f64(rp->hierarchy_threshold);
     a.cluster_threshold = uniform_f64(rp->cluster_threshold);
+#if PCX_ROUND_RAGGED == 3
+    const KmeansEntry* const ke = ktab + rround;
+    a.kmeans_k = __builtin_amdgcn_readfirstlane(ke->k);
+    a.kmeans_init = ka.kmeans_init + uniform64(ke->offset);
+#endif
 #elif PCX_ROUND_RAGGED
 #define PCX_ROUND_CELL0 rcell
 #define PCX_ROUND_ROW0 rrow
@@ -554,6 +571,9 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
 #if !PCX_ROUND_RAGGED  // (a ragged launch refuses k-means: its code-book size depends on the round's N)
             else if (alg == 5)
                 nc_i = kmeans_nc(a, b, S.F, S.mu, ES, N, E, X);
+#elif PCX_ROUND_RAGGED == 3  // (the round's own books: a.kmeans_init points at them)
+            else if (alg == 5)
+                nc_i = kmeans_nc(a, 0, S.F, S.mu, ES, N, E, X);
 #endif
             else
                 nc_i = feck_nc(a, S.F, ES, N, E, rep, X);

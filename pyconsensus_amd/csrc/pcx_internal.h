@@ -296,6 +296,23 @@ hipError_t launch_ragged_medium_params(const BatchArgs& a, const MediumDesc* des
                                        bool clus, size_t lds, const int64_t s[3], double* Fscr, double* Cscr,
                                        double* Xscr, hipStream_t st);
 
+// k-means in ragged batches (pcx_consensus_ragged_kmeans_f64): round b's entry of a
+// device table [B] -- where its restarts x k code-book rows start in the call's flat book array, and
+// k ({0, 0} for a round of another algorithm, unread).  The clustering launches of that call run the
+// two ragged kernels in a form that reads it (ragged_kmeans_round_kernel, ragged_kmeans_medium_kernel);
+// BatchArgs.kmeans_init is the flat array and kmeans_restarts the call's.
+struct KmeansEntry {
+    int64_t offset;
+    int32_t k, pad;
+};
+static_assert(sizeof(KmeansEntry) == 16, "k-means book entry");
+// launch_ragged_params' group 2 / launch_ragged_medium_params' clus = true with the book table
+hipError_t launch_ragged_kmeans(const BatchArgs& a, const MediumDesc* desc, const RoundParams* params,
+                                const KmeansEntry* books, int64_t nb, size_t lds, hipStream_t st);
+hipError_t launch_ragged_medium_kmeans(const BatchArgs& a, const MediumDesc* desc, const RoundParams* params,
+                                       const KmeansEntry* books, int64_t nb, size_t lds, const int64_t s[3],
+                                       double* Fscr, double* Cscr, double* Xscr, hipStream_t st);
+
 // ---------------------------------------------------------------- Monte Carlo simulator (pcx_sim.hip)
 // one timestep's rounds on the device / on the host (the same inline generator, pcx_sim.h)
 hipError_t launch_sim_generate(const sim::Gen& g, int64_t B, int64_t N, int64_t E, uint32_t t,

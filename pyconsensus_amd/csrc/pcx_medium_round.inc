@@ -22,6 +22,11 @@
 // RoundParams[P] written over the seven parameter fields of a local copy `a` of the kernel argument
 // `ka` (workgroup-uniform, scalar registers, like the descriptor).  Everything below reads `a`: the
 // LDS carve, the work region, the scratch slots and the layout follow the round's own algorithm.
+//
+// k-means (PCX_MEDIUM_RAGGED 3, pcx_medium_kmeans.hip: ragged_kmeans_medium_kernel, DESIGN.md 5.5.2):
+// that form with the round's entry {offset, k} of a device table KmeansEntry[B], indexed by the
+// round, written over the copy's kmeans_k and added to its kmeans_init: mkmeans_nc reads the round's
+// own books as round 0's.
 #if PCX_MEDIUM_RAGGED
 #define PCX_MROUND_CELL0 rcell
 #define PCX_MROUND_ROW0 rrow
@@ -32,7 +37,11 @@
 #define PCX_MROUND_XSLOT ((int64_t)blockIdx.x * sX)
 #define PCX_MROUND_ARGS ar
 template <bool CLUS>
-#if PCX_MEDIUM_RAGGED == 2
+#if PCX_MEDIUM_RAGGED == 3
+__global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) ragged_kmeans_medium_kernel(
+    BatchArgs ka, const MediumDesc* __restrict__ rag, const RoundParams* __restrict__ ptab,
+    const KmeansEntry* __restrict__ ktab, int64_t sF, int64_t sC, int64_t sX, double* Fscr, double* Cscr, double* Xscr) {
+#elif PCX_MEDIUM_RAGGED == 2
 __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) ragged_params_medium_kernel(
     BatchArgs ka, const MediumDesc* __restrict__ rag, const RoundParams* __restrict__ ptab, int64_t sF, int64_t sC,
     int64_t sX, double* Fscr, double* Cscr, double* Xscr) {
@@ -48,7 +57,7 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) ragged_medium_kernel(Bat
     const int N = __builtin_amdgcn_readfirstlane(rd->N), E = __builtin_amdgcn_readfirstlane(rd->E), ES = E + 1;
     const int64_t b = __builtin_amdgcn_readfirstlane(rd->round);  // round; scratch slot blockIdx.x
     const int64_t rcell = muniform64(rd->cell), rrow = muniform64(rd->row), rev = muniform64(rd->ev);
-#if PCX_MEDIUM_RAGGED == 2
+#if PCX_MEDIUM_RAGGED >= 2
     const RoundParams* const rp = ptab + __builtin_amdgcn_readfirstlane(rd->param);
     BatchArgs a = ka;
     a.algorithm = __builtin_amdgcn_readfirstlane(rp->algorithm);
@@ -58,6 +67,11 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) ragged_medium_kernel(Bat
     a.variance_threshold = muniform_f64(rp->variance_threshold);
     a.hierarchy_threshold = muniform_f64(rp->hierarchy_threshold);
     a.cluster_threshold = muniform_f64(rp->cluster_threshold);
+#endif
+#if PCX_MEDIUM_RAGGED == 3
+    const KmeansEntry* const ke = ktab + b;
+    a.kmeans_k = __builtin_amdgcn_readfirstlane(ke->k);
+    a.kmeans_init = ka.kmeans_init + muniform64(ke->offset);
 #endif
     BatchArgs ar = a;  // what component_scores reads: the round's shape, max_components capped (:134-137)
     ar.N = N;
@@ -542,6 +556,9 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(Batc
 #if !PCX_MEDIUM_RAGGED  // (a ragged launch refuses k-means: its code-book size depends on the round's N)
         else if (alg == PCX_ALG_KMEANS)
             mkmeans_nc(a, b, F, VEp(VE_MU), N, E, X, mlds, nc, scal);
+#elif PCX_MEDIUM_RAGGED == 3  // (the round's own books: a.kmeans_init points at them)
+        else if (alg == PCX_ALG_KMEANS)
+            mkmeans_nc(a, 0, F, VEp(VE_MU), N, E, X, mlds, nc, scal);
 #endif
         else
             mfeck_nc(a, F, tok, N, E, X, mlds, nc, scal);

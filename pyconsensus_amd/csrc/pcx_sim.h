@@ -17,7 +17,7 @@
 namespace pcx {
 namespace sim {
 
-enum stream { EVENT_A = 0, EVENT_B = 1, EVENT_C = 2, REPORTER = 3, CELL = 4 };
+enum stream { EVENT_A = 0, EVENT_B = 1, EVENT_C = 2, REPORTER = 3, CELL = 4, KMEANS = 5 };
 enum liar_bit { LIAR = 1, COLLUDES = 2 };  // the liar[B][N] flags
 
 // What the generator needs of a pcx_sim: the key and the decision thresholds
@@ -124,6 +124,22 @@ PCX_SIM_HD double cell(const Gen& g, const Event& e, uint8_t who, uint32_t b, ui
     const double rv = e.scaled ? in_range(e.lo, e.hi, frac(u)) : (u < 0.5 ? 1.0 : 2.0);
     if (who & LIAR) return (who & COLLUDES) ? e.lie : rv;
     return decide(c.w1, g.thr_distort) ? rv : e.truth;
+}
+
+// The initial code book of k-means restart r of round b at timestep t: k distinct
+// rows of [0, N) by Floyd's sampling, one draw of the KMEANS stream per code -- for c = 0 .. k - 1,
+// j = N - k + c, v = (w * (j + 1)) >> 32 a row of [0, j], and the code is v unless an earlier code
+// is v already, then j (which no earlier code can be).  Every k-subset is equally likely up to the
+// multiply-shift's bias of at most (j + 1) / 2^32.  Integers only.  1 <= k <= N.
+PCX_SIM_HD void kmeans_book(const Gen& g, uint32_t b, uint32_t r, uint32_t t, int N, int k, int32_t* book) {
+    for (int c = 0; c < k; c++) {
+        const uint32_t j = (uint32_t)(N - k + c);
+        const uint32_t w = draw(g, (uint32_t)c, r, b, KMEANS, t).w0;
+        const int32_t v = (int32_t)(((uint64_t)w * (j + 1)) >> 32);
+        bool seen = false;
+        for (int q = 0; q < c; q++) seen |= book[q] == v;
+        book[c] = seen ? (int32_t)j : v;
+    }
 }
 
 }  // namespace sim

@@ -57,4 +57,18 @@ hipError_t launch_sim_sweep_metrics(const SweepTables& s, double scaled_tol, con
 // summary [C][PCX_SIM_NMETRICS]: each cell's means over its rounds, in k_sim_summary's order
 hipError_t launch_sim_sweep_summary(const SweepTables& s, const double* metrics, double* summary, hipStream_t st);
 
+
+// k-means code books from the generator's KMEANS stream (pcx_sim_kmeans.hip), on the
+// device and on the host, bit for bit.  Rounds of one shape: books [B][restarts][k].  A sweep: round
+// b's [restarts][tab[b].k] rows at tab[b].offset of the flat array (k = 0: no book), drawn under its
+// cell's key with the round's index inside the cell.
+struct KmeansEntry;
+hipError_t launch_sim_kmeans_books(const sim::Gen& g, int64_t B, int N, int k, int restarts, uint32_t t,
+                                   int32_t* books, hipStream_t st);
+void sim_kmeans_books_host(const sim::Gen& g, int64_t B, int N, int k, int restarts, uint32_t t, int32_t* books);
+hipError_t launch_sim_sweep_kmeans_books(const SweepTables& s, const KmeansEntry* tab, int restarts, uint32_t t,
+                                         int32_t* books, hipStream_t st);
+void sim_sweep_kmeans_books_host(const SweepCell* cells, int64_t C, const KmeansEntry* tab, int restarts, uint32_t t,
+                                 int32_t* books);
+
 }  // namespace pcx

@@ -10,8 +10,8 @@ from __future__ import annotations
 import numpy as np
 
 from . import _abi
-from .batched import (MAX_EVENTS, MAX_REPORTERS, WIDE_MAX_EVENTS, WIDE_MAX_REPORTERS, consensus_ragged, ragged_round,
-                      ragged_to_host)
+from .batched import (MAX_EVENTS, MAX_REPORTERS, WIDE_MAX_EVENTS, WIDE_MAX_REPORTERS, consensus_ragged,
+                      kmeans_draws_ragged, ragged_round, ragged_to_host)
 from .oracle import Oracle
 
 _SHARED = ("catch_tolerance", "alpha", "algorithm", "variance_threshold", "hierarchy_threshold", "device")
@@ -24,12 +24,20 @@ def consensus_many(problems, wide=False, **oracle_kwargs):
               ``reputation``, ``aux`` for cokurtosis, ...)
     Returns the list of result dicts, in order; each equals that problem's own
     ``Oracle(...).consensus()`` in values and container types (the dicts are built by the same code).
-    A problem above 64 x 32, and every problem under ``algorithm="k-means"`` (whose restarts draw from
-    numpy's global RandomState call by call), goes through ``Oracle`` itself, in list order.
+    A problem above 64 x 32 goes through ``Oracle`` itself, in list order.
+
+    ``algorithm="k-means"``: the problems within the limits join the ragged groups like the others
+    (``consensus_ragged(kmeans_init=...)``; ``last_info["path"] == "ragged"``).  The reference draws
+    every restart's code book from numpy's global RandomState call by call, so the draws are made in
+    list order, whichever path a problem takes: a k-means problem of a group draws its books
+    (:func:`pyconsensus_amd.batched.kmeans_draws_ragged`) where its turn comes, and one too large for
+    the batch runs through ``Oracle`` at its place in the list.  After ``np.random.seed(s)`` the call
+    therefore returns what the ``Oracle`` loop returns after the same seed, and leaves
+    ``np.random.get_state()`` where the loop leaves it.
 
     wide=True: problems up to 256 x 64 join the ragged groups as well (``consensus_ragged(wide=True)``,
-    one workgroup per such problem; ``last_info["path"] == "ragged"``); k-means and larger problems
-    still go through ``Oracle``.  What changes for a problem above 64 x 32: it runs in the batched
+    one workgroup per such problem; ``last_info["path"] == "ragged"``); larger problems still go
+    through ``Oracle``.  What changes for a problem above 64 x 32: it runs in the batched
     SPEC's operation order -- what ``consensus_batched`` gives that shape -- where ``Oracle`` gives it
     the single-matrix pipeline's order.  Its discrete outputs are equal; its continuous ones agree
     within the parity tolerances of the test suite (tests/parity.py), not bit for bit -- which is why
@@ -37,15 +45,20 @@ def consensus_many(problems, wide=False, **oracle_kwargs):
     max_n, max_e = (WIDE_MAX_REPORTERS, WIDE_MAX_EVENTS) if wide else (MAX_REPORTERS, MAX_EVENTS)
     oracles = [Oracle(**p, **oracle_kwargs) for p in problems]
     results = [None] * len(oracles)
-    groups, alone = {}, []
+    groups, alone, books = {}, [], {}
     for i, (p, o) in enumerate(zip(problems, oracles)):
         if o.algorithm not in _abi.ALGORITHMS:
             raise NotImplementedError("algorithm %r is not on the GPU path (supported: %s)"
                                       % (o.algorithm, ", ".join(sorted(_abi.ALGORITHMS))))
-        if (o.num_reports > max_n or o.num_events > max_e or o.algorithm == "k-means"
+        if (o.num_reports > max_n or o.num_events > max_e
                 or o.num_reports < 1 or o.num_events < 1 or o.devices is not None):
-            alone.append(i)
+            if o.algorithm == "k-means":  # its draws come now, in list order
+                results[i] = o.consensus()
+            else:
+                alone.append(i)
             continue
+        if o.algorithm == "k-means":  # this problem's draws, in list order
+            books[i] = kmeans_draws_ragged([o.num_reports])[0]
         # (the problems' own max_components: each Oracle holds it capped at its E already)
         mc = p.get("max_components", oracle_kwargs.get("max_components", 5))
         key = (o._int_dtype, o.event_bounds is not None, o._rep_raw is not None, mc) + tuple(
@@ -64,6 +77,8 @@ def consensus_many(problems, wide=False, **oracle_kwargs):
             if any(a.size != oracles[i].num_reports for a, i in zip(aux, idx)):
                 raise ValueError("aux['cokurt'] must hold one score per reporter")
             kw["aux_scores"] = aux
+        if first.algorithm == "k-means":
+            kw["kmeans_init"] = [books[i] for i in idx]
         out = consensus_ragged([oracles[i]._data for i in idx], filled=True, original=True,
                                int_dtype=first._int_dtype, algorithm=first.algorithm,
                                catch_tolerance=first.catch_tolerance, alpha=first.alpha, max_components=key[3],

@@ -21,6 +21,10 @@ of every round and timestep (did the consensus punish the liars? what kind of wr
 outcome?), every value's per-cell ``{n, mean, var, min, max}`` and, against a base cell, the paired
 differences in which common random numbers pay off (``pcx_simulate_study_f64``).
 ``--stats`` and ``--paired`` print them.
+
+"k-means" is simulated where ``kmeans_restarts`` is given (``--algorithm k-means`` on the command line):
+its restarts' initial code books are drawn on the device from a further stream of the generator
+(:func:`kmeans_books`, with the CPU twin :func:`kmeans_books_host`).
 """
 from __future__ import annotations
 
@@ -130,7 +134,7 @@ def metrics(rounds, old_rep, smooth_rep, outcomes_final, scaled_tol=0.1, device=
 def simulate(B, N=50, E=20, T=1, seed=0, liar_frac=0.3, collude_frac=0.5, distort=0.1, na_frac=0.1,
              scaled_frac=0.25, scaled_tol=0.1, reputation=None, algorithm="PCA", catch_tolerance=0.1,
              alpha=0.1, max_components=5, variance_threshold=0.9, hierarchy_threshold=0.5,
-             cluster_threshold=None, keep_rounds=False, keep_outputs=False, device=None):
+             cluster_threshold=None, keep_rounds=False, keep_outputs=False, device=None, kmeans_restarts=None):
     """T timesteps of B random N x E rounds on the GPU: generate, consensus, score, carry.
 
     Timestep t draws its rounds (liars stay the same people through the trajectory), runs the
@@ -145,8 +149,13 @@ def simulate(B, N=50, E=20, T=1, seed=0, liar_frac=0.3, collude_frac=0.5, distor
 
     Stream semantics are ``consensus_batched``'s: rounds up to 256 x 64 are asynchronous on
     torch's current stream with no host in the loop, "hierarchical" and "clusterfeck" included
-    (one workgroup per round above 64 x 32) -- synchronise before reading on the host; "k-means"
-    and "cokurtosis" are refused (they need host draws / caller scores)."""
+    (one workgroup per round above 64 x 32) -- synchronise before reading on the host; "cokurtosis"
+    is refused (it needs caller scores), and so is "k-means" unless ``kmeans_restarts`` is given.
+
+    ``kmeans_restarts`` (an int >= 1; None = today's refusal): "k-means" runs, its initial code books
+    drawn on the device every timestep from a further stream of the generator
+    (``pcx_simulate_kmeans_f64``) -- :func:`kmeans_books` shows them, and timestep t
+    equals ``consensus_batched(kmeans_init=kmeans_books(...))`` on :func:`generate`'s rounds."""
     tc = _device.require_gpu()
     dev = tc.device(device) if device is not None else tc.device("cuda", tc.cuda.current_device())
     rep = _device.as_device(reputation, tc.float64, dev)
@@ -174,9 +183,40 @@ def simulate(B, N=50, E=20, T=1, seed=0, liar_frac=0.3, collude_frac=0.5, distor
             setattr(res.last_out, name, outs[name].data_ptr())
         out["outputs"] = outs
     h = _lib.bind_stream(dev.index, _device.current_stream_handle(dev))
-    _lib.check(_lib.lib().pcx_simulate_f64(h, C.byref(s), C.byref(res)))
+    if kmeans_restarts is None:
+        _lib.check(_lib.lib().pcx_simulate_f64(h, C.byref(s), C.byref(res)))
+    else:
+        _lib.check(_lib.lib().pcx_simulate_kmeans_f64(h, C.byref(s), int(kmeans_restarts), C.byref(res)))
     out["_inputs"] = (rep,)  # alive until the caller syncs
     return out
+
+
+def kmeans_books_host(B, N, t=0, seed=0, restarts=_abi.KMEANS_RESTARTS):
+    """The initial k-means code books of timestep ``t`` drawn on the CPU (``pcx_sim_kmeans_books_host``;
+    no GPU needed): int32 ``(B, restarts, k)`` with k = ceil(sqrt(N)), every book k distinct rows of
+    [0, N) -- bit for bit what :func:`kmeans_books` writes on the device and what
+    ``simulate(algorithm="k-means", kmeans_restarts=restarts)`` reads at that timestep."""
+    from .batched import kmeans_k
+
+    s = _sim(B, N, 1, max(1, int(t) + 1), seed, 0.0, 0.0, 0.0, 0.0, 0.0)
+    books = np.empty((max(int(B), 0), max(int(restarts), 0), kmeans_k(int(N)) if int(N) >= 1 else 0), dtype=np.int32)
+    _lib.check(_lib.lib().pcx_sim_kmeans_books_host(C.byref(s), int(restarts), int(t), books.ctypes.data))
+    return books
+
+
+def kmeans_books(B, N, t=0, seed=0, restarts=_abi.KMEANS_RESTARTS, device=None):
+    """:func:`kmeans_books_host` on the device (``pcx_sim_kmeans_books_f64``): an int32 tensor
+    ``(B, restarts, k)``.  Asynchronous on torch's current stream."""
+    from .batched import kmeans_k
+
+    tc = _device.require_gpu()
+    dev = tc.device(device) if device is not None else tc.device("cuda", tc.cuda.current_device())
+    s = _sim(B, N, 1, max(1, int(t) + 1), seed, 0.0, 0.0, 0.0, 0.0, 0.0)
+    books = tc.empty((max(int(B), 0), max(int(restarts), 0), kmeans_k(int(N)) if int(N) >= 1 else 0), dtype=tc.int32,
+                     device=dev)
+    h = _lib.bind_stream(dev.index, _device.current_stream_handle(dev))
+    _lib.check(_lib.lib().pcx_sim_kmeans_books_f64(h, C.byref(s), int(restarts), int(t), books.data_ptr()))
+    return books
 
 
 # ---------------------------------------------------------------- sweeps
@@ -310,6 +350,43 @@ def sweep_generate(cells, t=0, fields=None, device=None):
     return rounds
 
 
+def _sweep_books_offsets(norm, restarts):
+    """int64 [B + 1]: where each round's ``restarts x k`` book rows start in a sweep's flat book array
+    (``pcx_kmeans_plan`` over the sweep's rounds, the rule's k)."""
+    from .batched import kmeans_plan
+
+    shapes = [(int(d["reporters"]), int(d["events"])) for d in norm for _ in range(int(d["rounds"]))]
+    return kmeans_plan(shapes, restarts)
+
+
+def sweep_kmeans_books_host(cells, t=0, restarts=_abi.KMEANS_RESTARTS):
+    """The k-means code books of timestep ``t`` of every round of a sweep, on the CPU
+    (``pcx_sim_sweep_kmeans_books_host``; no GPU needed): ``(books, offsets)`` -- a flat int32 array,
+    round b's ``(restarts, ceil(sqrt(N_c)))`` rows at ``offsets[b]`` (int64 [B + 1]), drawn under its
+    cell's seed with the round's index inside the cell: cell c's slice is that cell's own
+    :func:`kmeans_books_host`."""
+    s, arr, norm, _ = _sweep(cells, max(1, int(t) + 1))
+    _lib.check(_lib.lib().pcx_sim_study_kmeans_check(C.byref(s), None, None, int(restarts), C.byref(C.c_int64(-2))))
+    offsets = _sweep_books_offsets(norm, restarts)
+    books = np.empty(int(offsets[-1]), dtype=np.int32)
+    _lib.check(_lib.lib().pcx_sim_sweep_kmeans_books_host(C.byref(s), int(restarts), int(t), books.ctypes.data))
+    return books, offsets
+
+
+def sweep_kmeans_books(cells, t=0, restarts=_abi.KMEANS_RESTARTS, device=None):
+    """:func:`sweep_kmeans_books_host` on the device (``pcx_sim_sweep_kmeans_books_f64``): a flat int32
+    tensor and the numpy offsets.  Asynchronous on torch's current stream."""
+    tc = _device.require_gpu()
+    dev = tc.device(device) if device is not None else tc.device("cuda", tc.cuda.current_device())
+    s, arr, norm, _ = _sweep(cells, max(1, int(t) + 1))
+    _lib.check(_lib.lib().pcx_sim_study_kmeans_check(C.byref(s), None, None, int(restarts), C.byref(C.c_int64(-2))))
+    offsets = _sweep_books_offsets(norm, restarts)
+    books = tc.empty(int(offsets[-1]), dtype=tc.int32, device=dev)
+    h = _lib.bind_stream(dev.index, _device.current_stream_handle(dev))
+    _lib.check(_lib.lib().pcx_sim_sweep_kmeans_books_f64(h, C.byref(s), int(restarts), int(t), books.data_ptr()))
+    return books, offsets
+
+
 def sweep_metrics(cells, rounds, old_rep, smooth_rep, outcomes_final, scaled_tol=0.1, summary=True, device=None):
     """Score a sweep's flat rounds (``pcx_sim_sweep_metrics_f64``): ``metrics (B,6)`` and, unless
     ``summary`` is false, ``summary (C,6)``, every cell's means over its rounds."""
@@ -339,7 +416,7 @@ def sweep_metrics(cells, rounds, old_rep, smooth_rep, outcomes_final, scaled_tol
 
 def sweep(cells, T=1, scaled_tol=0.1, algorithm="PCA", catch_tolerance=0.1, alpha=0.1, max_components=5,
           variance_threshold=0.9, hierarchy_threshold=0.5, cluster_threshold=None, reputation=None,
-          keep_rounds=False, keep_outputs=False, device=None):
+          keep_rounds=False, keep_outputs=False, device=None, kmeans_restarts=None):
     """T timesteps of a whole study in one call: C cells, each with its own rounds, shape, rates and seed.
 
     ``cells`` is a list of dicts (or tuples, from the left) with ``rounds``, ``reporters``, ``events``,
@@ -365,16 +442,22 @@ def sweep(cells, T=1, scaled_tol=0.1, algorithm="PCA", catch_tolerance=0.1, alph
     ``reputation`` in: a flat starting reputation or None (uniform).  ``keep_rounds`` /
     ``keep_outputs`` add the last timestep's flat ``rounds`` / consensus ``outputs``.
 
+    ``kmeans_restarts`` (an int >= 1; None = k-means refused, as before) lets "k-means" in, shared or as
+    a cell's own ``algorithm`` (``pcx_simulate_study_kmeans_f64``): the books of the
+    k-means cells' rounds are drawn on the device every timestep, under the cell's seed, and a k-means
+    cell is byte for byte its own ``simulate(..., algorithm="k-means", kmeans_restarts=...)``.
+
     Asynchronous on torch's current stream, with no host wait between the timesteps.  A sweep runs
     the generic ragged kernels: a study of ONE shape belongs on :func:`simulate`, whose compiled
     equal-shape kernel is faster."""
     return _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_components, variance_threshold,
-                      hierarchy_threshold, cluster_threshold, reputation, keep_rounds, keep_outputs, device)
+                      hierarchy_threshold, cluster_threshold, reputation, keep_rounds, keep_outputs, device,
+                      kmeans_restarts=kmeans_restarts)
 
 
 def _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_components, variance_threshold,
                hierarchy_threshold, cluster_threshold, reputation, keep_rounds, keep_outputs, device,
-               with_study=False, pair_with=None, keep_detail=False):
+               with_study=False, pair_with=None, keep_detail=False, kmeans_restarts=None):
     """:func:`sweep` (``pcx_simulate_sweep_f64``) or, ``with_study``, :func:`study` (``pcx_simulate_study_f64``)."""
     tc = _device.require_gpu()
     dev = tc.device(device) if device is not None else tc.device("cuda", tc.cuda.current_device())
@@ -386,7 +469,13 @@ def _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_comp
                   cluster_threshold=cluster_threshold)
     cp = _cell_params(norm, **shared)  # None: no cell has parameters of its own
     st = base = None
-    if cp is None:
+    km = kmeans_restarts is not None
+    if km:  # one check of the cells, their sets (k-means allowed), the restarts and the pairing
+        base = pair_base(norm, pair_with) if with_study else None
+        _lib.check(_lib.lib().pcx_sim_study_kmeans_check(C.byref(s), None if cp is None else C.cast(cp, C.c_void_p),
+                                                         None if base is None else base.ctypes.data,
+                                                         int(kmeans_restarts), C.byref(C.c_int64(-2))))
+    elif cp is None:
         sweep_plan(cells, T, scaled_tol=scaled_tol, **shared)  # refuses by cell
     else:  # one check of the cells, their parameter sets and the pairing
         base = pair_base(norm, pair_with) if with_study else None
@@ -413,7 +502,7 @@ def _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_comp
             setattr(res.last_out, name, outs[name].data_ptr())
         out["outputs"] = outs
     if with_study:
-        if cp is None:
+        if cp is None and not km:
             base = study_check(norm, pair_with, T, algorithm=algorithm, scaled_tol=scaled_tol,
                                max_components=max_components)  # refuses by cell
         st = _abi.SimStudyResult()
@@ -427,7 +516,11 @@ def _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_comp
             out["detail"] = tc.empty((T, B, _abi.SIM_NDETAIL), dtype=tc.float64, device=dev)
             st.detail = out["detail"].data_ptr()
     h = _lib.bind_stream(dev.index, _device.current_stream_handle(dev))
-    if cp is not None:
+    if km:
+        _lib.check(_lib.lib().pcx_simulate_study_kmeans_f64(
+            h, C.byref(s), None if cp is None else C.cast(cp, C.c_void_p), None if base is None else base.ctypes.data,
+            int(kmeans_restarts), C.byref(res), None if st is None else C.byref(st)))
+    elif cp is not None:
         _lib.check(_lib.lib().pcx_simulate_study_params_f64(
             h, C.byref(s), C.cast(cp, C.c_void_p), None if base is None else base.ctypes.data, C.byref(res),
             None if st is None else C.byref(st)))
@@ -636,7 +729,7 @@ def sweep_stats(cells, metrics, detail, pair_with=None, device=None):
 
 def study(cells, T=1, pair_with=None, keep_detail=False, scaled_tol=0.1, algorithm="PCA", catch_tolerance=0.1,
           alpha=0.1, max_components=5, variance_threshold=0.9, hierarchy_threshold=0.5, cluster_threshold=None,
-          reputation=None, keep_rounds=False, keep_outputs=False, device=None):
+          reputation=None, keep_rounds=False, keep_outputs=False, device=None, kmeans_restarts=None):
     """:func:`sweep` with a study's result (``pcx_simulate_study_f64``): every key of
     :func:`sweep`'s dict, byte for byte, plus
 
@@ -654,10 +747,12 @@ def study(cells, T=1, pair_with=None, keep_detail=False, scaled_tol=0.1, algorit
 
     The detail metrics are written on the device inside the loop (one more launch per timestep), the
     statistics by one launch after the last timestep; the call stays asynchronous on torch's current
-    stream with no host wait.  Refusals are :func:`sweep`'s and :func:`study_check`'s."""
+    stream with no host wait.  Refusals are :func:`sweep`'s and :func:`study_check`'s.
+    ``kmeans_restarts`` as in :func:`sweep`: with it a cell may be k-means, and ``pair_with="first"``
+    pairs a PCA cell and a k-means cell of one seed and shape on the same drawn rounds."""
     return _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_components, variance_threshold,
                       hierarchy_threshold, cluster_threshold, reputation, keep_rounds, keep_outputs, device,
-                      with_study=True, pair_with=pair_with, keep_detail=keep_detail)
+                      with_study=True, pair_with=pair_with, keep_detail=keep_detail, kmeans_restarts=kmeans_restarts)
 
 
 def stderr(stats_or_paired):
@@ -720,6 +815,8 @@ def main(argv=None):
     ap.add_argument("--scaled-tol", type=float, default=0.1)
     ap.add_argument("--algorithm", type=_comma_list(str), default=["PCA"],
                     help="a comma list runs every cell under each algorithm, in one call")
+    ap.add_argument("--kmeans-restarts", type=int, default=None,
+                    help="restarts of every k-means round (default 20 where --algorithm names k-means)")
     ap.add_argument("--alpha", type=flt, default=None, help="the reputation smoothing (or a comma list)")
     ap.add_argument("--catch", type=flt, default=None, help="catch_tolerance (or a comma list)")
     ap.add_argument("--stats", action="store_true",
@@ -739,6 +836,8 @@ def main(argv=None):
             lists[key] = values
         elif values is not None:
             a.shared[key] = values[0]
+    if a.kmeans_restarts is not None or "k-means" in a.algorithm:  # naming k-means enables it
+        a.shared["kmeans_restarts"] = _abi.KMEANS_RESTARTS if a.kmeans_restarts is None else a.kmeans_restarts
     a.algorithm = ",".join(a.algorithm)
     if a.stats or a.paired:
         return _main_study(a, lists)
