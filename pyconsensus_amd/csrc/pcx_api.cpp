@@ -1,27 +1,26 @@
-// pcx_api.cpp -- the extern "C" boundary of libpcx (declared in include/pcx.h).
-// Host-side validation, context/stream management and kernel launches; no
-// compute happens here.
+// pcx_api.cpp -- the extern "C" boundary of libpcx (declared in include/pcx.h): contexts, streams and
+// communicators, the single-matrix entries, pcx_consensus_batched_f64, profiling and the self-test
+// shims.  The ragged entries are in pcx_ragged.cpp, the simulator's in pcx_simulate.cpp; what the
+// three share is in pcx_host.h.  Host-side validation and kernel launches; no compute happens here.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
+#include <algorithm>
+#include <atomic>
 #include <cstdio>
-#include <cstring>
+#include <cstdlib>
 #include <new>
 #include <string>
-#include <vector>
-#include <cstdlib>
-#include <atomic>
 #include <thread>
-#include <algorithm>
+#include <vector>
 
 #include "../../include/pcx.h"
+#include "pcx_host.h"
 #include "pcx_internal.h"
-#include "pcx_sim_study.h"
-#include "pcx_sim_sweep.h"
-#include "pcx_sync.h"
 #include "pcx_seqsum.h"
+#include "pcx_sync.h"
 
-namespace {
+namespace pcx {
+namespace host __attribute__((visibility("hidden"))) {
 thread_local std::string g_err;
 
 int fail(int code, const std::string& msg) {
@@ -33,77 +32,6 @@ int hip_fail(hipError_t e, const char* what) {
     return fail(PCX_EHIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-// The option checks that pcx_consensus_batched_f64 ("batched") and pcx_consensus_ragged_f64
-// ("ragged") share, in the order both make them.  `own` is what the entry's own checks found (the
-// algorithm's range, k-means, big-five; NULL: nothing): they follow reports / scaled and precede
-// catch_tolerance / alpha, and each of them, like each check here that names an algorithm, can
-// only fire alone, so one place among those serves both entries.
-template <class In>
-int check_options(const char* who, const In* in, const char* own) {
-    auto refuse = [who](const char* why) { return fail(PCX_EINVAL, std::string(who) + ": " + why); };
-    if (!in->reports) return refuse("reports is NULL");
-    if (in->scaled && (!in->lo || !in->hi)) return refuse("scaled given without lo/hi");
-    if (own) return refuse(own);
-    if (in->algorithm == PCX_ALG_HIERARCHICAL && std::isnan(in->hierarchy_threshold))
-        return refuse("hierarchy_threshold is NaN");
-    if (in->algorithm == PCX_ALG_FIXED_VARIANCE && !std::isfinite(in->variance_threshold))
-        return refuse("variance_threshold must be finite");
-    if (in->algorithm == PCX_ALG_COKURTOSIS && !in->aux_scores)
-        return refuse("cokurtosis needs aux_scores (aux[\"cokurt\"])");
-    if (!std::isfinite(in->catch_tolerance) || !std::isfinite(in->alpha))
-        return refuse("catch_tolerance/alpha must be finite");
-    return PCX_OK;
-}
-
-// what pcx_batch and pcx_ragged both carry: the inputs, the algorithm's options and every output
-template <class In>
-pcx::BatchArgs shared_args(const In* in, const pcx_batch_result* out) {
-    pcx::BatchArgs a{};
-    a.reports = in->reports;
-    a.reputation = in->reputation;
-    a.scaled = in->scaled;
-    a.lo = in->lo;
-    a.hi = in->hi;
-    a.int_dtype = in->int_dtype;
-    a.algorithm = in->algorithm;
-    a.max_components = in->max_components;
-    a.variance_threshold = in->variance_threshold;
-    a.aux_scores = in->aux_scores;
-    a.hierarchy_threshold = in->hierarchy_threshold;
-    a.cluster_threshold = in->cluster_threshold;
-    a.catch_tol = in->catch_tolerance;
-    a.alpha = in->alpha;
-    a.old_rep = out->old_rep;
-    a.this_rep = out->this_rep;
-    a.smooth_rep = out->smooth_rep;
-    a.scores = out->scores;
-    a.na_row = out->na_row;
-    a.participation_rows = out->participation_rows;
-    a.relative_part = out->relative_part;
-    a.reporter_bonus = out->reporter_bonus;
-    a.adj_first_loadings = out->adj_first_loadings;
-    a.outcomes_raw = out->outcomes_raw;
-    a.outcomes_adjusted = out->outcomes_adjusted;
-    a.outcomes_final = out->outcomes_final;
-    a.certainty = out->certainty;
-    a.consensus_reward = out->consensus_reward;
-    a.nas_filled = out->nas_filled;
-    a.participation_columns = out->participation_columns;
-    a.author_bonus = out->author_bonus;
-    a.participation = out->participation;
-    a.avg_certainty = out->avg_certainty;
-    a.branch = out->branch;
-    a.flags = out->flags;
-    a.pi_iters = out->pi_iters;
-    a.components = out->components;
-    a.original = out->original;
-    a.filled = out->filled;
-    return a;
-}
-
-// The PCX_STAMPS diagnostic's buffer (per-phase shader clocks, [B][32]): allocated and zeroed on
-// the stream when the variable is "1" -- a.stamps stays NULL otherwise, and when there are no rounds
-// or no memory -- then, after the launches, read back (the stream is synchronised) and freed.
 void stamps_begin(pcx::BatchArgs& a, hipStream_t stream) {
     const char* env = getenv("PCX_STAMPS");
     if (!env || env[0] != '1' || a.B <= 0) return;
@@ -123,7 +51,21 @@ std::vector<long long> stamps_end(pcx::BatchArgs& a, hipStream_t stream) {
     a.stamps = nullptr;
     return h;
 }
-}  // namespace
+
+// the context's workgroup scratch (pcx_ctx.mscr) grown to `need` bytes; 0 = ok
+int medium_scratch_reserve(pcx_ctx* ctx, size_t need) {
+    if (ctx->mscr_bytes >= need) return PCX_OK;
+    if (ctx->mscr) (void)hipFree(ctx->mscr);
+    ctx->mscr = nullptr;
+    ctx->mscr_bytes = 0;
+    const hipError_t e = hipMalloc(&ctx->mscr, need);
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc(medium scratch)");
+    ctx->mscr_bytes = need;
+    return PCX_OK;
+}
+}  // namespace host
+}  // namespace pcx
+using namespace pcx::host;
 
 extern "C" {
 
@@ -429,21 +371,6 @@ static void print_medium_stamps(const std::vector<long long>& h, int64_t B) {
     fprintf(stderr, " pi: presq:%.0f steps:%.0f\n", pw[0] / (double)B, pw[1] / (double)B);
 }
 
-// one workgroup per round (pcx_medium.hip), in chunks of bounded scratch
-constexpr size_t MEDIUM_SCRATCH_CAP = (size_t)2 << 30;
-
-// the context's workgroup scratch (pcx_ctx.mscr) grown to `need` bytes; 0 = ok
-static int medium_scratch_reserve(pcx_ctx* ctx, size_t need) {
-    if (ctx->mscr_bytes >= need) return PCX_OK;
-    if (ctx->mscr) (void)hipFree(ctx->mscr);
-    ctx->mscr = nullptr;
-    ctx->mscr_bytes = 0;
-    const hipError_t e = hipMalloc(&ctx->mscr, need);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(medium scratch)");
-    ctx->mscr_bytes = need;
-    return PCX_OK;
-}
-
 static int run_workgroup_route(pcx_ctx* ctx, pcx::BatchArgs& a) {
     const int64_t chunk = pcx::medium_chunk(a, MEDIUM_SCRATCH_CAP);
     if (const int rc = medium_scratch_reserve(ctx, pcx::medium_scratch_per_round(a) * (size_t)chunk)) return rc;
@@ -500,672 +427,6 @@ int pcx_consensus_batched_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_resul
     e = pcx::launch_batched(a, ctx->stream);
     if (a.stamps) print_wave_stamps(stamps_end(a, ctx->stream), a.B);
     return e == hipSuccess ? PCX_OK : hip_fail(e, "batched_round_kernel launch");
-}
-
-// ---------------------------------------------------------------- ragged batches
-// what pcx_ragged_plan and pcx_ragged_plan_wide refuse alike, before they look at a round
-static int ragged_plan_checks(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int algorithm,
-                              int64_t* bad_round) {
-    if (bad_round) *bad_round = -1;
-    if (n_rounds < 0 || n_rounds > 0x7fffffff) return fail(PCX_EINVAL, "ragged: n_rounds must be in [0, 2^31)");
-    if (algorithm < PCX_ALG_PCA || algorithm > PCX_ALG_CLUSTERFECK)
-        return fail(PCX_EINVAL, "ragged: algorithm must be an enum pcx_algorithm value (0..7)");
-    if (algorithm == PCX_ALG_KMEANS)
-        return fail(PCX_EINVAL, "ragged: k-means is not supported (its code-book size depends on each round's N)");
-    if (n_rounds > 0 && (!n_reporters || !n_events)) return fail(PCX_EINVAL, "ragged: n_reporters / n_events is NULL");
-    return PCX_OK;
-}
-
-static int ragged_bad_round(int64_t b, int N, int E, int max_n, int max_e, int64_t* bad_round) {
-    if (bad_round) *bad_round = b;
-    return fail(PCX_EINVAL, "ragged: round " + std::to_string(b) + " is " + std::to_string(N) + " x " +
-                                std::to_string(E) + "; a round must be within [1, " + std::to_string(max_n) +
-                                "] x [1, " + std::to_string(max_e) + "]");
-}
-
-int pcx_ragged_plan(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int algorithm,
-                    int64_t totals[3], int64_t* lds_bytes, int64_t* bad_round) {
-    if (const int rc = ragged_plan_checks(n_rounds, n_reporters, n_events, algorithm, bad_round)) return rc;
-    int64_t tn = 0, te = 0, tc = 0;
-    size_t lds = 0;
-    for (int64_t b = 0; b < n_rounds; b++) {
-        const int32_t N = n_reporters[b], E = n_events[b];
-        if (N < 1 || N > 64 || E < 1 || E > 32) return ragged_bad_round(b, N, E, 64, 32, bad_round);
-        tn += N;
-        te += E;
-        tc += (int64_t)N * E;
-        lds = std::max(lds, pcx::ragged_lds_bytes(N, E, algorithm));
-    }
-    if (totals) {
-        totals[0] = tn;
-        totals[1] = te;
-        totals[2] = tc;
-    }
-    if (lds_bytes) *lds_bytes = (int64_t)lds;
-    return PCX_OK;
-}
-
-// This call's staging slot (the two are taken in turn), with room for `bytes` on both sides and the
-// host side free to be rewritten: the slot's last upload has read it.  0 = ok.
-static int ragged_slot_take(pcx_ctx* ctx, size_t bytes, pcx_ctx::RaggedSlot** slot) {
-    hipError_t e = hipSuccess;
-    pcx_ctx::RaggedSlot& s = ctx->rag[ctx->rag_next];
-    ctx->rag_next ^= 1;
-    *slot = &s;
-    if (s.used) {  // the slot's last upload has read the staging
-        e = hipEventSynchronize(s.copy_ev);
-        if (e != hipSuccess) return hip_fail(e, "ragged: hipEventSynchronize");
-    }
-    if (!s.copy_ev) {
-        e = hipEventCreateWithFlags(&s.copy_ev, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.kern_ev, hipEventDisableTiming);
-        if (e != hipSuccess) return hip_fail(e, "ragged: hipEventCreate");
-    }
-    if (s.bytes < bytes) {
-        if (s.used) {  // the slot's last launch has read the table
-            e = hipEventSynchronize(s.kern_ev);
-            if (e != hipSuccess) return hip_fail(e, "ragged: hipEventSynchronize");
-        }
-        if (s.pin) (void)hipHostFree(s.pin);
-        if (s.dev) (void)hipFree(s.dev);
-        s.pin = s.dev = nullptr;
-        s.bytes = 0;
-        s.used = false;
-        const size_t cap = std::max(bytes + bytes / 2, (size_t)4096);
-        e = hipHostMalloc(&s.pin, cap, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc(&s.dev, cap);
-        if (e != hipSuccess) {
-            if (s.pin) (void)hipHostFree(s.pin);
-            s.pin = nullptr;
-            return fail(e == hipErrorOutOfMemory ? PCX_ENOMEM : PCX_EHIP,
-                        std::string("ragged: descriptor table: ") + hipGetErrorString(e));
-        }
-        s.bytes = cap;
-    }
-    return PCX_OK;
-}
-
-// The slot's first `bytes` from the staging to the device table on the stream, after any launch
-// that still reads the table (another stream's, maybe); copy_ev marks the staging read.
-static hipError_t ragged_slot_upload(pcx_ctx* ctx, pcx_ctx::RaggedSlot& s, size_t bytes) {
-    hipError_t e = hipSuccess;
-    if (s.used) e = hipStreamWaitEvent(ctx->stream, s.kern_ev, 0);
-    if (e == hipSuccess) e = hipMemcpyAsync(s.dev, s.pin, bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipEventRecord(s.copy_ev, ctx->stream);
-    if (e == hipSuccess) s.used = true;
-    return e;
-}
-
-int pcx_consensus_ragged_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_result* out) {
-    if (!ctx || !in || !out) return fail(PCX_EINVAL, "pcx_consensus_ragged_f64: null argument");
-    int64_t lds = 0;
-    if (const int rc = pcx_ragged_plan(in->n_rounds, in->n_reporters, in->n_events, in->algorithm, nullptr, &lds,
-                                       nullptr))
-        return rc;
-    if (in->n_rounds == 0) return PCX_OK;
-    // (max_components is capped at E_b per round on the device)
-    const bool bad_five = in->algorithm == PCX_ALG_BIG_FIVE && in->max_components < 1;
-    if (const int rc = check_options("ragged", in, bad_five ? "big-five needs max_components >= 1" : nullptr))
-        return rc;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    // the descriptor table: built in this call's staging slot, uploaded on the stream
-    const int64_t B = in->n_rounds;
-    const size_t bytes = (size_t)B * sizeof(pcx::RaggedDesc);
-    pcx_ctx::RaggedSlot* sp = nullptr;
-    if (const int rc = ragged_slot_take(ctx, bytes, &sp)) return rc;
-    pcx_ctx::RaggedSlot& s = *sp;
-    pcx::RaggedDesc* d = static_cast<pcx::RaggedDesc*>(s.pin);
-    int64_t cell = 0, row = 0, ev = 0;
-    for (int64_t b = 0; b < B; b++) {
-        const int32_t N = in->n_reporters[b], E = in->n_events[b];
-        d[b] = pcx::RaggedDesc{cell, row, ev, N, E};
-        cell += (int64_t)N * E;
-        row += N;
-        ev += E;
-    }
-    e = ragged_slot_upload(ctx, s, bytes);
-    if (e != hipSuccess) return hip_fail(e, "ragged: descriptor upload");
-    pcx::BatchArgs a = shared_args(in, out);
-    a.B = B;
-    e = pcx::launch_ragged(a, static_cast<const pcx::RaggedDesc*>(s.dev), (size_t)lds, ctx->stream);
-    if (e == hipSuccess) e = hipEventRecord(s.kern_ev, ctx->stream);
-    return e == hipSuccess ? PCX_OK : hip_fail(e, "ragged_round_kernel launch");
-}
-
-// where a round of a wide ragged batch runs: 0 = the one-wave kernel, else the workgroup kernel's
-// launch class (pcx::medium_launch_class), or the one class of PCX_RAGGED_ONE_CLASS
-static int wide_slot(int N, int E, int algorithm, bool one_class) {
-    if (N <= 64 && E <= 32) return 0;
-    return one_class ? 1 : pcx::medium_launch_class(pcx::medium_lds_bytes(N, E, algorithm));
-}
-
-static int ragged_plan_wide(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int algorithm,
-                            bool one_class, int64_t totals[3], int64_t counts[4], int64_t lds_bytes[4],
-                            int64_t* bad_round) {
-    if (const int rc = ragged_plan_checks(n_rounds, n_reporters, n_events, algorithm, bad_round)) return rc;
-    int64_t tot[3] = {0, 0, 0}, cnt[4] = {0, 0, 0, 0};
-    size_t lds[4] = {0, 0, 0, 0};
-    for (int64_t b = 0; b < n_rounds; b++) {
-        const int32_t N = n_reporters[b], E = n_events[b];
-        if (N < 1 || N > 256 || E < 1 || E > 64) return ragged_bad_round(b, N, E, 256, 64, bad_round);
-        tot[0] += N;
-        tot[1] += E;
-        tot[2] += (int64_t)N * E;
-        const int k = wide_slot(N, E, algorithm, one_class);
-        cnt[k]++;
-        lds[k] = std::max(lds[k], k ? pcx::medium_lds_bytes(N, E, algorithm) : pcx::ragged_lds_bytes(N, E, algorithm));
-    }
-    for (int k = 0; k < 3 && totals; k++) totals[k] = tot[k];
-    for (int k = 0; k < 4 && counts; k++) counts[k] = cnt[k];
-    for (int k = 0; k < 4 && lds_bytes; k++) lds_bytes[k] = (int64_t)lds[k];
-    return PCX_OK;
-}
-
-int pcx_ragged_plan_wide(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int algorithm,
-                         int64_t totals[3], int64_t counts[4], int64_t lds_bytes[4], int64_t* bad_round) {
-    return ragged_plan_wide(n_rounds, n_reporters, n_events, algorithm, false, totals, counts, lds_bytes, bad_round);
-}
-
-int pcx_test_scratch_cap(pcx_ctx* ctx, int64_t bytes) {
-    if (!ctx || bytes < 0) return fail(PCX_EINVAL, "pcx_test_scratch_cap: null context or negative bytes");
-    ctx->test_scratch_cap = bytes;
-    return PCX_OK;
-}
-
-// The descriptor tables of one wide ragged call in a staging slot, and what its launches need of
-// them.  They depend on the rounds' shapes and the algorithm alone, not on any data pointer:
-// pcx_consensus_ragged_wide_f64 builds them, uploads them and launches once; a simulator sweep
-// (pcx_simulate_sweep_f64) builds and uploads them once and launches every timestep.
-struct WidePlan {
-    pcx_ctx::RaggedSlot* slot = nullptr;
-    int64_t B = 0, nw = 0, nm = 0, chunk = 0;
-    int64_t cnt[4] = {0, 0, 0, 0}, lds[4] = {0, 0, 0, 0}, first[4] = {0, 0, 0, 0}, stride[3] = {0, 0, 0};
-    // slot offsets: the workgroup rounds' descriptors, the wave rounds' indices, the caller's `extra`
-    // bytes; `bytes` are uploaded, the wave rounds' six [B] outputs follow at off_t on the device
-    size_t off_m = 0, off_i = 0, off_x = 0, bytes = 0, off_t = 0;
-    bool filled = false;  // the caller gives `filled`: no N x E scratch of the library's
-};
-
-// Plan's tables into a staging slot taken here (cnt / lds as ragged_plan_wide found them), the
-// workgroup scratch reserved; `extra` bytes (a multiple of 8) of the caller's ride along at off_x.
-// One staging slot, one upload: the wave rounds' descriptors, the workgroup rounds' descriptors
-// class after class (3, 2, 1; a class's rounds in their order), the wave rounds' indices.  The
-// device side holds, past what is uploaded, the wave rounds' six [B] outputs until their scatter.
-// With wave rounds only (nm == 0) the first table is pcx_consensus_ragged_f64's own.
-static int wide_tables(pcx_ctx* ctx, int64_t B, const int32_t* n_reporters, const int32_t* n_events, int algorithm,
-                       bool one_class, const int64_t cnt[4], const int64_t lds[4], bool filled, size_t extra,
-                       WidePlan* plan) {
-    WidePlan& p = *plan;
-    p.B = B;
-    p.nw = cnt[0];
-    p.nm = B - p.nw;
-    p.filled = filled;
-    for (int k = 0; k < 4; k++) {
-        p.cnt[k] = cnt[k];
-        p.lds[k] = lds[k];
-    }
-    const int64_t nw = p.nw, nm = p.nm;
-    p.off_m = (size_t)nw * sizeof(pcx::RaggedDesc);
-    p.off_i = p.off_m + (size_t)nm * sizeof(pcx::MediumDesc);
-    p.off_x = (p.off_i + (size_t)nw * sizeof(int32_t) + 7) / 8 * 8;
-    p.bytes = p.off_t = p.off_x + extra;
-    if (const int rc = ragged_slot_take(ctx, p.off_t + (size_t)nw * 32, &p.slot)) return rc;
-    char* pin = static_cast<char*>(p.slot->pin);
-    pcx::RaggedDesc* dw = reinterpret_cast<pcx::RaggedDesc*>(pin);
-    pcx::MediumDesc* dm = reinterpret_cast<pcx::MediumDesc*>(pin + p.off_m);
-    int32_t* idx = reinterpret_cast<int32_t*>(pin + p.off_i);
-    int64_t at[4] = {0, 0, 0, 0};  // next entry of each class in dm: class 3 first
-    at[2] = cnt[3];
-    at[1] = cnt[3] + cnt[2];
-    for (int k = 0; k < 4; k++) p.first[k] = k ? at[k] : 0;
-    int64_t cell = 0, row = 0, ev = 0, w = 0;
-    for (int64_t b = 0; b < B; b++) {
-        const int32_t N = n_reporters[b], E = n_events[b];
-        const int k = wide_slot(N, E, algorithm, one_class);
-        if (k == 0) {
-            dw[w] = pcx::RaggedDesc{cell, row, ev, N, E};
-            idx[w++] = (int32_t)b;
-        } else {
-            dm[at[k]++] = pcx::MediumDesc{cell, row, ev, N, E, (int32_t)b, 0};
-            pcx::medium_slot_strides(N, E, algorithm, p.stride);
-        }
-        cell += (int64_t)N * E;
-        row += N;
-        ev += E;
-    }
-    if (nm == 0) return PCX_OK;
-    // the workgroup scratch: slot strides of the call's largest round, chunks that fit the cap
-    const size_t cap = ctx->test_scratch_cap > 0 ? (size_t)ctx->test_scratch_cap : MEDIUM_SCRATCH_CAP;
-    const size_t per = (size_t)((filled ? 0 : p.stride[0]) + p.stride[1] + p.stride[2]) * sizeof(double);
-    p.chunk = std::min<int64_t>(std::max<int64_t>((int64_t)(cap / per), 1), nm);
-    return medium_scratch_reserve(ctx, per * (size_t)p.chunk);
-}
-
-// the launches of a wide ragged call over uploaded tables, with these inputs, options and outputs
-static hipError_t wide_launch(pcx_ctx* ctx, const WidePlan& p, const pcx::BatchArgs& a) {
-    char* dev = static_cast<char*>(p.slot->dev);
-    const int64_t nw = p.nw;
-    if (p.nm == 0)
-        return pcx::launch_ragged(a, reinterpret_cast<const pcx::RaggedDesc*>(dev), (size_t)p.lds[0], ctx->stream);
-    double* Fscr = (double*)ctx->mscr;
-    double* Cscr = Fscr + (p.filled ? 0 : (size_t)p.chunk * p.stride[0]);
-    double* Xscr = Cscr + (size_t)p.chunk * p.stride[1];
-    hipError_t e = hipSuccess;
-    if (nw > 0) {
-        pcx::BatchArgs aw = a;
-        aw.B = nw;
-        const pcx::WaveTmp t = pcx::ragged_wave_tmp(dev + p.off_t, nw);
-        aw.participation = t.participation;
-        aw.avg_certainty = t.avg_certainty;
-        aw.branch = t.branch;
-        aw.flags = t.flags;
-        aw.pi_iters = t.pi_iters;
-        aw.components = t.components;
-        e = pcx::launch_ragged(aw, reinterpret_cast<const pcx::RaggedDesc*>(dev), (size_t)p.lds[0], ctx->stream);
-        if (e == hipSuccess)
-            e = pcx::launch_ragged_scatter(a, reinterpret_cast<const int32_t*>(dev + p.off_i), nw, dev + p.off_t,
-                                           ctx->stream);
-    }
-    const pcx::MediumDesc* ddm = reinterpret_cast<const pcx::MediumDesc*>(dev + p.off_m);
-    for (int k = 3; k >= 1 && e == hipSuccess; k--)
-        for (int64_t b0 = 0; b0 < p.cnt[k] && e == hipSuccess; b0 += p.chunk)
-            e = pcx::launch_ragged_medium(a, ddm + p.first[k] + b0, std::min<int64_t>(p.chunk, p.cnt[k] - b0),
-                                          (size_t)p.lds[k], p.stride, Fscr, Cscr, Xscr, ctx->stream);
-    return e;
-}
-
-int pcx_consensus_ragged_wide_f64(pcx_ctx* ctx, const pcx_ragged* in, pcx_batch_result* out) {
-    if (!ctx || !in || !out) return fail(PCX_EINVAL, "pcx_consensus_ragged_wide_f64: null argument");
-    const char* env = getenv("PCX_RAGGED_ONE_CLASS");  // diagnostic: every workgroup round in one launch
-    const bool one_class = env && env[0] == '1';
-    int64_t cnt[4], lds[4];
-    if (const int rc = ragged_plan_wide(in->n_rounds, in->n_reporters, in->n_events, in->algorithm, one_class, nullptr,
-                                        cnt, lds, nullptr))
-        return rc;
-    if (in->n_rounds == 0) return PCX_OK;
-    if (cnt[0] == in->n_rounds)  // wave-sized rounds only: that call as it is
-        return pcx_consensus_ragged_f64(ctx, in, out);
-    // (max_components is capped at E_b per round on the device)
-    const bool bad_five = in->algorithm == PCX_ALG_BIG_FIVE && in->max_components < 1;
-    if (const int rc = check_options("ragged", in, bad_five ? "big-five needs max_components >= 1" : nullptr))
-        return rc;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    WidePlan p;
-    if (const int rc = wide_tables(ctx, in->n_rounds, in->n_reporters, in->n_events, in->algorithm, one_class, cnt,
-                                   lds, out->filled != nullptr, 0, &p))
-        return rc;
-    e = ragged_slot_upload(ctx, *p.slot, p.bytes);
-    if (e != hipSuccess) return hip_fail(e, "ragged: descriptor upload");
-    pcx::BatchArgs a = shared_args(in, out);
-    a.B = in->n_rounds;
-    e = wide_launch(ctx, p, a);
-    if (e == hipSuccess) e = hipEventRecord(p.slot->kern_ev, ctx->stream);
-    return e == hipSuccess ? PCX_OK : hip_fail(e, "ragged wide launch");
-}
-
-// ---------------------------------------------------------------- per-round parameters
-static_assert(sizeof(pcx_round_params) == sizeof(pcx::RoundParams), "pcx_round_params is the device entry");
-
-// why a parameter set is refused (the words of check_options / sweep_check), or NULL.  sim: a
-// simulator cell's set, where k-means and cokurtosis are not simulated.  kmeans_ok: an entry that
-// takes code books (pcx_consensus_ragged_kmeans_f64).
-static const char* params_set_refusal(const pcx_round_params& q, bool sim, bool kmeans_ok = false) {
-    if (q.algorithm < PCX_ALG_PCA || q.algorithm > PCX_ALG_CLUSTERFECK)
-        return "algorithm must be an enum pcx_algorithm value (0..7)";
-    if (q.algorithm == PCX_ALG_KMEANS && !kmeans_ok)
-        return sim ? "k-means is not simulated (its code books are drawn on the host)"
-                   : "k-means is not supported (its code-book size depends on each round's N)";
-    if (sim && q.algorithm == PCX_ALG_COKURTOSIS) return "cokurtosis is not simulated (it needs the caller's scores)";
-    // (max_components is capped at E_b per round on the device)
-    if (q.algorithm == PCX_ALG_BIG_FIVE && q.max_components < 1) return "big-five needs max_components >= 1";
-    if (q.algorithm == PCX_ALG_HIERARCHICAL && std::isnan(q.hierarchy_threshold)) return "hierarchy_threshold is NaN";
-    if (q.algorithm == PCX_ALG_FIXED_VARIANCE && !std::isfinite(q.variance_threshold))
-        return "variance_threshold must be finite";
-    if (!std::isfinite(q.catch_tolerance) || !std::isfinite(q.alpha)) return "catch_tolerance/alpha must be finite";
-    return nullptr;
-}
-
-// The launches of a call with per-round parameters: nine segments of one descriptor table
-// (MediumDesc, every round's), each one launch (the workgroup ones times the scratch chunks).
-// 0..2: the one-wave kernel's instantiation groups (pcx::params_wave_group); 3..5: the workgroup
-// kernel's plain instantiation, launch classes 3, 2, 1; 6..8: its CLUS instantiation likewise.
-constexpr int PARAMS_SEGMENTS = 9;
-static int params_segment(int N, int E, int algorithm) {
-    if (N <= 64 && E <= 32) return pcx::params_wave_group(algorithm);
-    const int k = pcx::medium_launch_class(pcx::medium_lds_bytes(N, E, algorithm));
-    return 3 + (algorithm >= PCX_ALG_KMEANS ? 3 : 0) + (3 - k);
-}
-
-// a round's segment and dynamic LDS, remembered over a run of equal rounds (a simulator cell's: the
-// host passes over a sweep's 10^4..10^5 rounds lie between the call and its first launch)
-struct SegmentOf {
-    int N = 0, E = 0, alg = -1, seg = 0;
-    int64_t lds = 0;
-    bool fresh = false;  // the last at() computed (a new run)
-    int at(int n, int e, int a) {
-        fresh = n != N || e != E || a != alg;
-        if (fresh) {
-            N = n, E = e, alg = a;
-            seg = params_segment(n, e, a);
-            lds = (int64_t)(seg < 3 ? pcx::ragged_lds_bytes(n, e, a) : pcx::medium_lds_bytes(n, e, a));
-        }
-        return seg;
-    }
-};
-
-struct ParamsPlan {
-    pcx_ctx::RaggedSlot* slot = nullptr;
-    int64_t B = 0, P = 0, nm = 0, chunk = 0;
-    int64_t cnt[PARAMS_SEGMENTS] = {}, lds[PARAMS_SEGMENTS] = {}, first[PARAMS_SEGMENTS] = {};
-    int64_t stride[3] = {0, 0, 0};
-    // slot offsets: the parameter table, the caller's `extra` bytes; `bytes` are uploaded
-    size_t off_p = 0, off_x = 0, bytes = 0;
-    bool filled = false;
-};
-
-// a segment's count and dynamic LDS (the largest round's own, by its own algorithm) and the
-// workgroup rounds' slot strides, of rounds that the caller has checked
-static void params_count(int64_t B, const int32_t* n_reporters, const int32_t* n_events, const pcx_round_params* params,
-                         const int32_t* param_of, ParamsPlan* plan) {
-    ParamsPlan& p = *plan;
-    p.B = B;
-    SegmentOf run;
-    for (int64_t b = 0; b < B; b++) {
-        const int N = n_reporters[b], E = n_events[b], alg = params[param_of[b]].algorithm;
-        const int s = run.at(N, E, alg);
-        p.cnt[s]++;
-        if (s >= 3) p.nm++;
-        if (!run.fresh) continue;
-        p.lds[s] = std::max(p.lds[s], run.lds);
-        if (s >= 3) pcx::medium_slot_strides(N, E, alg, p.stride);
-    }
-    for (int s = 1; s < PARAMS_SEGMENTS; s++) p.first[s] = p.first[s - 1] + p.cnt[s - 1];
-}
-
-static int params_plan_check(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
-                             const pcx_round_params* params, const int32_t* param_of, int64_t totals[3],
-                             int64_t* bad_round, int64_t* bad_param, bool kmeans_ok = false) {
-    if (bad_round) *bad_round = -1;
-    if (bad_param) *bad_param = -1;
-    if (n_rounds < 0 || n_rounds > 0x7fffffff) return fail(PCX_EINVAL, "ragged: n_rounds must be in [0, 2^31)");
-    if (n_rounds > 0 && (!n_reporters || !n_events)) return fail(PCX_EINVAL, "ragged: n_reporters / n_events is NULL");
-    if (n_rounds > 0 && n_params < 1) return fail(PCX_EINVAL, "ragged: n_params must be >= 1 (a parameter set per round)");
-    if (n_params > 0x7fffffff) return fail(PCX_EINVAL, "ragged: n_params must be below 2^31");
-    if (n_params > 0 && !params) return fail(PCX_EINVAL, "ragged: params is NULL");
-    if (n_rounds > 0 && !param_of) return fail(PCX_EINVAL, "ragged: param_of is NULL");
-    for (int64_t q = 0; q < n_params; q++)
-        if (const char* why = params_set_refusal(params[q], false, kmeans_ok)) {
-            if (bad_param) *bad_param = q;
-            return fail(PCX_EINVAL, "ragged: parameter set " + std::to_string(q) + ": " + why);
-        }
-    int64_t tot[3] = {0, 0, 0};
-    for (int64_t b = 0; b < n_rounds; b++) {
-        const int32_t N = n_reporters[b], E = n_events[b];
-        if (N < 1 || N > 256 || E < 1 || E > 64) return ragged_bad_round(b, N, E, 256, 64, bad_round);
-        if (param_of[b] < 0 || param_of[b] >= n_params) {
-            if (bad_round) *bad_round = b;
-            return fail(PCX_EINVAL, "ragged: round " + std::to_string(b) + " has param_of " + std::to_string(param_of[b]) +
-                                        ", outside [0, " + std::to_string(n_params) + ")");
-        }
-        tot[0] += N;
-        tot[1] += E;
-        tot[2] += (int64_t)N * E;
-    }
-    for (int k = 0; k < 3 && totals; k++) totals[k] = tot[k];
-    return PCX_OK;
-}
-
-int pcx_ragged_plan_params(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
-                           const pcx_round_params* params, const int32_t* param_of, int64_t totals[3],
-                           int64_t* n_launches, int64_t* bad_round, int64_t* bad_param) {
-    if (const int rc = params_plan_check(n_rounds, n_reporters, n_events, n_params, params, param_of, totals, bad_round,
-                                         bad_param))
-        return rc;
-    if (n_launches) {
-        ParamsPlan p;
-        params_count(n_rounds, n_reporters, n_events, params, param_of, &p);
-        *n_launches = 0;
-        for (int s = 0; s < PARAMS_SEGMENTS; s++) *n_launches += p.cnt[s] > 0;
-    }
-    return PCX_OK;
-}
-
-// A counted plan's tables into a staging slot taken here: every round's descriptor, segment after
-// segment (a segment's rounds in their order), then the P parameter entries, then `extra` bytes (a
-// multiple of 8) of the caller's at off_x; the workgroup scratch reserved.  One slot, one upload.
-static int params_tables(pcx_ctx* ctx, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
-                         const pcx_round_params* params, const int32_t* param_of, bool filled, size_t extra,
-                         ParamsPlan* plan) {
-    ParamsPlan& p = *plan;
-    p.P = n_params;
-    p.filled = filled;
-    p.off_p = (size_t)p.B * sizeof(pcx::MediumDesc);
-    p.off_x = p.off_p + (size_t)n_params * sizeof(pcx::RoundParams);
-    p.bytes = p.off_x + extra;
-    if (const int rc = ragged_slot_take(ctx, p.bytes, &p.slot)) return rc;
-    char* pin = static_cast<char*>(p.slot->pin);
-    pcx::MediumDesc* d = reinterpret_cast<pcx::MediumDesc*>(pin);
-    int64_t at[PARAMS_SEGMENTS];
-    for (int s = 0; s < PARAMS_SEGMENTS; s++) at[s] = p.first[s];
-    int64_t cell = 0, row = 0, ev = 0;
-    SegmentOf run;
-    for (int64_t b = 0; b < p.B; b++) {
-        const int32_t N = n_reporters[b], E = n_events[b];
-        const int s = run.at(N, E, params[param_of[b]].algorithm);
-        d[at[s]++] = pcx::MediumDesc{cell, row, ev, N, E, (int32_t)b, param_of[b]};
-        cell += (int64_t)N * E;
-        row += N;
-        ev += E;
-    }
-    std::memcpy(pin + p.off_p, params, (size_t)n_params * sizeof(pcx::RoundParams));
-    if (p.nm == 0) return PCX_OK;
-    // the workgroup scratch: slot strides of the call's largest round, chunks that fit the cap
-    const size_t cap = ctx->test_scratch_cap > 0 ? (size_t)ctx->test_scratch_cap : MEDIUM_SCRATCH_CAP;
-    const size_t per = (size_t)((filled ? 0 : p.stride[0]) + p.stride[1] + p.stride[2]) * sizeof(double);
-    p.chunk = std::min<int64_t>(std::max<int64_t>((int64_t)(cap / per), 1), p.nm);
-    return medium_scratch_reserve(ctx, per * (size_t)p.chunk);
-}
-
-// the launches over uploaded tables, with these inputs and outputs (a's parameter fields are not read)
-static hipError_t params_launch(pcx_ctx* ctx, const ParamsPlan& p, const pcx::BatchArgs& a) {
-    char* dev = static_cast<char*>(p.slot->dev);
-    const pcx::MediumDesc* d = reinterpret_cast<const pcx::MediumDesc*>(dev);
-    const pcx::RoundParams* tab = reinterpret_cast<const pcx::RoundParams*>(dev + p.off_p);
-    hipError_t e = hipSuccess;
-    for (int g = 0; g < 3 && e == hipSuccess; g++)
-        e = pcx::launch_ragged_params(a, d + p.first[g], tab, p.cnt[g], g, (size_t)p.lds[g], ctx->stream);
-    if (p.nm == 0) return e;
-    double* Fscr = (double*)ctx->mscr;
-    double* Cscr = Fscr + (p.filled ? 0 : (size_t)p.chunk * p.stride[0]);
-    double* Xscr = Cscr + (size_t)p.chunk * p.stride[1];
-    for (int s = 3; s < PARAMS_SEGMENTS && e == hipSuccess; s++)
-        for (int64_t b0 = 0; b0 < p.cnt[s] && e == hipSuccess; b0 += p.chunk)
-            e = pcx::launch_ragged_medium_params(a, d + p.first[s] + b0, tab, std::min<int64_t>(p.chunk, p.cnt[s] - b0),
-                                                 s >= 6, (size_t)p.lds[s], p.stride, Fscr, Cscr, Xscr, ctx->stream);
-    return e;
-}
-
-int pcx_consensus_ragged_params_f64(pcx_ctx* ctx, const pcx_ragged* in, int64_t n_params,
-                                    const pcx_round_params* params, const int32_t* param_of, pcx_batch_result* out) {
-    if (!ctx || !in || !out) return fail(PCX_EINVAL, "pcx_consensus_ragged_params_f64: null argument");
-    if (const int rc = params_plan_check(in->n_rounds, in->n_reporters, in->n_events, n_params, params, param_of,
-                                         nullptr, nullptr, nullptr))
-        return rc;
-    if (in->n_rounds == 0) return PCX_OK;
-    if (!in->reports) return fail(PCX_EINVAL, "ragged: reports is NULL");
-    if (in->scaled && (!in->lo || !in->hi)) return fail(PCX_EINVAL, "ragged: scaled given without lo/hi");
-    for (int64_t b = 0; b < in->n_rounds && !in->aux_scores; b++)
-        if (params[param_of[b]].algorithm == PCX_ALG_COKURTOSIS)
-            return fail(PCX_EINVAL, "ragged: parameter set " + std::to_string(param_of[b]) +
-                                        ": cokurtosis needs aux_scores (aux[\"cokurt\"])");
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    ParamsPlan p;
-    params_count(in->n_rounds, in->n_reporters, in->n_events, params, param_of, &p);
-    if (const int rc = params_tables(ctx, in->n_reporters, in->n_events, n_params, params, param_of,
-                                     out->filled != nullptr, 0, &p))
-        return rc;
-    e = ragged_slot_upload(ctx, *p.slot, p.bytes);
-    if (e != hipSuccess) return hip_fail(e, "ragged: descriptor upload");
-    pcx::BatchArgs a = shared_args(in, out);
-    a.B = in->n_rounds;
-    e = params_launch(ctx, p, a);
-    if (e == hipSuccess) e = hipEventRecord(p.slot->kern_ev, ctx->stream);
-    return e == hipSuccess ? PCX_OK : hip_fail(e, "ragged params launch");
-}
-
-// ---------------------------------------------------------------- k-means in ragged batches
-// the reference's code-book size int(ceil(sqrt(N))) (:396), in integers (N <= 256)
-static int kmeans_rule(int N) {
-    int k = 1;
-    while (k * k < N) k++;
-    return k;
-}
-
-// The flat book layout of the rounds whose set params[param_of[b]] is k-means (params NULL: every
-// round), of rounds whose
-// shapes the caller has checked: offsets[b] = the books before round b's, offsets[B] the length.
-// Refuses a k_b outside [1, min(N_b, 8)] within 64 x 32 (the one-wave kernel's code-book rows),
-// [1, min(N_b, 16)] above (the workgroup kernel's), with the round named.
-static int kmeans_layout(int64_t B, const int32_t* n_reporters, const int32_t* n_events, const int32_t* k, int restarts,
-                         const pcx_round_params* params, const int32_t* param_of, int64_t* offsets,
-                         pcx::KmeansEntry* entries, int64_t* bad_round, int64_t* total = nullptr) {
-    int64_t at = 0;
-    for (int64_t b = 0; b < B; b++) {
-        if (offsets) offsets[b] = at;
-        if (entries) entries[b] = pcx::KmeansEntry{0, 0, 0};
-        if (params && params[param_of[b]].algorithm != PCX_ALG_KMEANS) continue;
-        const int N = n_reporters[b], E = n_events[b];
-        const int kmax = std::min(N, N <= 64 && E <= 32 ? 8 : 16);
-        const int kb = k ? k[b] : kmeans_rule(N);
-        if (kb < 1 || kb > kmax) {
-            if (bad_round) *bad_round = b;
-            return fail(PCX_EINVAL, "k-means: round " + std::to_string(b) + " (" + std::to_string(N) + " x " +
-                                        std::to_string(E) + ") has a code book of " + std::to_string(kb) +
-                                        " rows; it must be within [1, " + std::to_string(kmax) + "]");
-        }
-        if (entries) entries[b] = pcx::KmeansEntry{at, kb, 0};
-        at += (int64_t)restarts * kb;
-    }
-    if (offsets) offsets[B] = at;
-    if (total) *total = at;
-    return PCX_OK;
-}
-
-int pcx_kmeans_plan(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, const int32_t* k,
-                    int32_t restarts, int64_t* offsets, int64_t* bad_round) {
-    if (bad_round) *bad_round = -1;
-    if (n_rounds < 0 || n_rounds > 0x7fffffff) return fail(PCX_EINVAL, "k-means: n_rounds must be in [0, 2^31)");
-    if (restarts < 1) return fail(PCX_EINVAL, "k-means: restarts must be >= 1");
-    if (n_rounds > 0 && (!n_reporters || !n_events)) return fail(PCX_EINVAL, "k-means: n_reporters / n_events is NULL");
-    for (int64_t b = 0; b < n_rounds; b++) {
-        const int32_t N = n_reporters[b], E = n_events[b];
-        if (N < 1 || N > 256 || E < 1 || E > 64) return ragged_bad_round(b, N, E, 256, 64, bad_round);
-    }
-    return kmeans_layout(n_rounds, n_reporters, n_events, k, restarts, nullptr, nullptr, offsets, nullptr, bad_round);
-}
-
-// pcx_ragged_plan_kmeans' checks; *any = some round's set is k-means
-static int kmeans_plan_check(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
-                             const pcx_round_params* params, const int32_t* param_of, const pcx_kmeans_books* books,
-                             int64_t totals[3], int64_t* offsets, pcx::KmeansEntry* entries, int64_t* bad_round,
-                             int64_t* bad_param, bool* any) {
-    if (const int rc = params_plan_check(n_rounds, n_reporters, n_events, n_params, params, param_of, totals, bad_round,
-                                         bad_param, true))
-        return rc;
-    bool some = false;
-    for (int64_t b = 0; b < n_rounds && !some; b++) some = params[param_of[b]].algorithm == PCX_ALG_KMEANS;
-    if (any) *any = some;
-    if (some && !books) return fail(PCX_EINVAL, "k-means: a round's set is k-means and books is NULL");
-    if (some && books->restarts < 1) return fail(PCX_EINVAL, "k-means: restarts must be >= 1");
-    return kmeans_layout(n_rounds, n_reporters, n_events, some ? books->k : nullptr, some ? books->restarts : 0, params,
-                         param_of, offsets, entries, bad_round);
-}
-
-int pcx_ragged_plan_kmeans(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
-                           const pcx_round_params* params, const int32_t* param_of, const pcx_kmeans_books* books,
-                           int64_t totals[3], int64_t* n_launches, int64_t* offsets, int64_t* bad_round,
-                           int64_t* bad_param) {
-    if (const int rc = kmeans_plan_check(n_rounds, n_reporters, n_events, n_params, params, param_of, books, totals,
-                                         offsets, nullptr, bad_round, bad_param, nullptr))
-        return rc;
-    if (n_launches) {
-        ParamsPlan p;
-        params_count(n_rounds, n_reporters, n_events, params, param_of, &p);
-        *n_launches = 0;
-        for (int s = 0; s < PARAMS_SEGMENTS; s++) *n_launches += p.cnt[s] > 0;
-    }
-    return PCX_OK;
-}
-
-// params_launch with the clustering segments (one-wave group 2, workgroup 6..8) on the k-means form
-// (books: the per-round book table on the device, somewhere in the slot's `extra` bytes)
-static hipError_t kmeans_launch(pcx_ctx* ctx, const ParamsPlan& p, const pcx::BatchArgs& a,
-                                const pcx::KmeansEntry* books) {
-    char* dev = static_cast<char*>(p.slot->dev);
-    const pcx::MediumDesc* d = reinterpret_cast<const pcx::MediumDesc*>(dev);
-    const pcx::RoundParams* tab = reinterpret_cast<const pcx::RoundParams*>(dev + p.off_p);
-    hipError_t e = hipSuccess;
-    for (int g = 0; g < 2 && e == hipSuccess; g++)
-        e = pcx::launch_ragged_params(a, d + p.first[g], tab, p.cnt[g], g, (size_t)p.lds[g], ctx->stream);
-    if (e == hipSuccess)
-        e = pcx::launch_ragged_kmeans(a, d + p.first[2], tab, books, p.cnt[2], (size_t)p.lds[2], ctx->stream);
-    if (p.nm == 0) return e;
-    double* Fscr = (double*)ctx->mscr;
-    double* Cscr = Fscr + (p.filled ? 0 : (size_t)p.chunk * p.stride[0]);
-    double* Xscr = Cscr + (size_t)p.chunk * p.stride[1];
-    for (int s = 3; s < PARAMS_SEGMENTS && e == hipSuccess; s++)
-        for (int64_t b0 = 0; b0 < p.cnt[s] && e == hipSuccess; b0 += p.chunk) {
-            const int64_t nb = std::min<int64_t>(p.chunk, p.cnt[s] - b0);
-            e = s >= 6 ? pcx::launch_ragged_medium_kmeans(a, d + p.first[s] + b0, tab, books, nb, (size_t)p.lds[s], p.stride,
-                                                          Fscr, Cscr, Xscr, ctx->stream)
-                       : pcx::launch_ragged_medium_params(a, d + p.first[s] + b0, tab, nb, false, (size_t)p.lds[s],
-                                                          p.stride, Fscr, Cscr, Xscr, ctx->stream);
-        }
-    return e;
-}
-
-int pcx_consensus_ragged_kmeans_f64(pcx_ctx* ctx, const pcx_ragged* in, int64_t n_params,
-                                    const pcx_round_params* params, const int32_t* param_of,
-                                    const pcx_kmeans_books* books, pcx_batch_result* out) {
-    if (!ctx || !in || !out) return fail(PCX_EINVAL, "pcx_consensus_ragged_kmeans_f64: null argument");
-    const int64_t B = in->n_rounds;
-    bool any = false;
-    // (the checks first, without a table: a refusal takes no staging slot)
-    if (const int rc = kmeans_plan_check(B, in->n_reporters, in->n_events, n_params, params, param_of, books, nullptr,
-                                         nullptr, nullptr, nullptr, nullptr, &any))
-        return rc;
-    if (B == 0) return PCX_OK;
-    if (!in->reports) return fail(PCX_EINVAL, "ragged: reports is NULL");
-    if (in->scaled && (!in->lo || !in->hi)) return fail(PCX_EINVAL, "ragged: scaled given without lo/hi");
-    if (any && !books->init) return fail(PCX_EINVAL, "k-means: books->init is NULL");
-    for (int64_t b = 0; b < B && !in->aux_scores; b++)
-        if (params[param_of[b]].algorithm == PCX_ALG_COKURTOSIS)
-            return fail(PCX_EINVAL, "ragged: parameter set " + std::to_string(param_of[b]) +
-                                        ": cokurtosis needs aux_scores (aux[\"cokurt\"])");
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    ParamsPlan p;
-    params_count(B, in->n_reporters, in->n_events, params, param_of, &p);
-    if (const int rc = params_tables(ctx, in->n_reporters, in->n_events, n_params, params, param_of,
-                                     out->filled != nullptr, (size_t)B * sizeof(pcx::KmeansEntry), &p))
-        return rc;
-    // the per-round book table, behind the parameter entries in the one upload
-    pcx::KmeansEntry* entries = reinterpret_cast<pcx::KmeansEntry*>(static_cast<char*>(p.slot->pin) + p.off_x);
-    if (const int rc = kmeans_layout(B, in->n_reporters, in->n_events, any ? books->k : nullptr, any ? books->restarts : 0,
-                                     params, param_of, nullptr, entries, nullptr))
-        return rc;
-    e = ragged_slot_upload(ctx, *p.slot, p.bytes);
-    if (e != hipSuccess) return hip_fail(e, "ragged: descriptor upload");
-    pcx::BatchArgs a = shared_args(in, out);
-    a.B = B;
-    a.kmeans_restarts = any ? books->restarts : 0;
-    a.kmeans_init = any ? books->init : nullptr;
-    e = kmeans_launch(ctx, p, a, reinterpret_cast<const pcx::KmeansEntry*>(static_cast<char*>(p.slot->dev) + p.off_x));
-    if (e == hipSuccess) e = hipEventRecord(p.slot->kern_ev, ctx->stream);
-    return e == hipSuccess ? PCX_OK : hip_fail(e, "ragged k-means launch");
 }
 
 namespace {
@@ -1363,898 +624,6 @@ int pcx_test_inject_enomem(pcx_ctx* ctx, int worker) {
     if (!ctx) return fail(PCX_EINVAL, "pcx_test_inject_enomem: null context");
     ctx->test_enomem_worker = worker;
     return PCX_OK;
-}
-
-// ---------------------------------------------------------------- Monte Carlo simulator
-namespace {
-// the argument checks every simulator entry shares (no device needed); 0 = ok
-// (kmeans_ok: an entry that draws the code books on the device)
-int sim_check(const pcx_sim* s, const char* who, bool kmeans_ok = false) {
-    const std::string w = std::string(who) + ": ";
-    if (s->n_rounds < 0 || s->n_rounds > 0x7fffffff) return fail(PCX_EINVAL, w + "n_rounds must be in [0, 2^31)");
-    if (s->n_reporters < 1 || s->n_reporters > 0x7fffffff)
-        return fail(PCX_EINVAL, w + "n_reporters must be in [1, 2^31)");
-    if (s->n_events < 1 || s->n_events > 65536) return fail(PCX_EINVAL, w + "n_events must be in [1, 65536]");
-    if (s->n_timesteps < 1 || s->n_timesteps >= (1 << 24))
-        return fail(PCX_EINVAL, w + "n_timesteps must be in [1, 2^24)");
-    const struct {
-        const char* name;
-        double p;
-    } probs[] = {{"liar_frac", s->liar_frac}, {"collude_frac", s->collude_frac}, {"distort", s->distort},
-                 {"na_frac", s->na_frac},     {"scaled_frac", s->scaled_frac}};
-    for (const auto& q : probs)
-        if (!(q.p >= 0.0 && q.p <= 1.0))  // false for NaN too
-            return fail(PCX_EINVAL, w + q.name + " must be a probability in [0, 1]");
-    if (!(s->scaled_tol >= 0.0) || !std::isfinite(s->scaled_tol))
-        return fail(PCX_EINVAL, w + "scaled_tol must be finite and >= 0");
-    if (s->algorithm < PCX_ALG_PCA || s->algorithm > PCX_ALG_CLUSTERFECK)
-        return fail(PCX_EINVAL, w + "algorithm must be an enum pcx_algorithm value (0..7)");
-    if (s->algorithm == PCX_ALG_KMEANS && !kmeans_ok)
-        return fail(PCX_EINVAL, w + "k-means is not simulated (its code books are drawn on the host)");
-    if (s->algorithm == PCX_ALG_COKURTOSIS)
-        return fail(PCX_EINVAL, w + "cokurtosis is not simulated (it needs the caller's scores)");
-    // what pcx_consensus_batched_f64 would refuse, before anything is generated
-    if (s->algorithm == PCX_ALG_HIERARCHICAL && std::isnan(s->hierarchy_threshold))
-        return fail(PCX_EINVAL, w + "hierarchy_threshold is NaN");
-    if (s->algorithm == PCX_ALG_BIG_FIVE && (s->max_components < 1 || s->max_components > s->n_events))
-        return fail(PCX_EINVAL, w + "big-five needs 1 <= max_components <= n_events");
-    if (s->algorithm == PCX_ALG_FIXED_VARIANCE && !std::isfinite(s->variance_threshold))
-        return fail(PCX_EINVAL, w + "variance_threshold must be finite");
-    if (!std::isfinite(s->catch_tolerance) || !std::isfinite(s->alpha))
-        return fail(PCX_EINVAL, w + "catch_tolerance/alpha must be finite");
-    return PCX_OK;
-}
-
-int sim_check_timestep(int t, const char* who) {
-    if (t < 0 || t >= (1 << 24)) return fail(PCX_EINVAL, std::string(who) + ": timestep must be in [0, 2^24)");
-    return PCX_OK;
-}
-
-uint64_t sim_threshold(double p) { return (uint64_t)std::floor(p * 4294967296.0); }
-
-pcx::sim::Gen sim_gen(const pcx_sim* s) {
-    pcx::sim::Gen g;
-    g.key0 = (uint32_t)s->seed;
-    g.key1 = (uint32_t)(s->seed >> 32);
-    g.thr_liar = sim_threshold(s->liar_frac);
-    g.thr_collude = sim_threshold(s->collude_frac);
-    g.thr_distort = sim_threshold(s->distort);
-    g.thr_na = sim_threshold(s->na_frac);
-    g.thr_scaled = sim_threshold(s->scaled_frac);
-    return g;
-}
-
-int sim_reserve(pcx_ctx* ctx, size_t need) {
-    if (ctx->sim_bytes >= need) return PCX_OK;
-    pcx::sim_free(ctx);
-    const hipError_t e = hipMalloc(&ctx->sim_buf, need);
-    if (e != hipSuccess) {
-        ctx->sim_buf = nullptr;
-        return fail(e == hipErrorOutOfMemory ? PCX_ENOMEM : PCX_EHIP,
-                    std::string("pcx_simulate_f64: hipMalloc(work buffers): ") + hipGetErrorString(e));
-    }
-    ctx->sim_bytes = need;
-    return PCX_OK;
-}
-}  // namespace
-
-void pcx_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
-    const pcx::sim::U4 r = pcx::sim::philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1]);
-    out[0] = r.w0;
-    out[1] = r.w1;
-    out[2] = r.w2;
-    out[3] = r.w3;
-}
-
-int pcx_sim_generate_host(const pcx_sim* sim, int timestep, pcx_sim_rounds* out) {
-    if (!sim || !out) return fail(PCX_EINVAL, "pcx_sim_generate_host: null argument");
-    if (const int rc = sim_check(sim, "pcx_sim_generate_host")) return rc;
-    if (const int rc = sim_check_timestep(timestep, "pcx_sim_generate_host")) return rc;
-    pcx::sim_generate_host(sim_gen(sim), sim->n_rounds, sim->n_reporters, sim->n_events, (uint32_t)timestep, *out);
-    return PCX_OK;
-}
-
-int pcx_sim_generate_f64(pcx_ctx* ctx, const pcx_sim* sim, int timestep, pcx_sim_rounds* out) {
-    if (!ctx || !sim || !out) return fail(PCX_EINVAL, "pcx_sim_generate_f64: null argument");
-    if (const int rc = sim_check(sim, "pcx_sim_generate_f64")) return rc;
-    if (const int rc = sim_check_timestep(timestep, "pcx_sim_generate_f64")) return rc;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    e = pcx::launch_sim_generate(sim_gen(sim), sim->n_rounds, sim->n_reporters, sim->n_events, (uint32_t)timestep,
-                                 *out, ctx->stream);
-    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_sim_generate launch");
-}
-
-int pcx_sim_metrics_f64(pcx_ctx* ctx, const pcx_sim* sim, const pcx_sim_rounds* rounds, const double* old_rep,
-                        const double* smooth_rep, const double* outcomes_final, double* metrics, double* summary) {
-    if (!ctx || !sim || !rounds || !old_rep || !smooth_rep || !outcomes_final || !metrics)
-        return fail(PCX_EINVAL, "pcx_sim_metrics_f64: null argument");
-    if (!rounds->scaled || !rounds->lo || !rounds->hi || !rounds->truth || !rounds->liar)
-        return fail(PCX_EINVAL, "pcx_sim_metrics_f64: rounds needs scaled, lo, hi, truth and liar");
-    if (const int rc = sim_check(sim, "pcx_sim_metrics_f64")) return rc;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    e = pcx::launch_sim_metrics(sim->n_rounds, sim->n_reporters, sim->n_events, sim->scaled_tol, *rounds, old_rep,
-                                smooth_rep, outcomes_final, metrics, ctx->stream);
-    if (e == hipSuccess && summary) e = pcx::launch_sim_summary(metrics, sim->n_rounds, summary, ctx->stream);
-    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_sim_metrics / k_sim_summary launch");
-}
-
-// the reference's code-book size int(ceil(sqrt(N))) (:396) for any N, in integers
-static int64_t sim_kmeans_rule(int64_t N) {
-    int64_t k = 1;
-    while (k * k < N) k++;
-    return k;
-}
-
-// restarts / (rounds x restarts) that the books kernels take: one thread each, at most 2^31 - 1 workgroups
-static int sim_books_check(int64_t B, int restarts, const std::string& who) {
-    if (restarts < 1) return fail(PCX_EINVAL, who + ": k-means restarts must be >= 1");
-    if ((B * (int64_t)restarts + 255) / 256 > 0x7fffffff)
-        return fail(PCX_EINVAL, who + ": rounds x restarts is too large for one books launch");
-    return PCX_OK;
-}
-
-// The loop of pcx_simulate_f64 and pcx_simulate_kmeans_f64 (`who`).  restarts > 0: the latter, under
-// k-means -- every timestep's books are drawn into the workspace between the generator and the
-// batched launch, which reads them as kmeans_init.
-static int simulate_run(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* res, int restarts, const char* who) {
-    if (const int rc = sim_check(sim, who, restarts > 0)) return rc;
-    const bool km = restarts > 0 && sim->algorithm == PCX_ALG_KMEANS;
-    const int64_t kk = km ? sim_kmeans_rule(sim->n_reporters) : 0;
-    if (km)
-        if (const int rc = sim_books_check(sim->n_rounds, restarts, who)) return rc;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    const int64_t B = sim->n_rounds, N = sim->n_reporters, E = sim->n_events, T = sim->n_timesteps;
-    const size_t bn = (size_t)B * N, be = (size_t)B * E;
-    // work buffers, doubles first: reports, lo, hi, truth, outcomes_final, old_rep, two smooth_rep
-    // (ping-pong: a timestep reads one as its reputation and writes the other), metrics; then
-    // the bytes scaled and liar
-    const size_t n_f64 = bn * E + 4 * be + 3 * bn + (size_t)B * PCX_SIM_NMETRICS;
-    // (k-means: the books [B][restarts][k] int32 behind the bytes, on a 4-byte boundary)
-    const size_t off_books = (n_f64 * sizeof(double) + be + bn + 3) / 4 * 4;
-    const size_t n_books = km ? (size_t)B * restarts * kk : 0;
-    if (const int rc = sim_reserve(ctx, std::max<size_t>(off_books + n_books * sizeof(int32_t), 16))) return rc;
-    int32_t* const w_books = reinterpret_cast<int32_t*>(static_cast<char*>(ctx->sim_buf) + off_books);
-    double* p = (double*)ctx->sim_buf;
-    auto take = [&p](size_t n) {
-        double* q = p;
-        p += n;
-        return q;
-    };
-    pcx_sim_rounds work;
-    work.reports = take(bn * E);
-    work.lo = take(be);
-    work.hi = take(be);
-    work.truth = take(be);
-    double* w_outcomes = take(be);
-    double* w_old = take(bn);
-    double* w_smooth[2] = {take(bn), take(bn)};
-    double* w_metrics = take((size_t)B * PCX_SIM_NMETRICS);
-    work.scaled = (uint8_t*)p;
-    work.liar = work.scaled + be;
-    const pcx::sim::Gen g = sim_gen(sim);
-    const double* rep = sim->reputation0;
-    for (int64_t t = 0; t < T; t++) {
-        const bool last = t == T - 1;
-        pcx_sim_rounds r = work;
-        pcx_batch_result o{};
-        if (last) {  // the caller's buffers where given
-            const pcx_sim_rounds& u = res->last;
-            if (u.reports) r.reports = u.reports;
-            if (u.scaled) r.scaled = u.scaled;
-            if (u.lo) r.lo = u.lo;
-            if (u.hi) r.hi = u.hi;
-            if (u.truth) r.truth = u.truth;
-            if (u.liar) r.liar = u.liar;
-            o = res->last_out;
-        }
-        if (!o.old_rep) o.old_rep = w_old;
-        if (!o.smooth_rep) o.smooth_rep = w_smooth[t & 1];
-        if (!o.outcomes_final) o.outcomes_final = w_outcomes;
-        e = pcx::launch_sim_generate(g, B, N, E, (uint32_t)t, r, ctx->stream);
-        if (e != hipSuccess) return hip_fail(e, "k_sim_generate launch");
-        pcx_batch in{};
-        in.n_rounds = B;
-        in.n_reporters = N;
-        in.n_events = E;
-        in.reports = r.reports;
-        in.reputation = rep;
-        in.scaled = r.scaled;
-        in.lo = r.lo;
-        in.hi = r.hi;
-        in.catch_tolerance = sim->catch_tolerance;
-        in.alpha = sim->alpha;
-        in.algorithm = sim->algorithm;
-        in.max_components = sim->max_components;
-        in.variance_threshold = sim->variance_threshold;
-        in.hierarchy_threshold = sim->hierarchy_threshold;
-        in.cluster_threshold = sim->cluster_threshold;
-        if (km) {
-            e = pcx::launch_sim_kmeans_books(g, B, (int)N, (int)kk, restarts, (uint32_t)t, w_books, ctx->stream);
-            if (e != hipSuccess) return hip_fail(e, "k_kmeans_books launch");
-            in.kmeans_k = (int32_t)kk;
-            in.kmeans_restarts = restarts;
-            in.kmeans_init = w_books;
-        }
-        if (const int rc = pcx_consensus_batched_f64(ctx, &in, &o)) return rc;
-        if (res->metrics || res->summary) {
-            double* m = res->metrics ? res->metrics + (size_t)t * B * PCX_SIM_NMETRICS : w_metrics;
-            e = pcx::launch_sim_metrics(B, N, E, sim->scaled_tol, r, o.old_rep, o.smooth_rep, o.outcomes_final, m,
-                                        ctx->stream);
-            if (e == hipSuccess && res->summary)
-                e = pcx::launch_sim_summary(m, B, res->summary + (size_t)t * PCX_SIM_NMETRICS, ctx->stream);
-            if (e != hipSuccess) return hip_fail(e, "k_sim_metrics / k_sim_summary launch");
-        }
-        rep = o.smooth_rep;  // the next timestep's reputation
-    }
-    if (res->reputation && bn) {
-        e = hipMemcpyAsync(res->reputation, rep, bn * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
-        if (e != hipSuccess) return hip_fail(e, "pcx_simulate_f64: reputation copy");
-    }
-    return PCX_OK;
-}
-
-int pcx_simulate_f64(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* res) {
-    if (!ctx || !sim || !res) return fail(PCX_EINVAL, "pcx_simulate_f64: null argument");
-    return simulate_run(ctx, sim, res, 0, "pcx_simulate_f64");
-}
-
-int pcx_simulate_kmeans_f64(pcx_ctx* ctx, const pcx_sim* sim, int32_t restarts, pcx_sim_result* res) {
-    if (!ctx || !sim || !res) return fail(PCX_EINVAL, "pcx_simulate_kmeans_f64: null argument");
-    if (restarts < 1) return fail(PCX_EINVAL, "pcx_simulate_kmeans_f64: k-means restarts must be >= 1");
-    return simulate_run(ctx, sim, res, restarts, "pcx_simulate_kmeans_f64");
-}
-
-int pcx_sim_kmeans_books_host(const pcx_sim* sim, int32_t restarts, int timestep, int32_t* books) {
-    const char* who = "pcx_sim_kmeans_books_host";
-    if (!sim || !books) return fail(PCX_EINVAL, std::string(who) + ": null argument");
-    if (const int rc = sim_check(sim, who, true)) return rc;
-    if (const int rc = sim_check_timestep(timestep, who)) return rc;
-    if (const int rc = sim_books_check(sim->n_rounds, restarts, who)) return rc;
-    pcx::sim_kmeans_books_host(sim_gen(sim), sim->n_rounds, (int)sim->n_reporters, (int)sim_kmeans_rule(sim->n_reporters),
-                               restarts, (uint32_t)timestep, books);
-    return PCX_OK;
-}
-
-int pcx_sim_kmeans_books_f64(pcx_ctx* ctx, const pcx_sim* sim, int32_t restarts, int timestep, int32_t* books) {
-    const char* who = "pcx_sim_kmeans_books_f64";
-    if (!ctx || !sim || !books) return fail(PCX_EINVAL, std::string(who) + ": null argument");
-    if (const int rc = sim_check(sim, who, true)) return rc;
-    if (const int rc = sim_check_timestep(timestep, who)) return rc;
-    if (const int rc = sim_books_check(sim->n_rounds, restarts, who)) return rc;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    e = pcx::launch_sim_kmeans_books(sim_gen(sim), sim->n_rounds, (int)sim->n_reporters,
-                                     (int)sim_kmeans_rule(sim->n_reporters), restarts, (uint32_t)timestep, books,
-                                     ctx->stream);
-    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_kmeans_books launch");
-}
-
-// ---------------------------------------------------------------- simulator sweeps
-namespace {
-int sweep_fail(int64_t* bad_cell, int64_t c, const char* who, const std::string& why) {
-    if (bad_cell) *bad_cell = c;
-    return fail(PCX_EINVAL, std::string(who) + ": " + (c >= 0 ? "cell " + std::to_string(c) + ": " : "") + why);
-}
-
-// The checks every sweep entry shares (pure): the shared parameters as sim_check checks them
-// (*bad_cell = -1), then cell after cell.  Fills what pcx_sim_sweep_plan reports; 0 = ok.
-// cp: per-cell parameter sets [C] (NULL: the shared parameters) -- the shared ones are then neither
-// read nor checked, each cell's set is checked with the cell, and its rounds count by its algorithm.
-// kmeans_ok: an entry that draws the code books on the device -- k-means passes, shared or in a set.
-int sweep_check(const pcx_sim_sweep* s, const char* who, int64_t totals[4], int64_t counts[4], int64_t lds_bytes[4],
-                int64_t* bad_cell, const pcx_round_params* cp = nullptr, bool kmeans_ok = false) {
-    if (bad_cell) *bad_cell = -1;
-    if (s->n_cells < 0) return sweep_fail(bad_cell, -1, who, "n_cells must be >= 0");
-    if (s->n_cells > 0 && !s->cells) return sweep_fail(bad_cell, -1, who, "cells is NULL");
-    if (s->n_timesteps < 1 || s->n_timesteps >= (1 << 24))
-        return sweep_fail(bad_cell, -1, who, "n_timesteps must be in [1, 2^24)");
-    if (!(s->scaled_tol >= 0.0) || !std::isfinite(s->scaled_tol))
-        return sweep_fail(bad_cell, -1, who, "scaled_tol must be finite and >= 0");
-    if (cp) {
-        // (each cell's own set, below)
-    } else if (s->algorithm < PCX_ALG_PCA || s->algorithm > PCX_ALG_CLUSTERFECK)
-        return sweep_fail(bad_cell, -1, who, "algorithm must be an enum pcx_algorithm value (0..7)");
-    else if (s->algorithm == PCX_ALG_KMEANS && !kmeans_ok)
-        return sweep_fail(bad_cell, -1, who, "k-means is not simulated (its code books are drawn on the host)");
-    else if (s->algorithm == PCX_ALG_COKURTOSIS)
-        return sweep_fail(bad_cell, -1, who, "cokurtosis is not simulated (it needs the caller's scores)");
-    else if (s->algorithm == PCX_ALG_HIERARCHICAL && std::isnan(s->hierarchy_threshold))
-        return sweep_fail(bad_cell, -1, who, "hierarchy_threshold is NaN");
-    // (max_components is capped at E_c per round on the device)
-    else if (s->algorithm == PCX_ALG_BIG_FIVE && s->max_components < 1)
-        return sweep_fail(bad_cell, -1, who, "big-five needs max_components >= 1");
-    else if (s->algorithm == PCX_ALG_FIXED_VARIANCE && !std::isfinite(s->variance_threshold))
-        return sweep_fail(bad_cell, -1, who, "variance_threshold must be finite");
-    else if (!std::isfinite(s->catch_tolerance) || !std::isfinite(s->alpha))
-        return sweep_fail(bad_cell, -1, who, "catch_tolerance/alpha must be finite");
-    int64_t tot[4] = {0, 0, 0, 0}, cnt[4] = {0, 0, 0, 0};
-    size_t lds[4] = {0, 0, 0, 0};
-    for (int64_t c = 0; c < s->n_cells; c++) {
-        const pcx_sim_cell& k = s->cells[c];
-        if (k.n_reporters < 1 || k.n_reporters > 256 || k.n_events < 1 || k.n_events > 64)
-            return sweep_fail(bad_cell, c, who,
-                              "is " + std::to_string(k.n_reporters) + " x " + std::to_string(k.n_events) +
-                                  "; a cell's rounds must be within [1, 256] x [1, 64]");
-        if (k.n_rounds < 1 || k.n_rounds > 0x7fffffff)
-            return sweep_fail(bad_cell, c, who, "n_rounds must be in [1, 2^31)");
-        const struct {
-            const char* name;
-            double p;
-        } probs[] = {{"liar_frac", k.liar_frac}, {"collude_frac", k.collude_frac}, {"distort", k.distort},
-                     {"na_frac", k.na_frac},     {"scaled_frac", k.scaled_frac}};
-        for (const auto& q : probs)
-            if (!(q.p >= 0.0 && q.p <= 1.0))  // false for NaN too
-                return sweep_fail(bad_cell, c, who, std::string(q.name) + " must be a probability in [0, 1]");
-        if (cp)
-            if (const char* why = params_set_refusal(cp[c], true, kmeans_ok)) return sweep_fail(bad_cell, c, who, why);
-        const int algorithm = cp ? cp[c].algorithm : s->algorithm;
-        const int64_t R = k.n_rounds, N = k.n_reporters, E = k.n_events;
-        tot[0] += R;
-        if (tot[0] > 0x7fffffff)
-            return sweep_fail(bad_cell, c, who, "the rounds up to this cell reach 2^31 (sum of n_rounds must be < 2^31)");
-        tot[1] += R * N;
-        tot[2] += R * E;
-        tot[3] += R * N * E;
-        const int slot = wide_slot((int)N, (int)E, algorithm, false);
-        cnt[slot] += R;
-        lds[slot] = std::max(lds[slot], slot ? pcx::medium_lds_bytes((int)N, (int)E, algorithm)
-                                             : pcx::ragged_lds_bytes((int)N, (int)E, algorithm));
-    }
-    for (int k = 0; k < 4 && totals; k++) totals[k] = tot[k];
-    for (int k = 0; k < 4 && counts; k++) counts[k] = cnt[k];
-    for (int k = 0; k < 4 && lds_bytes; k++) lds_bytes[k] = (int64_t)lds[k];
-    return PCX_OK;
-}
-
-pcx::sim::Gen sweep_gen(const pcx_sim_cell& k) {
-    pcx::sim::Gen g;
-    g.key0 = (uint32_t)k.seed;
-    g.key1 = (uint32_t)(k.seed >> 32);
-    g.thr_liar = sim_threshold(k.liar_frac);
-    g.thr_collude = sim_threshold(k.collude_frac);
-    g.thr_distort = sim_threshold(k.distort);
-    g.thr_na = sim_threshold(k.na_frac);
-    g.thr_scaled = sim_threshold(k.scaled_frac);
-    return g;
-}
-
-// bytes of a checked sweep's tables: the cell table, then the round prefix sums [C + 1]
-size_t sweep_table_bytes(const pcx_sim_sweep* s) {
-    return (size_t)s->n_cells * sizeof(pcx::SweepCell) + (size_t)(s->n_cells + 1) * sizeof(int64_t);
-}
-
-// the tables of a checked sweep written at `host`; what the kernels get points at `dev`, where
-// the caller uploads them
-pcx::SweepTables sweep_tables_fill(const pcx_sim_sweep* s, void* host, const void* dev) {
-    const int64_t C = s->n_cells;
-    pcx::SweepCell* cells = static_cast<pcx::SweepCell*>(host);
-    int64_t* prefix = reinterpret_cast<int64_t*>(cells + C);
-    int64_t round = 0, cell = 0, row = 0, ev = 0;
-    for (int64_t c = 0; c < C; c++) {
-        const pcx_sim_cell& k = s->cells[c];
-        const int64_t R = k.n_rounds, N = k.n_reporters, E = k.n_events;
-        cells[c] = pcx::SweepCell{round, cell, row, ev, R, (int32_t)N, (int32_t)E, sweep_gen(k)};
-        prefix[c] = round;
-        round += R;
-        cell += R * N * E;
-        row += R * N;
-        ev += R * E;
-    }
-    prefix[C] = round;
-    pcx::SweepTables t;
-    t.cells = static_cast<const pcx::SweepCell*>(dev);
-    t.prefix = reinterpret_cast<const int64_t*>(t.cells + C);
-    t.C = (int32_t)C;
-    t.B = round;
-    return t;
-}
-}  // namespace
-
-// a checked sweep's tables through a staging slot of their own to the device, on the stream (the
-// stand-alone generator and metrics entries); the caller records the slot's kern_ev after its launches
-static int sweep_tables_upload(pcx_ctx* ctx, const pcx_sim_sweep* s, pcx_ctx::RaggedSlot** slot, pcx::SweepTables* t) {
-    const size_t bytes = sweep_table_bytes(s);
-    if (const int rc = ragged_slot_take(ctx, bytes, slot)) return rc;
-    *t = sweep_tables_fill(s, (*slot)->pin, (*slot)->dev);
-    const hipError_t e = ragged_slot_upload(ctx, **slot, bytes);
-    return e == hipSuccess ? PCX_OK : hip_fail(e, "sweep: table upload");
-}
-
-int pcx_sim_sweep_plan(const pcx_sim_sweep* sweep, int64_t totals[4], int64_t counts[4], int64_t lds_bytes[4],
-                       int64_t* bad_cell) {
-    if (!sweep) return fail(PCX_EINVAL, "pcx_sim_sweep_plan: null argument");
-    return sweep_check(sweep, "pcx_sim_sweep_plan", totals, counts, lds_bytes, bad_cell);
-}
-
-int pcx_sim_sweep_generate_host(const pcx_sim_sweep* sweep, int timestep, pcx_sim_rounds* rounds) {
-    if (!sweep || !rounds) return fail(PCX_EINVAL, "pcx_sim_sweep_generate_host: null argument");
-    if (const int rc = sweep_check(sweep, "pcx_sim_sweep_generate_host", nullptr, nullptr, nullptr, nullptr)) return rc;
-    if (const int rc = sim_check_timestep(timestep, "pcx_sim_sweep_generate_host")) return rc;
-    std::vector<char> tab(sweep_table_bytes(sweep));
-    sweep_tables_fill(sweep, tab.data(), tab.data());
-    pcx::sim_sweep_generate_host(reinterpret_cast<const pcx::SweepCell*>(tab.data()), sweep->n_cells,
-                                 (uint32_t)timestep, *rounds);
-    return PCX_OK;
-}
-
-int pcx_sim_sweep_generate_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, int timestep, pcx_sim_rounds* rounds) {
-    if (!ctx || !sweep || !rounds) return fail(PCX_EINVAL, "pcx_sim_sweep_generate_f64: null argument");
-    if (const int rc = sweep_check(sweep, "pcx_sim_sweep_generate_f64", nullptr, nullptr, nullptr, nullptr)) return rc;
-    if (const int rc = sim_check_timestep(timestep, "pcx_sim_sweep_generate_f64")) return rc;
-    if (sweep->n_cells == 0) return PCX_OK;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    pcx_ctx::RaggedSlot* slot = nullptr;
-    pcx::SweepTables tab;
-    if (const int rc = sweep_tables_upload(ctx, sweep, &slot, &tab)) return rc;
-    e = pcx::launch_sim_sweep_generate(tab, (uint32_t)timestep, *rounds, ctx->stream);
-    if (e == hipSuccess) e = hipEventRecord(slot->kern_ev, ctx->stream);
-    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_sim_sweep_generate launch");
-}
-
-int pcx_sim_sweep_metrics_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const pcx_sim_rounds* rounds,
-                              const double* old_rep, const double* smooth_rep, const double* outcomes_final,
-                              double* metrics, double* summary) {
-    if (!ctx || !sweep || !rounds) return fail(PCX_EINVAL, "pcx_sim_sweep_metrics_f64: null argument");
-    if (const int rc = sweep_check(sweep, "pcx_sim_sweep_metrics_f64", nullptr, nullptr, nullptr, nullptr)) return rc;
-    if (sweep->n_cells == 0) return PCX_OK;
-    if (!old_rep || !smooth_rep || !outcomes_final || !metrics)
-        return fail(PCX_EINVAL, "pcx_sim_sweep_metrics_f64: null argument");
-    if (!rounds->scaled || !rounds->lo || !rounds->hi || !rounds->truth || !rounds->liar)
-        return fail(PCX_EINVAL, "pcx_sim_sweep_metrics_f64: rounds needs scaled, lo, hi, truth and liar");
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    pcx_ctx::RaggedSlot* slot = nullptr;
-    pcx::SweepTables tab;
-    if (const int rc = sweep_tables_upload(ctx, sweep, &slot, &tab)) return rc;
-    e = pcx::launch_sim_sweep_metrics(tab, sweep->scaled_tol, *rounds, old_rep, smooth_rep, outcomes_final, metrics,
-                                      ctx->stream);
-    if (e == hipSuccess && summary) e = pcx::launch_sim_sweep_summary(tab, metrics, summary, ctx->stream);
-    if (e == hipSuccess) e = hipEventRecord(slot->kern_ev, ctx->stream);
-    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_sim_sweep_metrics / k_sim_sweep_summary launch");
-}
-
-// bytes of pair_base [C] behind a sweep's tables in a staging slot (a multiple of 8)
-static size_t pair_base_bytes(const pcx_sim_sweep* s) { return ((size_t)s->n_cells * sizeof(int32_t) + 7) / 8 * 8; }
-
-// the pair_base checks of pcx_sim_study_check, on a sweep that sweep_check has passed
-static int study_check(const pcx_sim_sweep* s, const int32_t* pair_base, const char* who, int64_t* bad_cell) {
-    if (bad_cell) *bad_cell = -1;
-    for (int64_t c = 0; pair_base && c < s->n_cells; c++) {
-        const int64_t base = pair_base[c];
-        if (base == -1) continue;
-        if (base < 0 || base >= s->n_cells)
-            return sweep_fail(bad_cell, c, who,
-                              "pair_base " + std::to_string(base) + " is outside [0, " + std::to_string(s->n_cells) +
-                                  ") (-1 = no base)");
-        if (base == c) return sweep_fail(bad_cell, c, who, "pair_base is the cell itself");
-        if (s->cells[base].n_rounds != s->cells[c].n_rounds)
-            return sweep_fail(bad_cell, c, who,
-                              "has " + std::to_string(s->cells[c].n_rounds) + " rounds, its base cell " +
-                                  std::to_string(base) + " has " + std::to_string(s->cells[base].n_rounds) +
-                                  " (a pair is round b of both)");
-    }
-    return PCX_OK;
-}
-
-// The loop of pcx_simulate_sweep_f64, pcx_simulate_study_f64 and pcx_simulate_study_params_f64
-// (`who`).  study NULL: the sweep.  Otherwise every timestep's metrics launch is followed by the
-// detail launch, and one statistics launch follows the last timestep.  cp: per-cell parameter sets
-// [C] (NULL: the sweep's shared ones) -- the consensus launches are then those of
-// pcx_consensus_ragged_params_f64, round b of cell c on set c.
-// restarts > 0 (pcx_simulate_study_kmeans_f64): k-means passes; the call runs on parameter sets (the
-// shared parameters as every cell's set where cp is NULL), every timestep's books of the k-means
-// cells' rounds are drawn into the workspace behind the generator, and the consensus launches are
-// those of pcx_consensus_ragged_kmeans_f64.
-static int sweep_run(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* res, const int32_t* pair_base,
-                     const pcx_sim_study_result* study, const char* who, const pcx_round_params* cp = nullptr,
-                     int restarts = 0) {
-    const std::string name(who);
-    int64_t tot[4], cnt[4], lds[4];
-    const bool km = restarts > 0;
-    if (const int rc = sweep_check(sweep, who, tot, cnt, lds, nullptr, cp, km)) return rc;
-    std::vector<pcx_round_params> own_cp;
-    if (km && !cp) {
-        own_cp.assign((size_t)sweep->n_cells,
-                      pcx_round_params{sweep->algorithm, sweep->max_components, sweep->catch_tolerance, sweep->alpha,
-                                       sweep->variance_threshold, sweep->hierarchy_threshold, sweep->cluster_threshold});
-        cp = own_cp.data();
-    }
-    if (km)
-        if (const int rc = sim_books_check(tot[0], restarts, name)) return rc;
-    if (study) {
-        if (const int rc = study_check(sweep, pair_base, who, nullptr)) return rc;
-        if (study->paired && !pair_base) return fail(PCX_EINVAL, name + ": paired needs pair_base");
-    }
-    const int64_t C = sweep->n_cells, B = tot[0], T = sweep->n_timesteps;
-    if (C == 0) return PCX_OK;
-    if (study && !study->stats) return fail(PCX_EINVAL, name + ": study->stats is NULL");
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    // the cells expanded into the wide ragged call's per-round shapes
-    std::vector<int32_t> shape;
-    try {
-        shape.resize((size_t)B * (cp ? 3 : 2));
-    } catch (const std::bad_alloc&) {
-        return fail(PCX_ENOMEM, name + ": no host memory for the per-round shapes");
-    }
-    int32_t* nrep = shape.data();
-    int32_t* nev = nrep + B;
-    int32_t* pof = cp ? nev + B : nullptr;  // round b's parameter set: its cell
-    for (int64_t c = 0, b = 0; c < C; c++)
-        for (int64_t r = 0; r < sweep->cells[c].n_rounds; r++, b++) {
-            nrep[b] = sweep->cells[c].n_reporters;
-            nev[b] = sweep->cells[c].n_events;
-            if (pof) pof[b] = (int32_t)c;
-        }
-    // work buffers, pcx_simulate_f64's layout over the flat arrays
-    const size_t bn = (size_t)tot[1], be = (size_t)tot[2], bne = (size_t)tot[3];
-    // (a study keeps every timestep's metrics and detail for its statistics: in the workspace, behind
-    // the sweep's doubles, where the caller gives no buffer)
-    const bool all_metrics = study && !res->metrics;
-    const size_t n_metrics = (size_t)(all_metrics ? T : 1) * B * PCX_SIM_NMETRICS;
-    const size_t n_detail = study && !study->detail ? (size_t)T * B * PCX_SIM_NDETAIL : 0;
-    const size_t n_f64 = bne + 4 * be + 3 * bn + n_metrics + n_detail;
-    // (k-means: the flat books of the k-means cells' rounds, int32, behind the bytes)
-    int64_t n_books = 0;
-    if (km)
-        if (const int rc = kmeans_layout(B, nrep, nev, nullptr, restarts, cp, pof, nullptr, nullptr, nullptr, &n_books))
-            return rc;
-    const size_t off_books = (n_f64 * sizeof(double) + be + bn + 3) / 4 * 4;
-    if (const int rc = sim_reserve(ctx, std::max<size_t>(off_books + (size_t)n_books * sizeof(int32_t), 16))) return rc;
-    int32_t* const w_books = reinterpret_cast<int32_t*>(static_cast<char*>(ctx->sim_buf) + off_books);
-    double* p = (double*)ctx->sim_buf;
-    auto take = [&p](size_t n) {
-        double* q = p;
-        p += n;
-        return q;
-    };
-    pcx_sim_rounds work;
-    work.reports = take(bne);
-    work.lo = take(be);
-    work.hi = take(be);
-    work.truth = take(be);
-    double* w_outcomes = take(be);
-    double* w_old = take(bn);
-    double* w_smooth[2] = {take(bn), take(bn)};
-    double* w_metrics = take(n_metrics);
-    double* all_detail = study ? (study->detail ? study->detail : take(n_detail)) : nullptr;
-    work.scaled = (uint8_t*)p;
-    work.liar = work.scaled + be;
-    // every table of the call in one staging slot, uploaded once: the wide ragged call's descriptors
-    // (the same every timestep: only the data pointers change), then the sweep's own
-    WidePlan plan;
-    ParamsPlan pplan;
-    const bool pairs = study && study->paired;
-    const size_t off_ktab = sweep_table_bytes(sweep) + (pairs ? pair_base_bytes(sweep) : 0);  // inside `extra`
-    const size_t extra = off_ktab + (km ? (size_t)B * sizeof(pcx::KmeansEntry) : 0);
-    if (cp) {
-        params_count(B, nrep, nev, cp, pof, &pplan);
-        if (const int rc = params_tables(ctx, nrep, nev, C, cp, pof, false, extra, &pplan)) return rc;
-    } else if (const int rc = wide_tables(ctx, B, nrep, nev, sweep->algorithm, false, cnt, lds, false, extra, &plan)) {
-        return rc;
-    }
-    pcx_ctx::RaggedSlot* const slot = cp ? pplan.slot : plan.slot;
-    const size_t off_x = cp ? pplan.off_x : plan.off_x, up_bytes = cp ? pplan.bytes : plan.bytes;
-    const pcx::SweepTables tab = sweep_tables_fill(sweep, static_cast<char*>(slot->pin) + off_x,
-                                                   static_cast<char*>(slot->dev) + off_x);
-    const int32_t* dev_base = nullptr;  // pair_base rides behind the sweep's tables
-    if (pairs) {
-        const size_t at = off_x + sweep_table_bytes(sweep);
-        std::memcpy(static_cast<char*>(slot->pin) + at, pair_base, (size_t)C * sizeof(int32_t));
-        dev_base = reinterpret_cast<const int32_t*>(static_cast<char*>(slot->dev) + at);
-    }
-    const pcx::KmeansEntry* dev_ktab = nullptr;  // the per-round book table rides last
-    if (km) {
-        (void)kmeans_layout(B, nrep, nev, nullptr, restarts, cp, pof, nullptr,
-                            reinterpret_cast<pcx::KmeansEntry*>(static_cast<char*>(slot->pin) + off_x + off_ktab), nullptr);
-        dev_ktab = reinterpret_cast<const pcx::KmeansEntry*>(static_cast<char*>(slot->dev) + off_x + off_ktab);
-    }
-    e = ragged_slot_upload(ctx, *slot, up_bytes);
-    if (e != hipSuccess) return hip_fail(e, "sweep: table upload");
-    const double* rep = sweep->reputation0;
-    for (int64_t t = 0; t < T; t++) {  // launches only: no host wait in this loop
-        const bool last = t == T - 1;
-        pcx_sim_rounds r = work;
-        pcx_batch_result o{};
-        if (last) {  // the caller's buffers where given
-            const pcx_sim_rounds& u = res->last;
-            if (u.reports) r.reports = u.reports;
-            if (u.scaled) r.scaled = u.scaled;
-            if (u.lo) r.lo = u.lo;
-            if (u.hi) r.hi = u.hi;
-            if (u.truth) r.truth = u.truth;
-            if (u.liar) r.liar = u.liar;
-            o = res->last_out;
-        }
-        if (!o.old_rep) o.old_rep = w_old;
-        if (!o.smooth_rep) o.smooth_rep = w_smooth[t & 1];
-        if (!o.outcomes_final) o.outcomes_final = w_outcomes;
-        e = pcx::launch_sim_sweep_generate(tab, (uint32_t)t, r, ctx->stream);
-        if (e != hipSuccess) return hip_fail(e, "k_sim_sweep_generate launch");
-        pcx_ragged in{};
-        in.n_rounds = B;
-        in.reports = r.reports;
-        in.reputation = rep;
-        in.scaled = r.scaled;
-        in.lo = r.lo;
-        in.hi = r.hi;
-        in.catch_tolerance = sweep->catch_tolerance;
-        in.alpha = sweep->alpha;
-        in.algorithm = sweep->algorithm;
-        in.max_components = sweep->max_components;
-        in.variance_threshold = sweep->variance_threshold;
-        in.hierarchy_threshold = sweep->hierarchy_threshold;
-        in.cluster_threshold = sweep->cluster_threshold;
-        pcx::BatchArgs a = shared_args(&in, &o);
-        a.B = B;
-        if (km && n_books > 0) {
-            e = pcx::launch_sim_sweep_kmeans_books(tab, dev_ktab, restarts, (uint32_t)t, w_books, ctx->stream);
-            if (e != hipSuccess) return hip_fail(e, "k_kmeans_books_sweep launch");
-            a.kmeans_restarts = restarts;
-            a.kmeans_init = w_books;
-        }
-        e = km ? kmeans_launch(ctx, pplan, a, dev_ktab) : cp ? params_launch(ctx, pplan, a) : wide_launch(ctx, plan, a);
-        if (e != hipSuccess) return hip_fail(e, "sweep: ragged wide launch");
-        if (res->metrics || res->summary || study) {
-            double* m = res->metrics   ? res->metrics + (size_t)t * B * PCX_SIM_NMETRICS
-                        : all_metrics ? w_metrics + (size_t)t * B * PCX_SIM_NMETRICS
-                                      : w_metrics;
-            e = pcx::launch_sim_sweep_metrics(tab, sweep->scaled_tol, r, o.old_rep, o.smooth_rep, o.outcomes_final, m,
-                                              ctx->stream);
-            if (e == hipSuccess && res->summary)
-                e = pcx::launch_sim_sweep_summary(tab, m, res->summary + (size_t)t * C * PCX_SIM_NMETRICS,
-                                                  ctx->stream);
-            if (e != hipSuccess) return hip_fail(e, "k_sim_sweep_metrics / k_sim_sweep_summary launch");
-        }
-        if (study) {
-            e = pcx::launch_sim_study_detail(tab, 0, 0, sweep->scaled_tol, r, o.old_rep, o.smooth_rep, o.outcomes_final,
-                                             all_detail + (size_t)t * B * PCX_SIM_NDETAIL, ctx->stream);
-            if (e != hipSuccess) return hip_fail(e, "k_sim_study_detail launch");
-        }
-        rep = o.smooth_rep;  // the next timestep's reputation
-    }
-    if (study) {
-        e = pcx::launch_sim_study_stats(tab, T, res->metrics ? res->metrics : w_metrics, all_detail, dev_base,
-                                        study->stats, pairs ? study->paired : nullptr, ctx->stream);
-        if (e != hipSuccess) return hip_fail(e, "k_sim_study_stats launch");
-    }
-    e = hipEventRecord(slot->kern_ev, ctx->stream);
-    if (e != hipSuccess) return hip_fail(e, "sweep: hipEventRecord");
-    if (res->reputation && bn) {
-        e = hipMemcpyAsync(res->reputation, rep, bn * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
-        if (e != hipSuccess) return hip_fail(e, (name + ": reputation copy").c_str());
-    }
-    return PCX_OK;
-}
-
-int pcx_simulate_sweep_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* res) {
-    if (!ctx || !sweep || !res) return fail(PCX_EINVAL, "pcx_simulate_sweep_f64: null argument");
-    return sweep_run(ctx, sweep, res, nullptr, nullptr, "pcx_simulate_sweep_f64");
-}
-
-// ---------------------------------------------------------------- simulator studies
-int pcx_simulate_study_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const int32_t* pair_base, pcx_sim_result* res,
-                           pcx_sim_study_result* study) {
-    if (!ctx || !sweep || !res || !study) return fail(PCX_EINVAL, "pcx_simulate_study_f64: null argument");
-    return sweep_run(ctx, sweep, res, pair_base, study, "pcx_simulate_study_f64");
-}
-
-int pcx_sim_study_params_check(const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,
-                               const int32_t* pair_base, int64_t* bad_cell) {
-    if (!sweep) return fail(PCX_EINVAL, "pcx_sim_study_params_check: null argument");
-    if (const int rc = sweep_check(sweep, "pcx_sim_study_params_check", nullptr, nullptr, nullptr, bad_cell, cell_params))
-        return rc;
-    return study_check(sweep, pair_base, "pcx_sim_study_params_check", bad_cell);
-}
-
-int pcx_simulate_study_params_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,
-                                  const int32_t* pair_base, pcx_sim_result* res, pcx_sim_study_result* study) {
-    if (!ctx || !sweep || !res) return fail(PCX_EINVAL, "pcx_simulate_study_params_f64: null argument");
-    if (!cell_params)  // the existing entries, the same bytes
-        return study ? pcx_simulate_study_f64(ctx, sweep, pair_base, res, study) : pcx_simulate_sweep_f64(ctx, sweep, res);
-    return sweep_run(ctx, sweep, res, study ? pair_base : nullptr, study, "pcx_simulate_study_params_f64", cell_params);
-}
-
-int pcx_sim_study_kmeans_check(const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,
-                               const int32_t* pair_base, int32_t restarts, int64_t* bad_cell) {
-    const char* who = "pcx_sim_study_kmeans_check";
-    if (!sweep) return fail(PCX_EINVAL, std::string(who) + ": null argument");
-    if (bad_cell) *bad_cell = -1;
-    if (restarts < 1) return fail(PCX_EINVAL, std::string(who) + ": k-means restarts must be >= 1");
-    int64_t tot[4];
-    if (const int rc = sweep_check(sweep, who, tot, nullptr, nullptr, bad_cell, cell_params, true)) return rc;
-    if (const int rc = sim_books_check(tot[0], restarts, who)) return rc;
-    return study_check(sweep, pair_base, who, bad_cell);
-}
-
-int pcx_simulate_study_kmeans_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,
-                                  const int32_t* pair_base, int32_t restarts, pcx_sim_result* res,
-                                  pcx_sim_study_result* study) {
-    if (!ctx || !sweep || !res) return fail(PCX_EINVAL, "pcx_simulate_study_kmeans_f64: null argument");
-    if (restarts < 1) return fail(PCX_EINVAL, "pcx_simulate_study_kmeans_f64: k-means restarts must be >= 1");
-    return sweep_run(ctx, sweep, res, study ? pair_base : nullptr, study, "pcx_simulate_study_kmeans_f64", cell_params,
-                     restarts);
-}
-
-// the book table of a sweep whose every round is k-means under the rule (pcx_kmeans_plan's layout)
-static int sweep_books_table(const pcx_sim_sweep* sweep, int restarts, const char* who, std::vector<char>* cells,
-                             std::vector<pcx::KmeansEntry>* tab, int64_t* B) {
-    int64_t tot[4];
-    if (const int rc = sweep_check(sweep, who, tot, nullptr, nullptr, nullptr, nullptr, true)) return rc;
-    if (const int rc = sim_books_check(tot[0], restarts, who)) return rc;
-    *B = tot[0];
-    cells->resize(sweep_table_bytes(sweep));
-    sweep_tables_fill(sweep, cells->data(), cells->data());
-    tab->resize((size_t)tot[0]);
-    std::vector<int32_t> shape((size_t)tot[0] * 2);
-    for (int64_t c = 0, b = 0; c < sweep->n_cells; c++)
-        for (int64_t r = 0; r < sweep->cells[c].n_rounds; r++, b++) {
-            shape[b] = sweep->cells[c].n_reporters;
-            shape[tot[0] + b] = sweep->cells[c].n_events;
-        }
-    return kmeans_layout(tot[0], shape.data(), shape.data() + tot[0], nullptr, restarts, nullptr, nullptr, nullptr,
-                         tab->data(), nullptr);
-}
-
-int pcx_sim_sweep_kmeans_books_host(const pcx_sim_sweep* sweep, int32_t restarts, int timestep, int32_t* books) {
-    const char* who = "pcx_sim_sweep_kmeans_books_host";
-    if (!sweep || !books) return fail(PCX_EINVAL, std::string(who) + ": null argument");
-    if (const int rc = sim_check_timestep(timestep, who)) return rc;
-    std::vector<char> cells;
-    std::vector<pcx::KmeansEntry> tab;
-    int64_t B = 0;
-    if (const int rc = sweep_books_table(sweep, restarts, who, &cells, &tab, &B)) return rc;
-    pcx::sim_sweep_kmeans_books_host(reinterpret_cast<const pcx::SweepCell*>(cells.data()), sweep->n_cells, tab.data(),
-                                     restarts, (uint32_t)timestep, books);
-    return PCX_OK;
-}
-
-int pcx_sim_sweep_kmeans_books_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, int32_t restarts, int timestep,
-                                   int32_t* books) {
-    const char* who = "pcx_sim_sweep_kmeans_books_f64";
-    if (!ctx || !sweep || !books) return fail(PCX_EINVAL, std::string(who) + ": null argument");
-    if (const int rc = sim_check_timestep(timestep, who)) return rc;
-    std::vector<char> cells;
-    std::vector<pcx::KmeansEntry> tab;
-    int64_t B = 0;
-    if (const int rc = sweep_books_table(sweep, restarts, who, &cells, &tab, &B)) return rc;
-    if (B == 0) return PCX_OK;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    // the sweep's tables and the book table through one staging slot
-    const size_t tb = sweep_table_bytes(sweep), kb = (size_t)B * sizeof(pcx::KmeansEntry);
-    pcx_ctx::RaggedSlot* slot = nullptr;
-    if (const int rc = ragged_slot_take(ctx, tb + kb, &slot)) return rc;
-    const pcx::SweepTables t = sweep_tables_fill(sweep, slot->pin, slot->dev);
-    std::memcpy(static_cast<char*>(slot->pin) + tb, tab.data(), kb);
-    e = ragged_slot_upload(ctx, *slot, tb + kb);
-    if (e != hipSuccess) return hip_fail(e, "sweep: table upload");
-    e = pcx::launch_sim_sweep_kmeans_books(t, reinterpret_cast<const pcx::KmeansEntry*>(static_cast<char*>(slot->dev) + tb),
-                                           restarts, (uint32_t)timestep, books, ctx->stream);
-    if (e == hipSuccess) e = hipEventRecord(slot->kern_ev, ctx->stream);
-    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_kmeans_books_sweep launch");
-}
-
-int pcx_sim_study_check(const pcx_sim_sweep* sweep, const int32_t* pair_base, int64_t* bad_cell) {
-    if (!sweep) return fail(PCX_EINVAL, "pcx_sim_study_check: null argument");
-    if (const int rc = sweep_check(sweep, "pcx_sim_study_check", nullptr, nullptr, nullptr, bad_cell)) return rc;
-    return study_check(sweep, pair_base, "pcx_sim_study_check", bad_cell);
-}
-
-static bool detail_args(const pcx_sim_rounds* r, const double* old_rep, const double* smooth_rep,
-                        const double* outcomes_final, const double* detail) {
-    return r->scaled && r->lo && r->hi && r->truth && r->liar && old_rep && smooth_rep && outcomes_final && detail;
-}
-
-int pcx_sim_detail_host(const pcx_sim* sim, const pcx_sim_rounds* rounds, const double* old_rep,
-                        const double* smooth_rep, const double* outcomes_final, double* detail) {
-    if (!sim || !rounds) return fail(PCX_EINVAL, "pcx_sim_detail_host: null argument");
-    if (const int rc = sim_check(sim, "pcx_sim_detail_host")) return rc;
-    if (!detail_args(rounds, old_rep, smooth_rep, outcomes_final, detail))
-        return fail(PCX_EINVAL, "pcx_sim_detail_host: null argument (rounds needs scaled, lo, hi, truth and liar)");
-    pcx::sim_study_detail_host(nullptr, 0, sim->n_rounds, (int32_t)sim->n_reporters, (int32_t)sim->n_events,
-                               sim->scaled_tol, *rounds, old_rep, smooth_rep, outcomes_final, detail);
-    return PCX_OK;
-}
-
-int pcx_sim_detail_f64(pcx_ctx* ctx, const pcx_sim* sim, const pcx_sim_rounds* rounds, const double* old_rep,
-                       const double* smooth_rep, const double* outcomes_final, double* detail) {
-    if (!ctx || !sim || !rounds) return fail(PCX_EINVAL, "pcx_sim_detail_f64: null argument");
-    if (const int rc = sim_check(sim, "pcx_sim_detail_f64")) return rc;
-    if (!detail_args(rounds, old_rep, smooth_rep, outcomes_final, detail))
-        return fail(PCX_EINVAL, "pcx_sim_detail_f64: null argument (rounds needs scaled, lo, hi, truth and liar)");
-    if (sim->n_reporters > 0x7fffffff || sim->n_events > 0x7fffffff)
-        return fail(PCX_EINVAL, "pcx_sim_detail_f64: n_reporters and n_events must be below 2^31");
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    pcx::SweepTables tab{nullptr, nullptr, 0, sim->n_rounds};
-    e = pcx::launch_sim_study_detail(tab, (int32_t)sim->n_reporters, (int32_t)sim->n_events, sim->scaled_tol, *rounds,
-                                     old_rep, smooth_rep, outcomes_final, detail, ctx->stream);
-    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_sim_study_detail launch");
-}
-
-int pcx_sim_sweep_detail_host(const pcx_sim_sweep* sweep, const pcx_sim_rounds* rounds, const double* old_rep,
-                              const double* smooth_rep, const double* outcomes_final, double* detail) {
-    if (!sweep || !rounds) return fail(PCX_EINVAL, "pcx_sim_sweep_detail_host: null argument");
-    if (const int rc = sweep_check(sweep, "pcx_sim_sweep_detail_host", nullptr, nullptr, nullptr, nullptr)) return rc;
-    if (sweep->n_cells == 0) return PCX_OK;
-    if (!detail_args(rounds, old_rep, smooth_rep, outcomes_final, detail))
-        return fail(PCX_EINVAL, "pcx_sim_sweep_detail_host: null argument (rounds needs scaled, lo, hi, truth and liar)");
-    std::vector<char> tab(sweep_table_bytes(sweep));
-    const pcx::SweepTables t = sweep_tables_fill(sweep, tab.data(), tab.data());
-    pcx::sim_study_detail_host(t.cells, t.C, t.B, 0, 0, sweep->scaled_tol, *rounds, old_rep, smooth_rep, outcomes_final,
-                               detail);
-    return PCX_OK;
-}
-
-int pcx_sim_sweep_detail_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const pcx_sim_rounds* rounds,
-                             const double* old_rep, const double* smooth_rep, const double* outcomes_final,
-                             double* detail) {
-    if (!ctx || !sweep || !rounds) return fail(PCX_EINVAL, "pcx_sim_sweep_detail_f64: null argument");
-    if (const int rc = sweep_check(sweep, "pcx_sim_sweep_detail_f64", nullptr, nullptr, nullptr, nullptr)) return rc;
-    if (sweep->n_cells == 0) return PCX_OK;
-    if (!detail_args(rounds, old_rep, smooth_rep, outcomes_final, detail))
-        return fail(PCX_EINVAL, "pcx_sim_sweep_detail_f64: null argument (rounds needs scaled, lo, hi, truth and liar)");
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    pcx_ctx::RaggedSlot* slot = nullptr;
-    pcx::SweepTables tab;
-    if (const int rc = sweep_tables_upload(ctx, sweep, &slot, &tab)) return rc;
-    e = pcx::launch_sim_study_detail(tab, 0, 0, sweep->scaled_tol, *rounds, old_rep, smooth_rep, outcomes_final, detail,
-                                     ctx->stream);
-    if (e == hipSuccess) e = hipEventRecord(slot->kern_ev, ctx->stream);
-    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_sim_study_detail launch");
-}
-
-// what the two statistics entries check alike
-static int stats_check(const pcx_sim_sweep* sweep, const double* metrics, const double* detail,
-                       const int32_t* pair_base, const double* stats, const double* paired, const char* who) {
-    if (const int rc = sweep_check(sweep, who, nullptr, nullptr, nullptr, nullptr)) return rc;
-    if (const int rc = study_check(sweep, pair_base, who, nullptr)) return rc;
-    if (paired && !pair_base) return fail(PCX_EINVAL, std::string(who) + ": paired needs pair_base");
-    if (sweep->n_cells > 0 && (!metrics || !detail || !stats)) return fail(PCX_EINVAL, std::string(who) + ": null argument");
-    return PCX_OK;
-}
-
-int pcx_sim_sweep_stats_host(const pcx_sim_sweep* sweep, const double* metrics, const double* detail,
-                             const int32_t* pair_base, double* stats, double* paired) {
-    if (!sweep) return fail(PCX_EINVAL, "pcx_sim_sweep_stats_host: null argument");
-    if (const int rc = stats_check(sweep, metrics, detail, pair_base, stats, paired, "pcx_sim_sweep_stats_host"))
-        return rc;
-    if (sweep->n_cells == 0) return PCX_OK;
-    std::vector<char> tab(sweep_table_bytes(sweep));
-    const pcx::SweepTables t = sweep_tables_fill(sweep, tab.data(), tab.data());
-    pcx::sim_study_stats_host(t.cells, t.C, t.B, sweep->n_timesteps, metrics, detail, pair_base, stats, paired);
-    return PCX_OK;
-}
-
-int pcx_sim_sweep_stats_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const double* metrics, const double* detail,
-                            const int32_t* pair_base, double* stats, double* paired) {
-    if (!ctx || !sweep) return fail(PCX_EINVAL, "pcx_sim_sweep_stats_f64: null argument");
-    if (const int rc = stats_check(sweep, metrics, detail, pair_base, stats, paired, "pcx_sim_sweep_stats_f64"))
-        return rc;
-    if (sweep->n_cells == 0) return PCX_OK;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    // the sweep's tables and, behind them, pair_base in one staging slot
-    const size_t bytes = sweep_table_bytes(sweep), all = bytes + (paired ? pair_base_bytes(sweep) : 0);
-    pcx_ctx::RaggedSlot* slot = nullptr;
-    if (const int rc = ragged_slot_take(ctx, all, &slot)) return rc;
-    const pcx::SweepTables tab = sweep_tables_fill(sweep, slot->pin, slot->dev);
-    const int32_t* dev_base = nullptr;
-    if (paired) {
-        std::memcpy(static_cast<char*>(slot->pin) + bytes, pair_base, (size_t)sweep->n_cells * sizeof(int32_t));
-        dev_base = reinterpret_cast<const int32_t*>(static_cast<char*>(slot->dev) + bytes);
-    }
-    e = ragged_slot_upload(ctx, *slot, all);
-    if (e != hipSuccess) return hip_fail(e, "study: table upload");
-    e = pcx::launch_sim_study_stats(tab, sweep->n_timesteps, metrics, detail, dev_base, stats, paired, ctx->stream);
-    if (e == hipSuccess) e = hipEventRecord(slot->kern_ev, ctx->stream);
-    return e == hipSuccess ? PCX_OK : hip_fail(e, "k_sim_study_stats launch");
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-"""Context lifecycle (pcx_api.cpp / pcx_runner.cpp / pcx_rounds.cpp): the host resources a context
+"""Context lifecycle (pcx_api.cpp / pcx_runner.cpp / pcx_rounds.cpp; the ragged staging slots and the
+simulator's work buffers it frees are filled by pcx_ragged.cpp / pcx_simulate.cpp): the host resources a context
 gathers over mixed calls are each freed once, whatever the order they were made in.
 
 Round 5 shipped a stray hipHostFree of the pinned staging slots inside the medium-scratch growth
