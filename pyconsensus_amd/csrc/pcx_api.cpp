@@ -333,7 +333,13 @@ static void print_wave_stamps(const std::vector<long long>& h, int64_t B) {
     }
     fprintf(stderr, " median_sort:%.0f median_walk:%.0f outcome_shortcut:%.4f outcome_sorted:%.4f", sort / (double)B,
             walk / (double)B, fast / (double)B, slow / (double)B);
-    fprintf(stderr, " interp_screened:%.4f interp_sorted:%.4f\n", iscr / (double)B, isort / (double)B);
+    double grep = 0, gtot = 0;  // 26, 27: binary guesses from the exact replay / rounds that ran the replay
+    for (int64_t b = 0; b < B; b++) {
+        grep += (double)h[b * 32 + 26];
+        gtot += (double)h[b * 32 + 27];
+    }
+    fprintf(stderr, " interp_screened:%.4f interp_sorted:%.4f", iscr / (double)B, isort / (double)B);
+    fprintf(stderr, " guess_replayed:%.4f replay_rounds:%.4f\n", grep / (double)B, gtot / (double)B);
 }
 
 // PCX_STAMPS, workgroup kernel: stamps 0..15 in program order (pcx_medium.hip MSTAMP(k))

@@ -211,48 +211,96 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
     // ---- a3: interpolation guesses (:284-313), column phase ----------------
     uint64_t miss_j = 0;
     if (col) miss_j = S.miss[l];
+    // every reputation >= 0 (a NaN fails): the condition of the row-split sums here and of the
+    // prescreen below.  Equal reputations (reputation == nullptr) are 1 / N and pass.
+    const bool nonneg = !ballot(row && !(rep >= 0.0));
+    const bool binary_fill = col && miss_j && !scj;
+    bool tot_exact;          // S.tot holds the SPEC's sequential totals (else the row-split ones)
+    uint64_t need_bin = 0;   // the binary columns whose guess waits for the exact replay (below)
     {
-        // tot: the SPEC's sequential sum of the present reputations (a missing row adds
-        // +0.0, which leaves a sum that starts at +0.0 unchanged).  A binary column's
-        // guess only matters through catch(): the sum of (rep/tot)*F is formed cheaply as
-        // (sum rep*F)/tot, and the SPEC's exact sequential sum is replayed only for a
-        // column whose cheap value lies within 1e-12 * sum|rep*F|/tot of a catch threshold
-        // (the two differ by at most ~2*(N+2) ulp of that magnitude), so the caught value
-        // is the SPEC's bit for bit.  Scaled columns only need tot here (the median).
-        constexpr int NR = NT > 0 ? NT : 64;
+        // The fast sums of column c over its present rows: tot = sum rep, sp = sum rep * F,
+        // sa = sum |rep| * |F|.  A binary column's guess only matters through catch(): it is
+        // catch(sp / tot) where that value clears both thresholds by 1e-12 * sa / tot, and the
+        // SPEC's exact sequential sum is replayed otherwise (after the prescreen, below).  A
+        // scaled column's tot feeds the prescreen, whose margin is 2^-16 tot; the sort divides by
+        // the SPEC's sequential total, replayed with the binary columns'.
+        //   Row-split (every rep >= 0 and 3 E <= 64): lane g * E + c sums column c's rows g, g + 3,
+        // g + 6, ... in ascending order, and lane c takes (p0 + p1) + p2 by ds_bpermute: chains a
+        // third as long on lanes that idle otherwise.  Each split sum is within (N + N / 3 + 1) u
+        // of the sum of its terms' magnitudes from the sequential one (DESIGN.md 5.2), fifty times
+        // inside the fast test's margin, and tot' > 0 exactly when the sequential total is (no term < 0).
+        //   Otherwise the sums run on lane c over all its rows in row order (G = 1): tot is then
+        // the SPEC's own.  A compiled shape's round with a negative or NaN reputation forms no
+        // fast sums at all: every guess and total of it comes from the replay.
+        constexpr bool SPLITC = NT > 0 && ET > 0 && 3 * ET <= W;
+        const bool split = SPLITC ? nonneg : (nonneg && 3 * E <= W);
+        const bool sums = SPLITC ? nonneg : true;
+        tot_exact = SPLITC ? false : !split;
         double tot = 0.0, sp = 0.0, sa = 0.0;
-#pragma unroll 10
-        for (int i = 0; i < NR; i++) {
-            if (i < N) {
-                const bool miss = (miss_j >> i) & 1;
+        const int g = split ? (l >= E) + (l >= 2 * E) : 0;
+        const bool live = l < (split ? 3 * E : E);
+        const int c = live ? l - g * E : 0;
+        // bit k of m: row g + k is missing.  Rows past N and idle lanes count as missing.
+        uint64_t m = ~0ull;
+        if (sums) {
+            const uint64_t past = N < 64 ? ~0ull << N : 0ull;
+            const uint64_t mc = split ? S.miss[c] : miss_j;
+            m = live ? ((mc | past) >> g) | ~(~0ull >> g) : ~0ull;
+        }
+        if constexpr (SPLITC) {
+            if (split) {
+                // every bound, offset and bit position a constant: the loads are unconditional
+                // (two rows past F's end lie in the round's own LDS, idle lanes read column 0)
+                // and a missing row is zeroed by selects: rep to +0.0, F by its high word alone
+                // (what is left is finite, and 0 times it is 0)
+                constexpr int TS = (NT + 2) / 3;
+                const double* const Fp = S.F + g * ES + c;
+                const double* const rp = S.rep + g;
+                const uint32_t mlo = (uint32_t)m, mhi = (uint32_t)(m >> 32);
+#pragma unroll
+                for (int t = 0; t < TS; t++) {
+                    const bool miss = ((3 * t < 32 ? mlo : mhi) & (1u << ((3 * t) & 31))) != 0;
+                    const double r0 = rp[3 * t];
+                    const uint64_t fu = (uint64_t)__double_as_longlong(Fp[3 * t * ES]);
+                    const uint32_t fh = miss ? 0u : (uint32_t)(fu >> 32);
+                    const double re = miss ? 0.0 : r0;
+                    const double f = __longlong_as_double((long long)(((uint64_t)fh << 32) | (uint32_t)fu));
+                    tot = tot + re;
+                    sp = fma(re, f, sp);
+                    sa = fma(re, fabs(f), sa);
+                }
+            }
+        } else {
+            const int G = split ? 3 : 1;
+            const double* const Fc = S.F + c;
+            for (int k = 0; k < N; k += G) {
+                const bool miss = (m >> k) & 1;
+                const int i = g + k;
                 const double re = miss ? 0.0 : S.rep[i];
-                const double f = miss ? 0.0 : S.F[i * ES + (col ? l : 0)];
+                const double f = miss ? 0.0 : Fc[i * ES];
                 tot = tot + re;
                 sp = fma(re, f, sp);
                 sa = fma(fabs(re), fabs(f), sa);
             }
         }
+        if (split) {  // lane c: (p0 + p1) + p2
+            const int l1 = (l + E) & (W - 1), l2 = (l + 2 * E) & (W - 1);
+            const double t1 = bpermute_d(l1, tot), t2 = bpermute_d(l2, tot);
+            const double p1 = bpermute_d(l1, sp), p2 = bpermute_d(l2, sp);
+            const double a1 = bpermute_d(l1, sa), a2 = bpermute_d(l2, sa);
+            tot = (tot + t1) + t2;
+            sp = (sp + p1) + p2;
+            sa = (sa + a1) + a2;
+        }
         const double t_lo = 1.5 - a.catch_tol, t_hi = 1.5 + a.catch_tol;  // catch_() thresholds
         const double accf = sp / tot, margin = 1e-12 * (sa / tot);
-        const bool binary_fill = col && miss_j && !scj;
-        const bool fast = tot > 0.0 && __builtin_isfinite(accf) && __builtin_isfinite(margin) &&
+        const bool fast = sums && tot > 0.0 && __builtin_isfinite(accf) && __builtin_isfinite(margin) &&
                           fabs(accf - t_lo) > margin && fabs(accf - t_hi) > margin;
-        double acc = accf;
-        if (ballot(binary_fill && !fast)) {
-            double ex = 0.0;  // SPEC: sum of (rep/tot)*F over the present rows, in row order
-#pragma unroll
-            for (int i = 0; i < NR; i++) {
-                if (i < N) {
-                    const double t = (S.rep[i] / tot) * S.F[i * ES + (col ? l : 0)];
-                    ex = ((miss_j >> i) & 1) ? ex : ex + t;
-                }
-            }
-            if (!fast) acc = ex;
-        }
-        if (binary_fill) {
-            double g = catch_(acc, a.catch_tol);
-            if (a.int_dtype) g = trunc(g);
-            S.guess[l] = g;
+        need_bin = ballot(binary_fill && !fast);
+        if (binary_fill && fast) {
+            double gs = catch_(accf, a.catch_tol);
+            if (a.int_dtype) gs = trunc(gs);
+            S.guess[l] = gs;
         }
         if (col && miss_j) S.tot[l] = tot;  // the present-reputation total, for the median phase
     }
@@ -283,7 +331,7 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
         // the prescreen's work, and the batch measured slower than with the sort alone (DESIGN.md 5.2).
         constexpr int NRS = NT > 0 ? NT : 64, KP = (NRS + 3) & ~3;
         const uint64_t all_j = todo;
-        if (todo && a.reputation && !ballot(row && !(rep >= 0.0))) {
+        if (todo && a.reputation && nonneg) {
             uint32_t* const kx = reinterpret_cast<uint32_t*>(S.M);
             float* const wf = reinterpret_cast<float*>(S.M) + KP;
             if (l < KP) wf[l] = row ? (float)rep : 0.f;
@@ -303,6 +351,45 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
         if (a.stamps && l == 0) {  // diagnostic counters: plain stores, no clock read
             a.stamps[b * 32 + 24] = popc(all_j) - popc(todo);
             a.stamps[b * 32 + 25] = popc(todo);
+        }
+        // The exact replay, the SPEC's sequential form: tot in row order (a missing row adds +0.0,
+        // which leaves a sum that starts at +0.0 unchanged), then sum (rep / tot) * F in row order.
+        // Wave-wide when a binary column's fast value did not clear the thresholds (or the round
+        // formed no fast sums), or when a median goes to the sort, which divides by the exact total.
+        const bool replay = need_bin || (todo && !tot_exact);
+        if (a.stamps && l == 0) {
+            a.stamps[b * 32 + 26] = popc(need_bin);
+            a.stamps[b * 32 + 27] = replay;
+        }
+        if (replay) {
+            constexpr int NR = NT > 0 ? NT : 64;
+            const double* const Fc = S.F + (col ? l : 0);
+            double tot = 0.0;
+#pragma unroll 10
+            for (int i = 0; i < NR; i++) {
+                if (i < N) {
+                    const bool miss = (miss_j >> i) & 1;
+                    const double re = miss ? 0.0 : S.rep[i];
+                    tot = tot + re;
+                }
+            }
+            if (need_bin) {
+                double ex = 0.0;
+#pragma unroll 10
+                for (int i = 0; i < NR; i++) {
+                    if (i < N) {
+                        const double t = (S.rep[i] / tot) * Fc[i * ES];
+                        ex = ((miss_j >> i) & 1) ? ex : ex + t;
+                    }
+                }
+                if ((need_bin >> l) & 1) {
+                    double gs = catch_(ex, a.catch_tol);
+                    if (a.int_dtype) gs = trunc(gs);
+                    S.guess[l] = gs;
+                }
+            }
+            if (col && miss_j) S.tot[l] = tot;
+            wsync();
         }
         // the rest one median at a time: the scratch lives in M, dead until the covariance
         while (todo) {
