@@ -273,6 +273,114 @@ __device__ PCX_OUTLINE double wave_pw_sum_prefix(double v, int nrt) {
     return res;
 }
 
+// lane l <- lane l + D of its 16-lane row (row_shl: the lanes past the row's end read +0.0)
+template <int D>
+__device__ __forceinline__ double shl_lane(double v) {
+    const uint64_t u = (uint64_t)__double_as_longlong(v);
+    const uint32_t lo = dpp32<0x100 + D>((uint32_t)u), hi = dpp32<0x100 + D>((uint32_t)(u >> 32));
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
+// numpy's fixed tree over eight accumulators r_k on lanes 8 q + k, k < 8, of a 16-lane row: lane 8 q
+// ends with ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), three DPP steps.  Lane 8 q + 1 forms
+// r1 + r0 where lane 8 q forms r0 + r1, and so on: the operand order inside an addition does not
+// change its bits.  The last step is row_shl:4 alone, since only lane 8 q reads the result.
+__device__ __forceinline__ double pw_tree8(double c) {
+    c = c + xor_lane<1>(c);
+    c = c + xor_lane<2>(c);
+    return c + shl_lane<4>(c);
+}
+
+// wave_pw_sum_prefix with the accumulator chains in lanes 0..7, the values staged in LDS: lane l
+// reads scr[(l & 7) + 8 t] and adds in t order (a compiled shape: one ds_read per step, the offsets
+// immediates, all of them issued ahead of the adds), pw_tree8 leaves the tree's result on lane 0,
+// the tail is added from LDS broadcast reads, and one readlane pair makes the sum wave-uniform.
+// Every chain starts from its first element (no 0.0 enters: a -0.0 stays -0.0).  Same additions in
+// the same order as wave_pw_sum_prefix, with no permute, no DPP chain and no readlane per accumulator.
+// scr: n doubles of LDS that are dead at the call (the first wsync orders the caller's last reads of
+// them before the store).  n < 8 keeps the readlane loop.
+template <int NC>
+__device__ PCX_OUTLINE double wave_pw_sum_lds(double v, int nrt, double* scr) {
+    const int l = lane_id();
+    const int n = NC > 0 ? NC : nrt;
+    if (n < 8) {
+        double res = 0.0;
+        for (int k = 0; k < n; k++) res += readlane_d(v, k);
+        return res;
+    }
+    wsync();
+    if (l < n) scr[l] = v;
+    wsync();
+    const int T = n >> 3;
+    const double* const p = scr + (l & 7);
+    double c = p[0];
+    if constexpr (NC > 0) {
+#pragma unroll
+        for (int t = 1; t < NC / 8; t++) c = c + p[8 * t];
+    } else {
+        for (int t = 1; t < T; t++) c = c + p[8 * t];
+    }
+    c = pw_tree8(c);
+    for (int q = 8 * T; q < n; q++) c = c + scr[q];  // (lane 0's is the sum; the other lanes' are not read)
+    return readlane_d(c, 0);
+}
+
+// Two such sums at once, v1 and v2 over the same n lanes: the second sum's values are staged behind
+// the first's (scr: 2 n doubles) and its chains, tree and tail run in lanes 8..15 of the same
+// instructions.
+template <int NC>
+__device__ PCX_OUTLINE void wave_pw_sum2_lds(double v1, double v2, int nrt, double* scr, double& s1, double& s2) {
+    const int l = lane_id();
+    const int n = NC > 0 ? NC : nrt;
+    if (n < 8) {
+        double r1 = 0.0, r2 = 0.0;
+        for (int k = 0; k < n; k++) {
+            r1 += readlane_d(v1, k);
+            r2 += readlane_d(v2, k);
+        }
+        s1 = r1;
+        s2 = r2;
+        return;
+    }
+    wsync();
+    if (l < n) {
+        scr[l] = v1;
+        scr[n + l] = v2;
+    }
+    wsync();
+    const int T = n >> 3;
+    const double* const base = scr + ((l & 8) ? n : 0);
+    const double* const p = base + (l & 7);
+    double c = p[0];
+    if constexpr (NC > 0) {
+#pragma unroll
+        for (int t = 1; t < NC / 8; t++) c = c + p[8 * t];
+    } else {
+        for (int t = 1; t < T; t++) c = c + p[8 * t];
+    }
+    c = pw_tree8(c);
+    for (int q = 8 * T; q < n; q++) c = c + base[q];
+    s1 = readlane_d(c, 0);
+    s2 = readlane_d(c, 8);
+}
+
+// wave_pw_sum_prefix for 8 <= n < 24 (T = 1 or 2), registers only: lane k + 8 is row_shl:8 away from
+// lane k inside the first DPP row, so the chains are one addition (n >= 16) or none, pw_tree8 leaves
+// the tree's result on lane 0, and the tail (lanes 8 T .. n - 1) is read by readlane.  The same
+// additions in the same order.  Other lengths take wave_pw_sum_prefix.
+template <int NC>
+__device__ PCX_OUTLINE double wave_pw_sum_dpp(double v, int nrt) {
+    const int n = NC > 0 ? NC : nrt;
+    if (n < 8 || n >= 24) return wave_pw_sum_prefix<NC>(v, nrt);
+    const int T = n >> 3;
+    double c = v;
+    if (T == 2) c = v + shl_lane<8>(v);  // (wave-uniform)
+    c = pw_tree8(c);
+    double res = readlane_d(c, 0);
+    for (int q = 8 * T; q < n; q++) res += readlane_d(v, q);
+    return res;
+}
+
 // SPEC dot2 over rows i < N of column-strided data: a[i] * b[i*bs]
 __device__ __forceinline__ double dot2(const double* a, const double* b, int bs, int n) {
     double s = 0.0, c = 0.0;

@@ -94,9 +94,13 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
     const int64_t bo = a.bounds_shared ? 0 : PCX_ROUND_EV0;
     const bool has_bounds = a.scaled != nullptr;
     // numpy's pairwise sum over the reporters' / the events' lanes: both are prefixes of the wave
-    // (of compile-time length in a compiled shape), see wave_pw_sum_prefix
-    auto pw_rows = [&](double v) { return wave_pw_sum_prefix<NT>(v, N); };
-    auto pw_cols = [&](double v) { return wave_pw_sum_prefix<ET>(v, E); };
+    // (of compile-time length in a compiled shape).  The row sums stage their values in the head of
+    // the "M" region, N doubles (2 N for a pair), dead at every one of their sites (DESIGN.md 5.2,
+    // "Pairwise sums with the chains in lanes 0..7"): see wave_pw_sum_lds; the column sums of fewer
+    // than 24 events run in registers, see wave_pw_sum_dpp.
+    auto pw_rows = [&](double v) { return wave_pw_sum_lds<NT>(v, N, S.M); };
+    auto pw_rows2 = [&](double v1, double v2, double& s1, double& s2) { wave_pw_sum2_lds<NT>(v1, v2, N, S.M, s1, s2); };
+    auto pw_cols = [&](double v) { return wave_pw_sum_dpp<ET>(v, E); };
     constexpr int CR = live_rows(ET);  // 16-lane rows that hold events (a compiled shape's; else all four)
 
     // The output pointers are read from the kernel-argument segment where they are used (scalar
@@ -681,12 +685,12 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
         const double set1 = sc_i + fabs(mn);
         const double set2 = sc_i - mx;
         double a1 = fabs(set1), a2 = fabs(set2);
-        double S1 = pw_rows(a1);
+        double S1, S2;
+        pw_rows2(a1, a2, S1, S2);  // (both operands exist before either sum is needed; the re-sums are rare)
         if (S1 == 0) {
             a1 += 1.0;
             S1 = pw_rows(a1);
         }
-        double S2 = pw_rows(a2);
         if (S2 == 0) {
             a2 += 1.0;
             S2 = pw_rows(a2);
@@ -798,6 +802,52 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
         const bool wok = Mg < __builtin_inf() && !ballot(row && !(smooth_i >= 0.0 && smooth_i < mid - slack)) &&
                          ballot(row && smooth_i > 0.0) != 0;
         uint64_t slow = 0;  // the columns the test does not decide
+        // Compiled shapes with 3 E <= 64: every column's two sums in one pass, in the guesses' layout.
+        // Lane g * E + c adds, over column c's rows g, g + 3, g + 6, ... in ascending order,
+        // w [x < fill_c] and w [x == fill_c] (w = smooth_rep from LDS, fill_c read from the column's
+        // first missing row; the indicator is 1.0 or 0.0 and fma(w, 1, s) is s + w), keeps a "saw a NaN
+        // value" bit, and lane c takes (p0 + p1) + p2 by ds_bpermute.  The sums need accuracy only:
+        // any order of adding at most N non-negative terms stays within (N - 1) u of the exact sum,
+        // inside the (N + 6) u Wt the margin Mg allows, so mid, slack and Mg are the loop's.
+        constexpr bool FGSPLIT = NT > 0 && ET > 0 && 3 * ET <= W;
+        if constexpr (FGSPLIT) {
+            slow = scaled_mask;
+            if (wok) {  // (wave-uniform)
+                constexpr int TS = (NT + 2) / 3;
+                const int g = (l >= ET) + (l >= 2 * ET);
+                const bool live = l < 3 * ET;
+                const int c = live ? l - g * ET : 0;
+                const uint64_t mc = S.miss[c];
+                const int fm = mc ? __builtin_ctzll(mc) : 0;
+                const double gf = S.F[fm * ES + c];  // the fill (a column with no missing row: unused)
+                const double* const Fp = S.F + g * ES + c;
+                const double* const wp = S.smooth + g;
+                double below = 0.0, group = 0.0;
+                bool sawnan = false;
+#pragma unroll
+                for (int t = 0; t < TS; t++) {
+                    // (rows past the last: the loads lie in the round's own LDS and are switched off here)
+                    const bool in = 3 * t + 2 < NT || g + 3 * t < NT;
+                    const double x = Fp[3 * t * ES], w = in ? wp[3 * t] : 0.0;
+                    const double ib = in && x < gf ? 1.0 : 0.0, ig = in && x == gf ? 1.0 : 0.0;
+                    below = fma(w, ib, below);
+                    group = fma(w, ig, group);
+                    sawnan |= in && x != x;
+                }
+                const int l1 = (l + ET) & (W - 1), l2 = (l + 2 * ET) & (W - 1);
+                const double b1 = bpermute_d(l1, below), b2 = bpermute_d(l2, below);
+                const double g1 = bpermute_d(l1, group), g2 = bpermute_d(l2, group);
+                below = (below + b1) + b2;
+                group = (group + g1) + g2;
+                const uint64_t nm = ballot(live && sawnan);
+                const bool cnan = (((nm | (nm >> ET)) | (nm >> (2 * ET))) >> l) & 1;  // (read on lanes < E)
+                // (a NaN fill fails the second compare)
+                const bool decided = col && scj && mc != 0 && gf != 0.0 && fabs(gf) < 0x1p1023 && !cnan &&
+                                     below <= mid - Mg && below + group > mid + Mg;
+                if (decided) rawj = gf;
+                slow = scaled_mask & ~ballot(decided);
+            }
+        } else
         for (uint64_t todo = scaled_mask; todo; todo &= todo - 1) {  // (no LDS write, no wave barrier)
             const int j = __builtin_ctzll(todo);
             const double x0 = row ? S.F[l * ES + j] : 0.0;
