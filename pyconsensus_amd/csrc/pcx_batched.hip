@@ -20,6 +20,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "pcx_internal.h"
 
 namespace pcx {
@@ -82,10 +84,12 @@ __device__ __forceinline__ double bcast(double v, int src) {
 }
 
 // lane l <- lane l ^ S inside a 16-lane row, DPP only (VALU, no LDS-pipe round trip):
-// quad_perm (1, 2), row_shr:4 / row_shl:4 selected by lane bit 2 (4), row_ror:8 (8)
+// quad_perm (1, 2), row_shr:4 / row_shl:4 selected by lane bit 2 (4), row_ror:8 (8).
+// bound_ctrl: a lane whose source lies outside its row reads 0, which is what `old` = 0 gave it --
+// but with it the compiler need not write that 0 into the destination ahead of every DPP move.
 template <int CTRL>
 __device__ __forceinline__ uint32_t dpp32(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
 }
 template <int S>
 __device__ __forceinline__ uint32_t xor_lane32(uint32_t v) {
@@ -106,6 +110,14 @@ __device__ __forceinline__ double xor_lane(double v) {
     return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
 
+// lane l <- lane l + D of its 16-lane row (row_shl: the lanes past the row's end read +0.0)
+template <int D>
+__device__ __forceinline__ double shl_lane(double v) {
+    const uint64_t u = (uint64_t)__double_as_longlong(v);
+    const uint32_t lo = dpp32<0x100 + D>((uint32_t)u), hi = dpp32<0x100 + D>((uint32_t)(u >> 32));
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
 __device__ __forceinline__ double lane_value(double v, int k) {  // lane k's v (k wave-uniform)
     const uint64_t u = (uint64_t)__double_as_longlong(v);
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, k);
@@ -114,7 +126,10 @@ __device__ __forceinline__ double lane_value(double v, int k) {  // lane k's v (
 }
 
 // SPEC tree64: a butterfly inside each 16-lane row (xor 1, 2, 4, 8: every lane of a row
-// ends with the same row sum R_r), then (R0 + R1) + (R2 + R3) from lanes 0, 16, 32, 48
+// ends with the same row sum R_r), then (R0 + R1) + (R2 + R3) from lanes 0, 16, 32, 48.
+// Only those four lanes are read, so the xor-4 step is row_shl:4 alone: lane 0 needs lane 4's value
+// and lane 8, which lane 0 reads at the xor-8 step, lane 12's -- the additions that reach lane 0 and
+// their order are the butterfly's (pw_tree8 relies on the same).  wave_max does likewise.
 // ROWS < 4: the caller's lanes from 16 * ROWS on hold +0.0 and no row sum is -0.0 (squares, say),
 // so the dead rows' sums are +0.0 and adding them changes no bit: R0 + 0 = R0 unless R0 is -0.0.
 // The dead rows' readlanes and adds are left out.
@@ -123,7 +138,7 @@ __device__ __forceinline__ double tree_sum(double v) {
     static_assert(ROWS == 1 || ROWS == 2 || ROWS == 4, "live 16-lane rows");
     v = v + xor_lane<1>(v);
     v = v + xor_lane<2>(v);
-    v = v + xor_lane<4>(v);
+    v = v + shl_lane<4>(v);
     v = v + xor_lane<8>(v);
     if constexpr (ROWS == 1) return lane_value(v, 0);
     if constexpr (ROWS == 2) return lane_value(v, 0) + lane_value(v, 16);
@@ -137,8 +152,8 @@ constexpr int live_rows(int ET) { return ET > 0 ? (ET <= 16 ? 1 : ET <= 32 ? 2 :
 template <int D>
 __device__ __forceinline__ double shr_lane(double v) {  // lane l <- lane l - D of its row, else +0.0
     const uint64_t u = (uint64_t)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, 0x110 + D, 0xf, 0xf, false);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), 0x110 + D, 0xf, 0xf, false);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, 0x110 + D, 0xf, 0xf, true);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), 0x110 + D, 0xf, 0xf, true);
     return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
 __device__ __forceinline__ double wave_scan_d(double v) {
@@ -159,7 +174,7 @@ __device__ __forceinline__ double wave_max(double v) {
     static_assert(ROWS == 1 || ROWS == 2 || ROWS == 4, "live 16-lane rows");
     v = fmax(v, xor_lane<1>(v));
     v = fmax(v, xor_lane<2>(v));
-    v = fmax(v, xor_lane<4>(v));
+    v = fmax(v, shl_lane<4>(v));
     v = fmax(v, xor_lane<8>(v));
     if constexpr (ROWS == 1) return lane_value(v, 0);
     if constexpr (ROWS == 2) return fmax(lane_value(v, 0), lane_value(v, 16));
@@ -271,14 +286,6 @@ __device__ PCX_OUTLINE double wave_pw_sum_prefix(double v, int nrt) {
     double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
     for (int q = 8 * T; q < n; q++) res += readlane_d(a, (q & 7) * 8 + (q >> 3));
     return res;
-}
-
-// lane l <- lane l + D of its 16-lane row (row_shl: the lanes past the row's end read +0.0)
-template <int D>
-__device__ __forceinline__ double shl_lane(double v) {
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    const uint32_t lo = dpp32<0x100 + D>((uint32_t)u), hi = dpp32<0x100 + D>((uint32_t)(u >> 32));
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
 
 // numpy's fixed tree over eight accumulators r_k on lanes 8 q + k, k < 8, of a 16-lane row: lane 8 q
@@ -997,12 +1004,115 @@ __device__ Smem carve(double* base, int N, int E, int ES, int NR, bool pk) {
     return s;
 }
 
+// ---- broadcasts inside the 16-lane row, taken by the arithmetic instruction itself ------------
+// gfx950's v_fmac_f64 (VOP2) accepts a DPP source with row_newbcast:K: every lane reads lane K of
+// its own 16-lane row.  A column-phase vector v (v_k on lane k, E <= 32) is laid out for it once
+// by row_spread2 (rows 0 and 1) or row_spread4 (all four rows): lo holds v_(l & 15) and hi holds
+// v_(16 + (l & 15)), so column k is lane k & 15 of lo (k < 16) or of hi.  The compiler neither forms
+// these instructions nor sees the DPP read inside the statement, so two things are the caller's:
+//  (1) wait states: a VALU write of a register needs two wait states before a DPP read of it.  The
+//      registers read through DPP here are written by row_spread2 / row_spread4 alone and pass
+//      through dpp_ready() (s_nop 1, tied to them as operands) before any statement reads them.
+//  (2) EXEC: a source lane that EXEC has switched off is not read, so the statements run with the
+//      whole wave active: in wave-uniform control flow only (branches on ballots and scalars), never
+//      under `if (col)` or `if (row)`.
+struct RowSpread {
+    double lo, hi;
+};
+__device__ __forceinline__ double pack_d(uint32_t lo, uint32_t hi) {
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+__device__ __forceinline__ void dpp_ready(RowSpread& s) { asm("s_nop 1" : "+v"(s.lo), "+v"(s.hi)); }
+// v_permlane16_swap(u, u): the first result is rows [0, 0, 2, 2] of u, the second rows [1, 1, 3, 3]
+__device__ __forceinline__ RowSpread row_spread2(double v) {
+    const uint64_t u = (uint64_t)__double_as_longlong(v);
+    const auto a = __builtin_amdgcn_permlane16_swap((uint32_t)u, (uint32_t)u, false, false);
+    const auto b = __builtin_amdgcn_permlane16_swap((uint32_t)(u >> 32), (uint32_t)(u >> 32), false, false);
+    RowSpread s = {pack_d(a[0], b[0]), pack_d(a[1], b[1])};
+    dpp_ready(s);
+    return s;
+}
+// v_permlane32_swap(w, w): the first result is the lower half of w in both halves
+__device__ __forceinline__ RowSpread row_spread4(double v) {
+    const uint64_t u = (uint64_t)__double_as_longlong(v);
+    const auto a = __builtin_amdgcn_permlane16_swap((uint32_t)u, (uint32_t)u, false, false);
+    const auto b = __builtin_amdgcn_permlane16_swap((uint32_t)(u >> 32), (uint32_t)(u >> 32), false, false);
+    const uint32_t ll = __builtin_amdgcn_permlane32_swap(a[0], a[0], false, false)[0];
+    const uint32_t lh = __builtin_amdgcn_permlane32_swap(b[0], b[0], false, false)[0];
+    const uint32_t hl = __builtin_amdgcn_permlane32_swap(a[1], a[1], false, false)[0];
+    const uint32_t hh = __builtin_amdgcn_permlane32_swap(b[1], b[1], false, false)[0];
+    RowSpread s = {pack_d(ll, lh), pack_d(hl, hh)};
+    dpp_ready(s);
+    return s;
+}
+// acc = fma(s_K, m, acc), s_K from the row (one v_fmac_f64: the fused operation of fma(m, s_K, acc));
+// NEG: fma(-s_K, m, acc), the negation a source modifier (exact)
+template <int K, bool NEG = false>
+__device__ __forceinline__ void fmac_rowbcast(double& acc, const RowSpread& s, double m) {
+    static_assert(K >= 0 && K < 32, "a column of a two-row vector");
+    if constexpr (NEG)
+        asm("v_fmac_f64_dpp %0, -%1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
+            : "+v"(acc)
+            : "v"(K < 16 ? s.lo : s.hi), "v"(m), "n"(K & 15));
+    else
+        asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
+            : "+v"(acc)
+            : "v"(K < 16 ? s.lo : s.hi), "v"(m), "n"(K & 15));
+}
+// f - s_K as fma(-s_K, 1.0, f): the product is exact, so this is one rounding of f + (-s_K), the
+// subtraction's own operation on the same operands (signed zeros, infinities and a NaN s_K included).
+// Only v_fmac_f64 has a DPP form among the 64-bit instructions: v_add_f64 and v_mul_f64 are VOP3 and
+// take none.  `one` is 1.0 in a register (the instruction has no constant operand in this form).
+template <int K>
+__device__ __forceinline__ double sub_rowbcast(double f, const RowSpread& s, double one) {
+    fmac_rowbcast<K, true>(f, s, one);
+    return f;
+}
+template <int K, int ET, class F>
+__device__ __forceinline__ void static_cols(F&& f) {  // f(column constant) for K, K + 1, .. ET - 1
+    if constexpr (K < ET) {
+        f(std::integral_constant<int, K>());
+        static_cols<K + 1, ET>(f);
+    }
+}
+
+// Entry (r, K) of the packed triangle for a constant column K: at tri(r) + K for K <= r, at tri(K) + r
+// above the diagonal.  The LDS byte addresses of M[tri(r)] and M[r] are formed once per round
+// (sym_base, outside the step loop) and column K selects between them: one compare, one add and one
+// select, with 8 K left to the read's offset field.  From sym_at's expression the compiler forms
+// max(r, K), min(r, K) and a product for every column, eight instructions each; the empty asm keeps
+// it from seeing through the bases.
+typedef const __attribute__((address_space(3))) double* LdsDoubles;
+struct SymBase {
+    uint32_t tri, row;
+};
+__device__ __forceinline__ SymBase sym_base(const double* M, int r) {
+    const uint32_t m = (uint32_t)(uintptr_t)(LdsDoubles)M;
+    SymBase b = {m + (uint32_t)(r * (r + 1) / 2 * 8), m + (uint32_t)(r * 8)};
+    asm("" : "+v"(b.tri), "+v"(b.row));
+    return b;
+}
+template <bool PK, int K>
+__device__ __forceinline__ double sym_col(const double* M, const SymBase& b, int r, int ES) {
+    if constexpr (!PK) return M[r * ES + K];
+    const uint32_t at = K <= r ? b.tri : b.row + 8u * (K * (K + 1) / 2 - K);
+    return ((LdsDoubles)(uintptr_t)at)[K];
+}
+
 // y = normalize(M x) for lane j < E, x_k on lane k; returns y_j (0 on other lanes)
-template <bool PK, int ROWS = 4>
-__device__ PCX_OUTLINE double matvec_unit(const double* M, int ES, double xv, int E) {
-    const int l = lane_id(), r = l < E ? l : 0;  // (every lane runs the chain: readlane is wave-wide)
+// ET in 1..32 (a compiled shape): x is spread over rows 0 and 1 and each column's multiply-add takes
+// its x_k by row_newbcast; the lanes of rows 2 and 3 multiply by their own rows' x (0.0: no event
+// there) and are dropped like today's.  The sum's terms and their order are the loop's.
+template <bool PK, int ROWS = 4, int ET = 0>
+__device__ PCX_OUTLINE double matvec_unit(const double* M, int ES, double xv, int E, const SymBase& sb) {
+    const int l = lane_id(), r = l < E ? l : 0;  // (every lane runs the chain: the broadcasts are wave-wide)
     double acc = 0.0;
-    for (int k = 0; k < E; k++) acc = fma(M[sym_at<PK>(r, k, ES)], lane_value(xv, k), acc);
+    if constexpr (ET > 0 && ET <= 32) {
+        const RowSpread x = row_spread2(xv);
+        static_cols<0, ET>([&](auto k) { fmac_rowbcast<k.value>(acc, x, sym_col<PK, k.value>(M, sb, r, ES)); });
+    } else {
+        for (int k = 0; k < E; k++) acc = fma(M[sym_at<PK>(r, k, ES)], lane_value(xv, k), acc);
+    }
     const double y = l < E ? acc : 0.0;
     const double nrm = sqrt(tree_sum<ROWS>(l < E ? y * y : 0.0));  // squares: no row sum is -0.0
     return l < E ? y / nrm : 0.0;

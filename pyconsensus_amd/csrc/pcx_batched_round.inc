@@ -552,9 +552,10 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
             int sqn = 0;
             for (; sqn < PI_PRESQUARE; sqn++) square(false);
             if constexpr (PK) store_sym_ops<NS>(S.C, E, mreg);
+            const SymBase sb = sym_base(S.C, col ? l : 0);  // (the matrix-vector steps' row of the triangle)
             int it = 0, since = 0;
             for (;;) {
-                const double y = matvec_unit<PK, CR>(PK ? S.C : S.M, ES, xv, E);
+                const double y = matvec_unit<PK, CR, ET>(PK ? S.C : S.M, ES, xv, E, sb);
                 // SPEC: d = max over the events of |y - x|, stop when d <= PI_TOL.  Only the compare
                 // is used, and d <= PI_TOL holds exactly when no event lane has |y - x| > PI_TOL:
                 // the maximum (v_max_f64) drops a NaN operand and the lanes from E on feed 0.0, so a
@@ -578,7 +579,7 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
             }
             // the polish steps run on C itself
             if constexpr (PK) store_sym_ops<NS>(S.C, E, creg);
-            for (int p = 0; p < PI_POLISH; p++) xv = matvec_unit<PK, CR>(S.C, ES, xv, E);
+            for (int p = 0; p < PI_POLISH; p++) xv = matvec_unit<PK, CR, ET>(S.C, ES, xv, E, sb);
             // SPEC sign: first nonzero component negative; a unit vector e_k is +e_k
             const uint64_t nzm = ballot(col && xv != 0.0);
             if (nzm) {
@@ -598,7 +599,19 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
             // scores s = wcd . loading (:337), row phase (column j's mean and loading from lane j)
             const int r = row ? l : 0;
             double acc = 0.0;
-            for (int j = 0; j < E; j++) acc = fma(S.F[r * ES + j] - lane_value(muj, j), lane_value(ld_j, j), acc);
+            if constexpr (ET > 0 && ET <= 32) {
+                // the means and the loading spread once over all four rows, each column's subtraction
+                // and multiply-add taking its own by row_newbcast (pcx_batched.hip, "broadcasts inside
+                // the 16-lane row"); the whole wave runs this: `clus` and `alg` are launch constants
+                const RowSpread mu = row_spread4(muj), ld = row_spread4(ld_j);
+                double one = 1.0;  // (a register operand of the subtraction, settled like the spreads)
+                asm("s_nop 1" : "+v"(one));
+                static_cols<0, ET>([&](auto j) {
+                    fmac_rowbcast<j.value>(acc, ld, sub_rowbcast<j.value>(S.F[r * ES + j.value], mu, one));
+                });
+            } else {
+                for (int j = 0; j < E; j++) acc = fma(S.F[r * ES + j] - lane_value(muj, j), lane_value(ld_j, j), acc);
+            }
             if (row) sc_i = acc;
         } else if (flags & 2) {
             sc_i = __builtin_nan("");  // the reference's second svd raises (:375, :431)
