@@ -1075,6 +1075,16 @@ __device__ __forceinline__ void static_cols(F&& f) {  // f(column constant) for 
         static_cols<K + 1, ET>(f);
     }
 }
+// lane K of v <- the wave-uniform s (v_writelane_b32: a scalar source and a constant lane, so the one
+// wait the instruction can need, after a VALU write of a lane-select register, does not arise); the
+// other lanes keep v.  One instruction where `l == K ? s : v` is a move, a compare and a select.
+template <int K>
+__device__ __forceinline__ uint32_t write_lane(uint32_t v, uint32_t s) {
+    static_assert(K >= 0 && K < W, "a lane of the wave");
+    // (readfirstlane: the operand constraint alone does not keep a uniform value out of a vector register)
+    asm("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(__builtin_amdgcn_readfirstlane((int)s)), "n"(K));
+    return v;
+}
 
 // Entry (r, K) of the packed triangle for a constant column K: at tri(r) + K for K <= r, at tri(K) + r
 // above the diagonal.  The LDS byte addresses of M[tri(r)] and M[r] are formed once per round

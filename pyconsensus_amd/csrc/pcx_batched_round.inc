@@ -93,6 +93,12 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
     const bool row = l < N, col = l < E;
     const int64_t bo = a.bounds_shared ? 0 : PCX_ROUND_EV0;
     const bool has_bounds = a.scaled != nullptr;
+    // Whether the call gave reputations.  The compiled shapes read a flag formed here: testing the pointer
+    // at each site, with the rescale's row held in registers, the scalar allocator gave up the kernel's first
+    // eight-register argument load after the round's load and fetched it again for the test, and kept the
+    // 32-byte stack slot of the spill it had planned.  The other forms test the pointer where they did.
+    constexpr bool REPFLAG = NT > 0 && ET > 0;
+    const bool rep_flag = REPFLAG && a.reputation != nullptr;
     // numpy's pairwise sum over the reporters' / the events' lanes: both are prefixes of the wave
     // (of compile-time length in a compiled shape).  The row sums stage their values in the head of
     // the "M" region, N doubles (2 N for a pair), dead at every one of their sites (DESIGN.md 5.2,
@@ -124,7 +130,7 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
         loj = a.lo[bo + l];
         hij = a.hi[bo + l];
     }
-    double raw = row && a.reputation ? a.reputation[PCX_ROUND_ROW0 + l] : 0.0;
+    double raw = row && (REPFLAG ? rep_flag : a.reputation != nullptr) ? a.reputation[PCX_ROUND_ROW0 + l] : 0.0;
     if constexpr (NT > 0 && ET > 0 && (NT * ET) % 2 == 0) {
         // every 16-byte load of the round in flight at once, then the LDS scatter
         constexpr int TOT2 = NT * ET / 2, NV = (TOT2 + W - 1) / W;
@@ -152,7 +158,7 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
 
     // ---- a1: reputation (__init__.py:138-146) -----------------------------
     double rep;
-    if (a.reputation) {
+    if (REPFLAG ? rep_flag : a.reputation != nullptr) {
         const double tot = pw_rows(raw);
         rep = raw / tot;
     } else {
@@ -177,9 +183,58 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
     // Only a scaled column (a wave-uniform branch on scaled_mask) fetches its bounds and divides,
     // and the lanes past the last row hold 1.0, neither NaN nor zero, so the compares are the
     // ballots with no row mask applied.
-    double xnext = row ? S.F[l * ES] : 1.0;
     uint32_t nanb = 0, zerob = 0;
     int zcol = 0;  // column l's zero count (lanes < E)
+    constexpr bool ROWREG = NT > 0 && ET > 0;  // the compiled shapes: column loops over a register-held row
+    uint32_t missb = 0;                        // ROWREG: row l's missing columns (nanb | zerob), kept for the fill
+    uint32_t mjlo = 0, mjhi = 0;               // ROWREG: column l's missing rows, the two halves of miss[l]
+    if constexpr (ROWREG) {
+        // The row lane reads its whole row in one batch of 16-byte reads (the compiled pitch is even, so
+        // every row starts on 16 bytes) and the column loop runs from registers: no LDS read, no wait
+        // and no per-column address in it.  Column j's two scalars go to lane j by v_writelane_b32: its
+        // zero count, and the two halves of its missing mask, which lane j stores as miss[j] once after
+        // the loop and keeps as miss_j (lane 0 stored each from under its own EXEC pair, and the next
+        // column's wait on its load waited for that store too).
+        static_assert(compiled_es(ET) % 2 == 0, "16-byte row reads");
+        double xr[ET];
+#pragma unroll
+        for (int j = 0; j < ET; j++) xr[j] = 1.0;
+        if (row) {
+            const double2* const Fr = reinterpret_cast<const double2*>(S.F + l * ES);
+#pragma unroll
+            for (int q = 0; q < ET / 2; q++) {
+                const double2 v = Fr[q];
+                xr[2 * q] = v.x;
+                xr[2 * q + 1] = v.y;
+            }
+            if (ET & 1) xr[ET - 1] = S.F[l * ES + ET - 1];
+        }
+        static_cols<0, ET>([&](auto jc) {
+            constexpr int j = jc.value;
+            const bool sc = (scaled_mask >> j) & 1;
+            double x = xr[j];
+            if (sc) {  // wave-uniform
+                const double lo = bcast(loj, j), hi = bcast(hij, j);
+                if (row) {
+                    x = (x - lo) / (hi - lo);
+                    if (a.int_dtype) x = trunc(x);
+                    S.F[l * ES + j] = x;
+                }
+            }
+            const bool xn = __builtin_isnan(x), xz = x == 0.0;
+            nanb |= xn ? 1u << j : 0u;
+            zerob |= xz ? 1u << j : 0u;
+            const uint64_t zm = ballot(xz), mm = ballot(xn) | zm;
+            zcol = (int)write_lane<j>((uint32_t)zcol, (uint32_t)popc(zm));
+            mjlo = write_lane<j>(mjlo, (uint32_t)mm);
+            mjhi = write_lane<j>(mjhi, (uint32_t)(mm >> 32));
+            // (formed here, as below: a column's compare masks die with it)
+            asm volatile("" : "+v"(nanb), "+v"(zerob), "+v"(zcol), "+v"(mjlo), "+v"(mjhi));
+        });
+        missb = nanb | zerob;
+        if (col) S.miss[l] = ((uint64_t)mjhi << 32) | mjlo;
+    } else {
+    double xnext = row ? S.F[l * ES] : 1.0;
     // (the compiled shapes' loop unrolled: left rolled, as the compiler leaves it with the
     // scaled columns' branch inside, a column's load runs only one column ahead)
 #pragma unroll(ET > 0 ? ET : 1)
@@ -205,6 +260,7 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
         // the first use again and keeps every column's compare masks alive for them
         asm volatile("" : "+v"(nanb), "+v"(zerob), "+v"(zcol));
     }
+    }
     nacnt = (uint32_t)__popc(zerob) | ((uint32_t)__popc(nanb) << 8) | ((uint32_t)zcol << 16);
     wsync();
     // result["original"] (the rescaled reports), from LDS in row-major order: every store
@@ -214,7 +270,11 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
     STAMP(2);
     // ---- a3: interpolation guesses (:284-313), column phase ----------------
     uint64_t miss_j = 0;
-    if (col) miss_j = S.miss[l];
+    if constexpr (ROWREG) {
+        if (col) miss_j = ((uint64_t)mjhi << 32) | mjlo;  // (lane j took column j's mask in the rescale loop)
+    } else {
+        if (col) miss_j = S.miss[l];
+    }
     // every reputation >= 0 (a NaN fails): the condition of the row-split sums here and of the
     // prescreen below.  Equal reputations (reputation == nullptr) are 1 / N and pass.
     const bool nonneg = !ballot(row && !(rep >= 0.0));
@@ -335,7 +395,7 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
         // the prescreen's work, and the batch measured slower than with the sort alone (DESIGN.md 5.2).
         constexpr int NRS = NT > 0 ? NT : 64, KP = (NRS + 3) & ~3;
         const uint64_t all_j = todo;
-        if (todo && a.reputation && nonneg) {
+        if (todo && (REPFLAG ? rep_flag : a.reputation != nullptr) && nonneg) {
             uint32_t* const kx = reinterpret_cast<uint32_t*>(S.M);
             float* const wf = reinterpret_cast<float*>(S.M) + KP;
             if (l < KP) wf[l] = row ? (float)rep : 0.f;
@@ -409,6 +469,19 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
     wsync();
     STAMP(14);
     // fill (row phase; the next column's masks and fill loaded ahead of this column's store)
+    if constexpr (ROWREG) {
+        // the row's missing columns are the bits the lane collected in the rescale loop (bit l of
+        // miss[j] is bit j of nanb | zerob): the guesses in one batch of uniform reads, then the
+        // predicated stores with no read between them
+        if (row) {
+            double gs[ET];
+#pragma unroll
+            for (int j = 0; j < ET; j++) gs[j] = S.guess[j];
+#pragma unroll
+            for (int j = 0; j < ET; j++)
+                if ((missb >> j) & 1) S.F[l * ES + j] = gs[j];
+        }
+    } else
     if (row) {
         uint64_t mn = S.miss[0];
         double gn = S.guess[0];
@@ -916,6 +989,40 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
     double certj = 0.0;
     {
         uint64_t* hitm = reinterpret_cast<uint64_t*>(S.M);  // [E]; M is dead after the medians
+        const int NS = cert_stride(N, ES);  // odd stride: lane-per-column reads spread over the banks
+        double* comp = S.F;    // [E][NS]
+        uint64_t hm_l = 0;     // ROWREG: column l's hit mask (lanes < E)
+        if constexpr (ROWREG) {
+            // The row in one batch of reads, after which F is dead and the hit lists can go over it:
+            // column j's adjusted outcome comes from lane j's register (readlane), its hit mask stays
+            // in scalar registers for the scatter's store and goes to lane j by v_writelane_b32 for
+            // the sum below.  One loop, no LDS read and no wait in it, no mask in LDS.
+            double fr[ET];
+#pragma unroll
+            for (int j = 0; j < ET; j++) fr[j] = 0.0;
+            if (row) {
+                const double2* const Fr = reinterpret_cast<const double2*>(S.F + l * ES);
+#pragma unroll
+                for (int q = 0; q < ET / 2; q++) {
+                    const double2 v = Fr[q];
+                    fr[2 * q] = v.x;
+                    fr[2 * q + 1] = v.y;
+                }
+                if (ET & 1) fr[ET - 1] = S.F[l * ES + ET - 1];
+            }
+            wsync();
+            uint32_t hlo = 0, hhi = 0;
+            static_cols<0, ET>([&](auto jc) {
+                constexpr int j = jc.value;
+                const double av = bcast(adjj, j);
+                const uint64_t hm = ballot(row && fr[j] == av);
+                if ((hm >> l) & 1) comp[j * NS + mbcnt64(hm)] = smooth_i;
+                hlo = write_lane<j>(hlo, (uint32_t)hm);
+                hhi = write_lane<j>(hhi, (uint32_t)(hm >> 32));
+            });
+            hm_l = ((uint64_t)hhi << 32) | hlo;
+            wsync();
+        } else {
         double fn = row ? S.F[l * ES] : 0.0, an = S.adj[0];  // (next column's loads ahead of this column's store)
         for (int j = 0; j < E; j++) {
             const double f = fn, av = an;
@@ -927,16 +1034,15 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
             if (l == 0) hitm[j] = hm;
         }
         wsync();
-        const int NS = cert_stride(N, ES);  // odd stride: lane-per-column reads spread over the banks
-        double* comp = S.F;    // [E][NS]
         for (int j = 0; j < E; j++) {
             const uint64_t hm = hitm[j];
             if ((hm >> l) & 1) comp[j * NS + mbcnt64(hm)] = smooth_i;
         }
         wsync();
+        }
         if (col) {
             constexpr int TMAX = (NT > 0 ? NT : 64) / 8;
-            const uint64_t hm = hitm[l];
+            const uint64_t hm = ROWREG ? hm_l : hitm[l];
             const int n = popc(hm), T = n >> 3;
             const double* c = comp + l * NS;
             double res = 0.0;
