@@ -22,6 +22,7 @@
 
 #include <type_traits>
 
+#include "pcx_fastdiv.h"
 #include "pcx_internal.h"
 
 namespace pcx {
@@ -179,6 +180,27 @@ __device__ __forceinline__ double wave_max(double v) {
     if constexpr (ROWS == 1) return lane_value(v, 0);
     if constexpr (ROWS == 2) return fmax(lane_value(v, 0), lane_value(v, 16));
     return fmax(fmax(lane_value(v, 0), lane_value(v, 16)), fmax(lane_value(v, 32), lane_value(v, 48)));
+}
+
+// sqrt of a wave-uniform s (a tree_sum, a pairwise sum: the same value on every lane).  The library's
+// sqrt scales an argument below 2^-767 by 2^256 and its root back by 2^-128, and passes +-0 and +inf
+// through a class test: a compare, two v_ldexp_f64, the class test and three selects around the Newton
+// sequence, nine of its 21 instructions.  With 2^-767 <= s < inf (decided on the scalar unit from the
+// high word: a negative or NaN s fails the unsigned compare) the scale is zero, both ldexps are the
+// identity and the select passes the result through, so the sequence alone is the library's result
+// bit for bit: v_rsq_f64, g = s r, h = r / 2, one coupled step, two residual corrections, as in the
+// compiler's listing of sqrt for gfx950.  Every other s takes sqrt itself.
+__device__ __forceinline__ double sqrt_uniform(double s) {
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)__double_as_longlong(s) >> 32));
+    if (hi - 0x10000000u >= 0x7ff00000u - 0x10000000u) return sqrt(s);
+    const double r = __builtin_amdgcn_rsq(s);
+    double g = s * r, h = r * 0.5;
+    const double e = __builtin_fma(-h, g, 0.5);
+    g = __builtin_fma(g, e, g);
+    h = __builtin_fma(h, e, h);
+    g = __builtin_fma(__builtin_fma(-g, g, s), h, g);
+    g = __builtin_fma(__builtin_fma(-g, g, s), h, g);
+    return g;
 }
 
 __device__ __forceinline__ double catch_(double x, double tol) {  // __init__.py:251-258
@@ -1124,7 +1146,12 @@ __device__ PCX_OUTLINE double matvec_unit(const double* M, int ES, double xv, in
         for (int k = 0; k < E; k++) acc = fma(M[sym_at<PK>(r, k, ES)], lane_value(xv, k), acc);
     }
     const double y = l < E ? acc : 0.0;
-    const double nrm = sqrt(tree_sum<ROWS>(l < E ? y * y : 0.0));  // squares: no row sum is -0.0
+    const double ss = tree_sum<ROWS>(l < E ? y * y : 0.0);  // squares: no row sum is -0.0
+    double nrm;
+    if constexpr (ET > 0)  // (a compiled shape: the root without the library's range scaling)
+        nrm = sqrt_uniform(ss);
+    else
+        nrm = sqrt(ss);
     return l < E ? y / nrm : 0.0;
 }
 

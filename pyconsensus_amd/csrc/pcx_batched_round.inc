@@ -500,7 +500,12 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
 
     STAMP(3);
     // ---- old = rep . F (np.dot) -------------------------------------------
-    double oldj = col ? ob_vecmat(S.rep, S.F + l, ES, N, E, l) : 0.0;  // np.dot(rep, F) (:490)
+    // A compiled shape with 3 E <= 64 forms it in the nonconformity block, as the third vector of the
+    // n1 / n2 pass (F does not change in between), and only where it is read: not for alg == 1 or a
+    // clustering.
+    constexpr bool OLD3 = NT > 0 && ET > 0 && 3 * ET <= W;
+    double oldj = 0.0;
+    if constexpr (!OLD3) oldj = col ? ob_vecmat(S.rep, S.F + l, ES, N, E, l) : 0.0;  // np.dot(rep, F) (:490)
 
     double sc_i = 0.0, nc_i = 0.0, ld_j = 0.0;
     int branch = 5, flags = 0, iters = 0, comps = -1;
@@ -558,8 +563,18 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
                     }
                 }
             }
+            // The compiled shapes divide through one reciprocal of the wave-uniform denom per round (div_rn,
+            // pcx_fastdiv.h: four instructions for the division's eleven, the same bits).  An exact-zero
+            // accumulator (a column every reporter agrees on), denom == 0 and a non-finite denom take
+            // div_rn's guard, the division itself, behind a branch no lane of an ordinary round takes.
+            double yden = 0.0;
+            if constexpr (ROWREG) yden = range_rcp(denom);
             auto put = [&](int j, int k, double acc) {  // j >= k
-                const double c = acc / denom;
+                double c;
+                if constexpr (ROWREG)
+                    c = div_rn(acc, denom, yden);
+                else
+                    c = acc / denom;
                 S.C[sym_at<PK>(j, k, ES)] = c;
                 if (!PK) {
                     S.M[sym_at<PK>(j, k, ES)] = c;
@@ -601,7 +616,12 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
             const double dgmax = wave_max<CR>(dg);
             const int kd = __builtin_ctzll(ballot(col && dg == dgmax));
             double x0 = col ? S.C[sym_at<PK>(l, kd, ES)] : 0.0;
-            const double n0 = sqrt(tree_sum<CR>(x0 * x0));  // squares, +0.0 from lane E on: no row sum is -0.0
+            const double ss0 = tree_sum<CR>(x0 * x0);  // squares, +0.0 from lane E on: no row sum is -0.0
+            double n0;
+            if constexpr (ROWREG)
+                n0 = sqrt_uniform(ss0);
+            else
+                n0 = sqrt(ss0);
             xv = col ? x0 / n0 : 0.0;
             // packed: M starts as C's operands and is squared in registers (the covariance
             // accumulators cannot seed it: (d_j tok) d_k and (d_k tok) d_j round differently, and C
@@ -663,7 +683,12 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
             iters = it + PI_POLISH + sqn;
         }
         // loading = v / sqrt(sum(v**2)) with numpy's pairwise sum (:336)
-        const double nv = sqrt(pw_cols(xv * xv));
+        const double ssv = pw_cols(xv * xv);
+        double nv;
+        if constexpr (ROWREG)
+            nv = sqrt_uniform(ssv);
+        else
+            nv = sqrt(ssv);
         ld_j = col ? xv / nv : 0.0;
         wsync();
         if (clus) {
@@ -784,11 +809,32 @@ __global__ void __launch_bounds__(64, (NT > 0 && PK) ? PACKED_WAVES : 3) batched
         if (row) {
             S.n1[l] = a1 / S1;
             S.n2[l] = a2 / S2;
+            // OLD3: rep from the row lanes' registers into the smooth slot, dead from the scores until
+            // the reputation update stores smooth_rep (rep's own place went to the covariance)
+            if constexpr (OLD3) S.smooth[l] = rep;
         }
-        if (col) S.old[l] = oldj;
+        if constexpr (!OLD3) {
+            if (col) S.old[l] = oldj;
+        }
         wsync();
         double d1 = 0.0, d2 = 0.0;
-        {
+        if constexpr (OLD3) {
+            // three products in one pass over the rows: lane g E + j runs column j on n1, n2 or rep
+            // (g = 0, 1, 2), each lane ob_vecmat's own sequence on its vector, then d2 and old come
+            // down to lane j by ds_bpermute
+            const int g = (l >= ET) + (l >= 2 * ET);
+            const bool live = l < 3 * ET;
+            const int jc = live ? l - g * ET : 0;
+            double d = 0.0;
+            if (live) d = ob_vecmat(g == 0 ? S.n1 : g == 1 ? S.n2 : S.smooth, S.F + jc, ES, N, E, jc);
+            const double dn = bpermute_d((l + ET) & (W - 1), d), dr = bpermute_d((l + 2 * ET) & (W - 1), d);
+            if (col) {
+                d1 = d;
+                d2 = dn;
+                oldj = dr;
+                S.old[l] = oldj;
+            }
+        } else {
             // both products in one pass over the rows: lane j < E runs column j on n1, lane 32 + j
             // the same column on n2 (E <= 32) -- one instruction stream, each lane its own vector
             // and its column's own order (block, tail or ddot), then d2 moves down to lane j

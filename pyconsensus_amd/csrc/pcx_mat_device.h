@@ -10,6 +10,7 @@
 
 #include "../../include/pcx.h"
 #include "pcx_device.h"
+#include "pcx_fastdiv.h"
 #include "pcx_internal.h"
 #include "pcx_mat_layout.h"
 
@@ -32,28 +33,7 @@ struct ColParam {
     double rr;  // RN(1 / range); NaN when range lies outside [2^-100, 2^100] (quotients then divide)
 };
 
-// d / b correctly rounded from y = RN(1 / b) (Markstein: q0 = RN(d y) is faithful, the residual
-// d - b q0 is exact in one fma, and RN(q0 + r y) = RN(d / b)), in 4 fp64 ops where the IEEE
-// division sequence (div_scale x2, rcp, 5 fma, div_fmas, div_fixup) takes 11 with a quarter-rate
-// rcp.  The theorem assumes no underflow or overflow: with |b| in [2^-100, 2^100] (else y is
-// NaN) and |q0| in [2^-860, 2^1000], |d| >= 2^-960 keeps the residual exact and q finite.  Other
-// cells -- zeros among them, whose sign the fast path can get wrong (-0 / b) -- divide (a branch,
-// skipped when no lane needs it).  NaN d passes: the fast path returns NaN as the division does.
-// tests/test_fastdiv.py checks the sequence and its guard against the division bit for bit.
-__device__ __forceinline__ double div_rn(double d, double b, double y) {
-    const double q0 = d * y;
-    const double r = __builtin_fma(-q0, b, d);
-    double q = __builtin_fma(r, y, q0);
-    const bool slow = __builtin_isnan(y) | (fabs(q0) < 0x1p-860) | (fabs(q0) > 0x1p1000);
-    if (__builtin_expect(slow, 0)) q = d / b;
-    return q;
-}
-
-__device__ __forceinline__ double range_rcp(double range) {
-    const double a = fabs(range);
-    return (a >= 0x1p-100 && a <= 0x1p100) ? 1.0 / range : __builtin_nan("");
-}
-
+// (div_rn and range_rcp, the rescale's division through the range's reciprocal: pcx_fastdiv.h)
 __device__ __forceinline__ double rescale(double r, const ColParam& p, int int_dtype) {
     if (!p.scaled) return r;
     double x = div_rn(r - p.lo, p.range, p.rr);
