@@ -81,6 +81,8 @@ int      pcx_synchronize(pcx_ctx* ctx);
 /* other shape (E <= 65536) or code-book size: each round is one single-matrix   */
 /* consensus, a pool of worker streams keeps many in flight (PCX_ROUND_WORKERS,  */
 /* default 16); synchronous.  pcx_batched_route tells which of the three.        */
+/* pcx_consensus_batched_tall_f64 (below) moves rounds of up to 1024 x 64 from   */
+/* the last regime to a workgroup per round; this entry's routes do not change.  */
 /* ------------------------------------------------------------------------ */
 typedef struct {
     int64_t n_rounds;             /* B                                           */
@@ -156,6 +158,19 @@ typedef struct {
 } pcx_batch_result;
 
 int pcx_consensus_batched_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_result* out);
+
+/* Tall rounds (added under ABI 9; detect by symbol): pcx_consensus_batched_f64's
+ * arguments and refusals, with rounds of 256 < N <= 1024 reporters and E <= 64 events on the
+ * workgroup-per-round kernel's tall form -- one workgroup per round, ONE asynchronous launch, every
+ * output bit-identical to the batched SPEC (oracle/pcx_oracle_batched.c) built with NMAX = 1024.
+ * Algorithms: PCA, absolute, big-five, fixed-variance, cokurtosis.  The kernel carves its LDS by a plan
+ * per shape; a shape whose plan does not fit the 160 KiB of a workgroup (big-five and fixed-variance
+ * with many reporters AND many events), the clusterings, N > 1024 and E > 64 run exactly as
+ * pcx_consensus_batched_f64 runs them: same route, same bytes, and so does every shape up to 256 x 64.
+ * pcx_tall_route tells which.  Opt-in because the scheduler's results above 256 reporters are the
+ * single-matrix path's arithmetic, not the SPEC's bits: the two routes agree within tolerance, not bit
+ * for bit.  Calls share the context's workgroup scratch: keep them on one stream. */
+int pcx_consensus_batched_tall_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_result* out);
 
 /* ------------------------------------------------------------------------ */
 /* Ragged batches (added under ABI 9; detect by symbol): B rounds of DIFFERENT  */
@@ -796,8 +811,23 @@ int64_t pcx_medium_lds_bytes(int n_reporters, int n_events, int algorithm);
  * written).  kmeans_k matters for PCX_ALG_KMEANS only.  -1: arguments that call would refuse.  A
  * pure function of its arguments -- no context, no device, and the PCX_NO_MEDIUM diagnostic override
  * is not consulted; pcx_consensus_batched_f64 decides with the same code. */
-enum pcx_route { PCX_ROUTE_WAVE = 0, PCX_ROUTE_WORKGROUP = 1, PCX_ROUTE_SCHEDULER = 2 };
+enum pcx_route { PCX_ROUTE_WAVE = 0, PCX_ROUTE_WORKGROUP = 1, PCX_ROUTE_SCHEDULER = 2, PCX_ROUTE_TALL = 3 };
 int pcx_batched_route(int n_reporters, int n_events, int algorithm, int kmeans_k);
+
+/* The tall entry's routes (added under ABI 9; detect by symbol).  pcx_tall_route: where
+ * pcx_consensus_batched_tall_f64 runs a batch -- pcx_batched_route's value, except PCX_ROUTE_TALL (3)
+ * for 256 < n_reporters <= 1024, n_events <= 64 and an algorithm and shape whose LDS plan fits.  Pure,
+ * like pcx_batched_route.  pcx_tall_lds_bytes: the dynamic LDS of one such round, at most 160 KiB less
+ * the kernel's static LDS; 0 where the route is not PCX_ROUTE_TALL.  pcx_tall_plan: the plan itself,
+ * out = {waves that run weighted medians and certainties side by side (4, 2 or 1), reporter rows per
+ * chunk of np.dot's four-row block partials, the number of such chunks (the last may be shorter; 1
+ * for n_events == 1), threads per workgroup}; PCX_EINVAL (out zeroed) where the route is not
+ * PCX_ROUTE_TALL.  The dynamic LDS is 8 * (max(E (E + 1) [twice for big-five and fixed-variance],
+ * waves * (2 N + 5 P / 2) [P = the power of two >= N], rows / 4 * E4 + (E - E4) * N [E4 = E & ~3; 0 for
+ * E == 1]) + 11 N + 22 E) + 4 * ((N E + 15) >> 4) + 16 bytes. */
+int pcx_tall_route(int n_reporters, int n_events, int algorithm, int kmeans_k);
+int64_t pcx_tall_lds_bytes(int n_reporters, int n_events, int algorithm);
+int pcx_tall_plan(int n_reporters, int n_events, int algorithm, int32_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -119,6 +119,10 @@ def _declare(lib):
         ("pcx_sim_study_kmeans_check", i32, [C.POINTER(_abi.SimSweep), vp, vp, C.c_int32, C.POINTER(i64)]),
         ("pcx_simulate_study_kmeans_f64", i32, [vp, C.POINTER(_abi.SimSweep), vp, vp, C.c_int32,
                                                 C.POINTER(_abi.SimResult), C.POINTER(_abi.SimStudyResult)]),
+        ("pcx_consensus_batched_tall_f64", i32, [vp, C.POINTER(_abi.Batch), C.POINTER(_abi.BatchResult)]),
+        ("pcx_tall_route", i32, [i32, i32, i32, i32]),
+        ("pcx_tall_lds_bytes", i64, [i32, i32, i32]),
+        ("pcx_tall_plan", i32, [i32, i32, i32, C.POINTER(C.c_int32)]),
     ]:
         if (name in ("pcx_batched_lds_bytes", "pcx_medium_lds_bytes", "pcx_batched_route", "pcx_ragged_plan",
                      "pcx_consensus_ragged_f64", "pcx_ragged_plan_wide", "pcx_consensus_ragged_wide_f64",
@@ -131,7 +135,8 @@ def _declare(lib):
                      "pcx_simulate_study_params_f64", "pcx_kmeans_plan", "pcx_ragged_plan_kmeans",
                      "pcx_consensus_ragged_kmeans_f64", "pcx_sim_kmeans_books_host", "pcx_sim_kmeans_books_f64",
                      "pcx_sim_sweep_kmeans_books_host", "pcx_sim_sweep_kmeans_books_f64", "pcx_simulate_kmeans_f64",
-                     "pcx_sim_study_kmeans_check", "pcx_simulate_study_kmeans_f64")
+                     "pcx_sim_study_kmeans_check", "pcx_simulate_study_kmeans_f64",
+                     "pcx_consensus_batched_tall_f64", "pcx_tall_route", "pcx_tall_lds_bytes", "pcx_tall_plan")
                 and os.environ.get("PCX_LIB") and not hasattr(lib, name)):
             continue  # an A/B build of a revision before these queries (tools/ab_build.sh)
         f = getattr(lib, name)

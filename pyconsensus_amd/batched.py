@@ -8,6 +8,8 @@ Rounds of at most 64 reporters x 32 events run in one wavefront each of
 ``medium_round_kernel`` (csrc/pcx_medium.hip), every algorithm (k-means with up to 16 codes);
 larger rounds run as single-matrix consensuses, many in flight on a pool of worker streams
 (csrc/pcx_rounds.cpp).  :func:`route` tells which of the three a shape takes.
+With ``tall=True`` rounds of 257 to 1024 reporters and at most 64 events run in one workgroup each of
+``tall_round_kernel`` (csrc/pcx_tall.hip) instead: one asynchronous launch, the SPEC's bits.
 Rounds of DIFFERENT shapes (each at most 64 x 32) run in one launch of the one-wave kernel through
 :func:`consensus_ragged`; with ``wide=True`` rounds up to 256 x 64 join them, on the ragged form of
 the workgroup kernel.
@@ -24,6 +26,7 @@ MAX_REPORTERS = 64  # one wavefront per round up to here (and MAX_EVENTS)
 MAX_EVENTS = 32
 WIDE_MAX_REPORTERS = 256  # one workgroup per round up to here (and WIDE_MAX_EVENTS)
 WIDE_MAX_EVENTS = 64
+TALL_MAX_REPORTERS = 1024  # one workgroup per round up to here with tall=True (and WIDE_MAX_EVENTS)
 
 
 def kmeans_k(N):
@@ -83,23 +86,43 @@ def kmeans_plan(shapes, restarts=_abi.KMEANS_RESTARTS, k=None):
     return offsets
 
 
-ROUTES = ("wave", "workgroup", "scheduler")  # include/pcx.h enum pcx_route
+ROUTES = ("wave", "workgroup", "scheduler", "tall")  # include/pcx.h enum pcx_route
 
 
-def route(N, E, algorithm="PCA", kmeans_k=None):
+def route(N, E, algorithm="PCA", kmeans_k=None, tall=False):
     """Where ``consensus_batched`` runs rounds of N x E: ``"wave"`` (one wavefront per round, up to
     64 x 32) and ``"workgroup"`` (one workgroup per round, up to 256 x 64; k-means with at most 16
     codes) are ONE asynchronous kernel launch; ``"scheduler"`` is the host-driven round scheduler,
     which returns once every output is written.  ``kmeans_k`` defaults to :func:`kmeans_k` (N).
+    ``tall=True``: where ``consensus_batched(..., tall=True)`` runs them (pcx_tall_route) -- ``"tall"``
+    (one workgroup per round of ``tall_round_kernel``, ONE asynchronous launch) for 256 < N <= 1024,
+    E <= 64 and "PCA", "absolute", "big-five", "fixed-variance" or "cokurtosis" where the round's LDS
+    plan fits a workgroup (:func:`tall_plan`); every other shape and algorithm as without it.
     Needs no GPU; raises ValueError for arguments ``consensus_batched`` refuses."""
     alg = _abi.ALGORITHMS.get(algorithm)
     if alg is None:
         raise NotImplementedError("algorithm %r is not on the GPU path" % (algorithm,))
     k = kmeans_k_default(N) if kmeans_k is None else int(kmeans_k)
-    r = _lib.lib().pcx_batched_route(int(N), int(E), alg, k)
+    query = _lib.lib().pcx_tall_route if tall else _lib.lib().pcx_batched_route
+    r = query(int(N), int(E), alg, k)
     if r < 0:
         raise ValueError("no batched route for %d x %d rounds, algorithm %r, kmeans_k %d" % (N, E, algorithm, k))
     return ROUTES[r]
+
+
+def tall_plan(N, E, algorithm="PCA"):
+    """The LDS plan of one tall N x E round (pcx_tall_plan, pcx_tall_lds_bytes), or None where
+    ``route(..., tall=True)`` is not ``"tall"``: a dict of ``waves`` (weighted medians and certainties
+    that run side by side: 4, 2 or 1), ``dot_rows`` (reporter rows per chunk of np.dot's block
+    partials), ``dot_chunks``, ``threads`` and ``lds_bytes`` (the launch's dynamic LDS).  Needs no GPU."""
+    alg = _abi.ALGORITHMS.get(algorithm)
+    if alg is None:
+        raise NotImplementedError("algorithm %r is not on the GPU path" % (algorithm,))
+    out = (C.c_int32 * 4)()
+    if _lib.lib().pcx_tall_plan(int(N), int(E), alg, out) != 0:
+        return None
+    return dict(waves=int(out[0]), dot_rows=int(out[1]), dot_chunks=int(out[2]), threads=int(out[3]),
+                lds_bytes=int(_lib.lib().pcx_tall_lds_bytes(int(N), int(E), alg)))
 
 
 def clusterfeck_threshold(E):
@@ -112,7 +135,8 @@ def consensus_batched(reports, reputation=None, scaled=None, lo=None, hi=None,
                       catch_tolerance=0.1, alpha=0.1, int_dtype=False, algorithm="PCA",
                       outputs=None, device=None, filled=False, original=False,
                       max_components=5, variance_threshold=0.9, aux_scores=None,
-                      hierarchy_threshold=0.5, kmeans_init=None, cluster_threshold=None, packed=False):
+                      hierarchy_threshold=0.5, kmeans_init=None, cluster_threshold=None, packed=False,
+                      tall=False):
     """Run B rounds of N x E reports on the GPU.
 
     reports:    (B, N, E) float64, NaN = missing (0.0 is missing too, as in the reference)
@@ -129,6 +153,13 @@ def consensus_batched(reports, reputation=None, scaled=None, lo=None, hi=None,
     packed:     numpy inputs travel to the device in ONE copy and every output is a view of ONE
                 device buffer (``out["_packed"]``; :func:`unpack_round` brings it back in one
                 copy) -- the drop-in's per-call path, where each separate small copy costs ~10 us
+    tall:       True: rounds of 257 to 1024 reporters and at most 64 events run one workgroup each
+                on ``tall_round_kernel`` (pcx_consensus_batched_tall_f64) where
+                ``route(N, E, algorithm, tall=True)`` says ``"tall"``: ONE asynchronous launch, every
+                output bit-identical to the C SPEC built for 1024 reporters.  Every other shape and
+                algorithm runs exactly as without it.  Opt-in, because above 256 reporters the round
+                scheduler gives the single-matrix path's arithmetic and the tall route the SPEC's:
+                the two agree within tolerance, not bit for bit
 
     Returns a dict of torch tensors on the device, named like the ABI fields
     (``smooth_rep``, ``outcomes_final``, ...).  Three regimes (:func:`route`):
@@ -137,7 +168,8 @@ def consensus_batched(reports, reputation=None, scaled=None, lo=None, hi=None,
     reference's own ceil(sqrt(N)) up to there; kmeans_init is read on the device) are ONE kernel
     launch, asynchronous on torch's current stream -- synchronise before reading the outputs on
     the host; the round scheduler (rounds above 256 x 64, k-means with larger code books) returns
-    only once every output is written.
+    only once every output is written.  ``tall=True`` moves rounds up to 1024 x 64 from the scheduler
+    to a fourth regime of that kind: one launch, asynchronous.
     """
     t = _device.require_gpu()
     dev = t.device(device) if device is not None else t.device("cuda", t.cuda.current_device())
@@ -218,7 +250,8 @@ def consensus_batched(reports, reputation=None, scaled=None, lo=None, hi=None,
             outs[name] = x
             setattr(res, name, x.data_ptr())
     h = _lib.bind_stream(dev.index, _device.current_stream_handle(dev))
-    _lib.check(_lib.lib().pcx_consensus_batched_f64(h, C.byref(inp), C.byref(res)))
+    entry = _lib.lib().pcx_consensus_batched_tall_f64 if tall else _lib.lib().pcx_consensus_batched_f64
+    _lib.check(entry(h, C.byref(inp), C.byref(res)))
     outs["_inputs"] = (R, rep, sc, lo_, hi_, aux, kinit)  # keep inputs alive until the caller syncs
     return outs
 

@@ -306,6 +306,32 @@ int pcx_batched_route(int n_reporters, int n_events, int algorithm, int kmeans_k
     return batched_route(n_reporters, n_events, algorithm, kmeans_k);
 }
 
+// batched_route with the tall route: tall where the scheduler would run a round of 257..1024
+// reporters that the tall kernel's LDS plan fits (pcx_tall_route and the tall entry itself)
+static int tall_route(int64_t N, int64_t E, int alg, int k) {
+    const int r = batched_route(N, E, alg, k);
+    if (r != PCX_ROUTE_SCHEDULER || N <= 256 || N > 1024 || E > 64) return r;
+    return pcx::tall_lds_bytes((int)N, (int)E, alg) ? PCX_ROUTE_TALL : r;
+}
+
+int pcx_tall_route(int n_reporters, int n_events, int algorithm, int kmeans_k) {
+    return tall_route(n_reporters, n_events, algorithm, kmeans_k);
+}
+
+int64_t pcx_tall_lds_bytes(int n_reporters, int n_events, int algorithm) {
+    if (tall_route(n_reporters, n_events, algorithm, 1) != PCX_ROUTE_TALL) return 0;
+    return (int64_t)pcx::tall_lds_bytes(n_reporters, n_events, algorithm);
+}
+
+int pcx_tall_plan(int n_reporters, int n_events, int algorithm, int32_t out[4]) {
+    if (!out) return fail(PCX_EINVAL, "pcx_tall_plan: null argument");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (tall_route(n_reporters, n_events, algorithm, 1) != PCX_ROUTE_TALL)
+        return fail(PCX_EINVAL, "pcx_tall_plan: not a shape and algorithm of the tall route");
+    pcx::tall_plan_query(n_reporters, n_events, algorithm, out);
+    return PCX_OK;
+}
+
 // PCX_STAMPS, one-wave kernel: h = the stamps read back, [B][32]
 static void print_wave_stamps(const std::vector<long long>& h, int64_t B) {
     // stamp ids in program order (pcx_batched.hip STAMP(k)); a phase is named by its closing stamp
@@ -377,7 +403,7 @@ static void print_medium_stamps(const std::vector<long long>& h, int64_t B) {
     fprintf(stderr, " pi: presq:%.0f steps:%.0f\n", pw[0] / (double)B, pw[1] / (double)B);
 }
 
-static int run_workgroup_route(pcx_ctx* ctx, pcx::BatchArgs& a) {
+static int run_workgroup_route(pcx_ctx* ctx, pcx::BatchArgs& a, bool tall = false) {
     const int64_t chunk = pcx::medium_chunk(a, MEDIUM_SCRATCH_CAP);
     if (const int rc = medium_scratch_reserve(ctx, pcx::medium_scratch_per_round(a) * (size_t)chunk)) return rc;
     hipError_t e = hipSuccess;
@@ -386,13 +412,18 @@ static int run_workgroup_route(pcx_ctx* ctx, pcx::BatchArgs& a) {
     double* Xscr = Cscr + (size_t)chunk * a.E * a.E;  // the clusterings' cluster sums / observations
     stamps_begin(a, ctx->stream);
     for (int64_t b0 = 0; b0 < a.B && e == hipSuccess; b0 += chunk)
-        e = pcx::launch_medium(a, b0, std::min<int64_t>(chunk, a.B - b0), Fscr, Cscr, Xscr, ctx->stream);
+        e = tall ? pcx::launch_tall(a, b0, std::min<int64_t>(chunk, a.B - b0), Fscr, Cscr, ctx->stream)
+                 : pcx::launch_medium(a, b0, std::min<int64_t>(chunk, a.B - b0), Fscr, Cscr, Xscr, ctx->stream);
     if (a.stamps) print_medium_stamps(stamps_end(a, ctx->stream), a.B);
-    return e == hipSuccess ? PCX_OK : hip_fail(e, "medium_round_kernel launch");
+    return e == hipSuccess ? PCX_OK : hip_fail(e, tall ? "tall_round_kernel launch" : "medium_round_kernel launch");
 }
 
-int pcx_consensus_batched_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_result* out) {
-    if (!ctx || !in || !out) return fail(PCX_EINVAL, "pcx_consensus_batched_f64: null argument");
+// pcx_consensus_batched_f64, and with `tall` pcx_consensus_batched_tall_f64: the same checks and
+// routes, the tall route's shapes on tall_round_kernel instead of the scheduler
+static int consensus_batched(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_result* out, bool tall) {
+    if (!ctx || !in || !out)
+        return fail(PCX_EINVAL, tall ? "pcx_consensus_batched_tall_f64: null argument"
+                                     : "pcx_consensus_batched_f64: null argument");
     if (in->n_rounds < 0 || in->n_rounds > 0x7fffffff)
         return fail(PCX_EINVAL, "batched: n_rounds must be in [0, 2^31)");
     if (in->n_reporters < 1 || in->n_reporters > 0x7fffffff)
@@ -423,6 +454,8 @@ int pcx_consensus_batched_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_resul
     const int route = batched_route(in->n_reporters, in->n_events, in->algorithm, in->kmeans_k);
     if (route < 0) return fail(PCX_EINVAL, "batched: invalid shape or algorithm");  // (refused above)
     if (route == PCX_ROUTE_WORKGROUP && !getenv("PCX_NO_MEDIUM")) return run_workgroup_route(ctx, a);
+    if (tall && tall_route(in->n_reporters, in->n_events, in->algorithm, in->kmeans_k) == PCX_ROUTE_TALL)
+        return run_workgroup_route(ctx, a, true);
     if (route != PCX_ROUTE_WAVE) {
         // one single-matrix consensus per round, many rounds in flight (pcx_rounds.cpp)
         std::string err;
@@ -433,6 +466,14 @@ int pcx_consensus_batched_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_resul
     e = pcx::launch_batched(a, ctx->stream);
     if (a.stamps) print_wave_stamps(stamps_end(a, ctx->stream), a.B);
     return e == hipSuccess ? PCX_OK : hip_fail(e, "batched_round_kernel launch");
+}
+
+int pcx_consensus_batched_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_result* out) {
+    return consensus_batched(ctx, in, out, false);
+}
+
+int pcx_consensus_batched_tall_f64(pcx_ctx* ctx, const pcx_batch* in, pcx_batch_result* out) {
+    return consensus_batched(ctx, in, out, true);
 }
 
 namespace {

@@ -234,6 +234,13 @@ size_t medium_scratch_per_round(const BatchArgs& a);
 int64_t medium_chunk(const BatchArgs& a, size_t scratch_bytes);
 hipError_t launch_medium(const BatchArgs& a, int64_t b0, int64_t nb, double* Fscr, double* Cscr, double* Xscr,
                          hipStream_t st);
+// tall rounds (256 < N <= 1024, E <= 64; PCA, absolute, big-five, fixed-variance, cokurtosis): one
+// workgroup each of tall_round_kernel (pcx_tall.hip), its LDS by a plan per shape.  plan: {median
+// waves, rows per np.dot chunk, np.dot chunks, threads}; false / 0 where the shape does not fit.
+// The scratch is launch_medium's (medium_scratch_per_round, medium_chunk; no clustering scratch).
+bool tall_plan_query(int N, int E, int algorithm, int32_t plan[4]);
+size_t tall_lds_bytes(int N, int E, int algorithm);
+hipError_t launch_tall(const BatchArgs& a, int64_t b0, int64_t nb, double* Fscr, double* Cscr, hipStream_t st);
 
 // One round of a ragged launch of the workgroup-per-round kernel (pcx_consensus_ragged_wide_f64):
 // RaggedDesc's offsets and shape, and the round's index in the caller's [B] outputs -- a launch

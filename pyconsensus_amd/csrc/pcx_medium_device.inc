@@ -2,9 +2,23 @@
 // weighted median, the Jacobi component scores, the clusterings, the LDS carve sizes), included inside
 // namespace pcx { namespace { by pcx_medium.hip (medium_round_kernel) and by pcx_medium_ragged.hip
 // (ragged_medium_kernel): two translation units, so the equal-shape kernels keep the code object
-// they had before the ragged form existed.
+// they had before the ragged form existed.  pcx_tall.hip includes it under PCX_MEDIUM_TALL 1 for rounds
+// of up to 1024 reporters: where a comment below says n <= 256, the text under that macro lifts it
+// (mpw, the NaN rank path of wv_wmedian, bvecmat_chunked, tall_plan); without the macro nothing changes.
+#ifndef PCX_MEDIUM_TALL
+#define PCX_MEDIUM_TALL 0  // 1: pcx_tall.hip (tall_round_kernel, rounds of up to 1024 reporters; DESIGN.md 5.3.1)
+#endif
+#if PCX_MEDIUM_TALL
+#ifndef PCX_TALL_THREADS  // 256, 512 and 1024 were measured (DESIGN.md 5.3.1): 512 is fastest, and at 1024
+#define PCX_TALL_THREADS 512  // the static LDS (sh[MT]) no longer leaves a 1024 x 64 round its one median wave
+#endif
+constexpr int MT = PCX_TALL_THREADS;  // threads per round (a build constant of the tall unit)
+constexpr int MN = 1024;              // max reporters
+static_assert(MT >= 256 && MT <= 1024 && MT % 64 == 0, "the round text owns tiles and columns by tid < 256");
+#else
 constexpr int MT = 256;  // threads per round
 constexpr int MN = 256;  // max reporters
+#endif
 constexpr int MEV = 64;  // max events
 constexpr double M_PI_TOL = 1e-14;
 constexpr int M_PI_MAXIT = 256, M_PI_PRESQUARE = 3, M_PI_SQUARE_EVERY = 32, M_PI_MAX_SQUARINGS = 8,
@@ -37,6 +51,43 @@ __device__ double mpw_sub(G g, int off, int n) {  // n <= 256: the right half ma
     n2 -= n2 % 8;
     return mpw_leaf(g, off, n2) + mpw_leaf(g, off + n2, n - n2);
 }
+#if PCX_MEDIUM_TALL
+// n <= 1024: the same recursion (pw_sum(left) + pw_sum(right)) to any depth, without recursion: the
+// leaves in index order, each with its depth; two finished values of one depth are siblings and add
+// into their parent.  At most five segments and five values are pending (n = 1023 splits four times:
+// 519, 263, 135 on the right), packed off | n << 11 | depth << 22.
+template <class G>
+__device__ double mpw(G g, int n) {
+    if (n <= 128) return mpw_leaf(g, 0, n);
+    uint32_t seg[6];
+    double val[6];
+    uint32_t vdep = 0;  // the pending values' depths, four bits each
+    int sp = 1, vp = 0;
+    seg[0] = (uint32_t)n << 11;
+    while (sp) {
+        const uint32_t s = seg[--sp];
+        const int off = s & 2047, m = (s >> 11) & 2047;
+        int d = (int)(s >> 22);
+        if (m > 128) {
+            int h = m / 2;
+            h -= h % 8;
+            seg[sp++] = (uint32_t)(off + h) | (uint32_t)(m - h) << 11 | (uint32_t)(d + 1) << 22;
+            seg[sp++] = (uint32_t)off | (uint32_t)h << 11 | (uint32_t)(d + 1) << 22;
+            continue;
+        }
+        double v = mpw_leaf(g, off, m);
+        while (vp && (int)((vdep >> (4 * (vp - 1))) & 15u) == d) {
+            vp--;
+            v = val[vp] + v;
+            d--;
+        }
+        val[vp] = v;
+        vdep = (vdep & ~(15u << (4 * vp))) | (uint32_t)d << (4 * vp);
+        vp++;
+    }
+    return val[0];
+}
+#else
 template <class G>
 __device__ double mpw(G g, int n) {
     if (n <= 128) return mpw_leaf(g, 0, n);
@@ -44,6 +95,7 @@ __device__ double mpw(G g, int n) {
     n2 -= n2 % 8;
     return mpw_leaf(g, 0, n2) + mpw_sub(g, n2, n - n2);
 }
+#endif
 
 // the same tree64 on wave 0 (lane = slot): the xor butterfly by shuffles; valid on lane 0
 template <class G>
@@ -171,6 +223,68 @@ __device__ __forceinline__ double mcatch(double x, double tol) {
     if (x > 1.5 + tol) return 2.0;
     return 1.5;
 }
+
+#if PCX_MEDIUM_TALL
+// tall rounds: the block partials in chunks of `nbc` four-row blocks (the plan's: tb holds nbc x E4
+// partials, then the staged tail columns).  Column j's chain y = y + t stays on thread j across the
+// chunks, in block order -- the order of additions is bvecmat's.
+template <class V>
+__device__ void bvecmat_chunked(V v, const double* F, int N, int E, double* out, double* tb, int nbc) {
+    const int E4 = E == 1 ? 0 : (E & ~3), nb = N >> 2, tid = threadIdx.x;
+    double* tl = tb + nbc * E4;  // the columns past E & ~3 staged from F (their chains read LDS)
+    const int nt = (E - E4) * N;
+    for (int idx = tid; idx < nt; idx += MT) tl[idx] = F[(idx % N) * E + E4 + idx / N];
+    double y = 0.0;
+    for (int b0 = 0; b0 < nb && E4; b0 += nbc) {
+        const int cb = nb - b0 < nbc ? nb - b0 : nbc, ni = cb * E4;
+        for (int idx = tid; idx < ni; idx += MT) {
+            const int j = idx % E4, n = 4 * (b0 + idx / E4);
+            double f[4], w[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                f[r] = F[(n + r) * E + j];
+                w[r] = v(n + r);
+            }
+            double t = f[1] * w[1];
+            t = fma(f[0], w[0], t);
+            t = fma(f[2], w[2], t);
+            t = fma(f[3], w[3], t);
+            tb[idx] = t;
+        }
+        __syncthreads();
+        if (tid < E4) {  // y = y + t, block order, loads eight ahead
+            int b = 0;
+            for (; b + 8 <= cb; b += 8) {
+                double t8[8];
+#pragma unroll
+                for (int q = 0; q < 8; q++) t8[q] = tb[(b + q) * E4 + tid];
+#pragma unroll
+                for (int q = 0; q < 8; q++) y += t8[q];
+            }
+            for (; b < cb; b++) y += tb[b * E4 + tid];
+        }
+        __syncthreads();  // (the next chunk overwrites tb; with E4 == 0 the barrier below orders tl)
+    }
+    if (!E4 || !nb) __syncthreads();
+    if (tid < E) {  // (E <= 64 <= MT: one column per thread)
+        const int j = tid;
+        if (j >= E4) {
+            const double* col = tl + (j - E4) * N;
+            out[j] = mob_vecmat(v, [&](int i) { return col[i]; }, N, E, j);
+        } else {
+            int n = 4 * nb;
+            if (n + 2 <= N) {
+                double t = F[(n + 1) * E + j] * v(n + 1);
+                t = fma(F[n * E + j], v(n), t);
+                y = y + t;
+                n += 2;
+            }
+            if (n < N) y = y + F[n * E + j] * v(n);
+            out[j] = y;
+        }
+    }
+}
+#endif
 
 template <class V>
 __device__ void bvecmat(V v, const double* F, int N, int E, double* out, double* tb) {
@@ -343,12 +457,18 @@ __device__ double wv_wmedian(const double* x, const double* w, int n, double* sb
     } else {
         // stable rank by (x, w) as the SPEC places it: this lane's elements i = lane + 64 q in
         // registers, the compared elements m read eight at a time (LDS broadcasts)
-        const int nq = (n + 63) >> 6;
+#if PCX_MEDIUM_TALL
+        // (n <= 1024: the lane's sixteen elements four at a time, each four against every m)
+        for (int q0 = 0; q0 < ((n + 63) >> 6); q0 += 4) {
+        const int nq = ((n + 63) >> 6) - q0, l0 = lane + 64 * q0;
+#else
+        const int nq = (n + 63) >> 6, l0 = lane;
+#endif
         double xi[4], wi[4];
         int rk[4];
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            const int i = lane + 64 * q;
+            const int i = l0 + 64 * q;
             xi[q] = i < n ? x[i] : 0.0;
             wi[q] = i < n ? w[i] : 0.0;
             rk[q] = 0;
@@ -363,7 +483,7 @@ __device__ double wv_wmedian(const double* x, const double* w, int n, double* sb
                 const bool xin = __builtin_isnan(xi[q]), win = __builtin_isnan(wi[q]);
                 const bool xlt = (xm < xi[q]) || (xin && !xmn), xeq = (xm == xi[q]) || (xin && xmn);
                 const bool wlt = (wm < wi[q]) || (win && !wmn), weq = (wm == wi[q]) || (win && wmn);
-                rk[q] += (xlt || (xeq && (wlt || (weq && m < lane + 64 * q)))) ? 1 : 0;
+                rk[q] += (xlt || (xeq && (wlt || (weq && m < l0 + 64 * q)))) ? 1 : 0;
             }
         };
         int m0 = 0;
@@ -380,10 +500,13 @@ __device__ double wv_wmedian(const double* x, const double* w, int n, double* sb
         for (; m0 < n; m0++) cmp(x[m0], w[m0], m0);
 #pragma unroll
         for (int q = 0; q < 4; q++)
-            if (lane + 64 * q < n) {
+            if (l0 + 64 * q < n) {
                 xs[rk[q]] = xi[q];
                 ws[rk[q]] = wi[q];
             }
+#if PCX_MEDIUM_TALL
+        }
+#endif
     }
     mwsync();
     if (prof) {
@@ -562,9 +685,10 @@ __device__ int component_scores(const BatchArgs& a, const double* C, double* A, 
 // N <= MT).  L is the LDS work region (medium_region doubles); X is this round's N x E global
 // scratch, laid out event-major ([k][i]) so that a thread per row or per cluster reads it
 // coalesced.
-static_assert(MT >= MN, "one thread per reporter row");
 constexpr int M_KMAX = 16;          // k-means code books: ceil(sqrt(256))
 constexpr int M_KMEANS_MAXIT = 4096;  // Lloyd steps per restart (the SPEC's guard)
+#if !PCX_MEDIUM_TALL  // (the tall unit takes no clustering: they are one thread per row by design)
+static_assert(MT >= MN, "one thread per reporter row");
 
 // first thread of the smallest key among the candidate threads (block call; -1: none), the key
 // through *kmin.  shd / shi: MT / 64 slots each, free again after the caller's next barrier.
@@ -1042,6 +1166,7 @@ __device__ __noinline__ void mkmeans_nc(const BatchArgs& a, int64_t b, const dou
     __syncthreads();
     mnc_from_sizes(row ? cntc[lab[tid]] : 0, N, nc, red);
 }
+#endif  // !PCX_MEDIUM_TALL
 
 // doubles of a round's clustering scratch: wcd / the whitened observations; clusterfeck's sums and means
 __host__ __device__ __forceinline__ int medium_xscratch(int N, int E, int alg) {
@@ -1085,6 +1210,49 @@ __host__ __device__ __forceinline__ int medium_region(int N, int E, int alg) {
     const int w = medium_work(N, E, alg), c = medium_clus(N, E, alg);
     return w > c ? w : c;
 }
+
+#if PCX_MEDIUM_TALL
+// The LDS plan of one tall round (256 < N <= 1024 reporters; DESIGN.md 5.3.1): a function of the
+// shape and the algorithm, used alike by the kernel, the launcher and pcx_tall_plan.  The vectors
+// and the flag words are fixed; what is left of the 160 KB a workgroup may use, after the kernel's
+// static LDS, is the work region.  It must hold M (and the Jacobi algorithms' second matrix), one
+// wave's median operands and sort scratch, and the staged np.dot tail columns beside one row of
+// block partials: else the shape does not fit (waves = 0) and stays on the round scheduler.  Within
+// that the plan takes as many median / certainty waves as fit (4, 2 or 1) and the np.dot block
+// partials in chunks of as many four-row blocks as fit; the region is the largest of the three.
+struct TallPlan {
+    int waves;   // concurrent median / certainty waves (0: the shape does not fit)
+    int nbc;     // four-row blocks per np.dot chunk
+    int chunks;  // np.dot chunks (the last one may be shorter)
+    int region;  // doubles of the work region
+};
+constexpr int TALL_LDS_LIMIT = 160 * 1024;
+// tall_round_kernel's static LDS (sh[MT], the scalars, the scaled-event list, component_scores'
+// tables), rounded up; pcx_tall.hip checks it against the code object's figure at the first launch
+constexpr int TALL_STATIC_LDS = 8 * MT + 2560;
+__host__ __device__ __forceinline__ int tall_fixed_bytes(int N, int E) {
+    return (VN_COUNT * N + VE_COUNT * E) * (int)sizeof(double) + ((N * E + 15) >> 4) * 4 + 16;
+}
+__host__ __device__ inline TallPlan tall_plan(int N, int E, int alg) {
+    TallPlan p = {0, 0, 0, 0};
+    if (N < 1 || N > MN || E < 1 || E > MEV || alg < PCX_ALG_PCA || alg > PCX_ALG_COKURTOSIS) return p;
+    const bool jac = alg == PCX_ALG_BIG_FIVE || alg == PCX_ALG_FIXED_VARIANCE;
+    const int E4 = E == 1 ? 0 : (E & ~3), nb = N >> 2, tail = (E - E4) * N;
+    const int mt = (jac ? 2 : 1) * E * (E + 1), stride = medium_wave_stride(N);
+    const int room = TALL_LDS_LIMIT - TALL_STATIC_LDS - tall_fixed_bytes(N, E);
+    const int avail = room > 0 ? room / (int)sizeof(double) : 0;
+    if (avail < mt || avail < stride || avail < tail + E4) return p;
+    const int maxw = MT / 64 < 4 ? MT / 64 : 4;
+    p.waves = maxw * stride <= avail ? maxw : 2 * stride <= avail ? 2 : 1;
+    const int fitb = E4 ? (avail - tail) / E4 : nb;
+    p.nbc = nb < 1 ? 1 : (fitb < nb ? fitb : nb);
+    p.chunks = E4 && nb ? (nb + p.nbc - 1) / p.nbc : 1;
+    const int wq = p.waves * stride, vb = p.nbc * E4 + tail;
+    const int m = mt > wq ? mt : wq;
+    p.region = m > vb ? m : vb;
+    return p;
+}
+#endif
 
 // diagnostic phase stamps (PCX_STAMPS=1): shader-clock reads at phase boundaries
 #define MSTAMP(k)                                                                 \

@@ -27,6 +27,24 @@
 // that form with the round's entry {offset, k} of a device table KmeansEntry[B], indexed by the
 // round, written over the copy's kmeans_k and added to its kmeans_init: mkmeans_nc reads the round's
 // own books as round 0's.
+//
+// Tall rounds (PCX_MEDIUM_TALL 1 with PCX_MEDIUM_RAGGED 0, pcx_tall.hip: tall_round_kernel, DESIGN.md
+// 5.3.1): rounds of one shape with 256 < N <= 1024.  The work region, the number of waves that run
+// medians and certainties side by side, and the np.dot partials' chunks come from the round's LDS
+// plan (tall_plan) in place of medium_region / medium_work / MT / 64; no clustering.
+#if PCX_MEDIUM_TALL
+#define PCX_MROUND_REGION tplan.region
+#define PCX_MROUND_WORK tplan.region
+#define PCX_MROUND_MWAVES tplan.waves
+#define PCX_MROUND_WV0(end) (wv < tplan.waves ? wv : (end))
+#define PCX_MROUND_VECMAT(v, out) bvecmat_chunked(v, F, N, E, out, mlds, tplan.nbc)
+#else
+#define PCX_MROUND_REGION medium_region(N, E, a.algorithm)
+#define PCX_MROUND_WORK medium_work(N, E, a.algorithm)
+#define PCX_MROUND_MWAVES (MT / 64)
+#define PCX_MROUND_WV0(end) wv
+#define PCX_MROUND_VECMAT(v, out) bvecmat(v, F, N, E, out, mlds)
+#endif
 #if PCX_MEDIUM_RAGGED
 #define PCX_MROUND_CELL0 rcell
 #define PCX_MROUND_ROW0 rrow
@@ -87,20 +105,28 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) ragged_medium_kernel(Bat
 #define PCX_MROUND_XSLOT ((int64_t)blockIdx.x * medium_xscratch(N, E, alg))
 #define PCX_MROUND_ARGS a
 template <bool CLUS>
+#if PCX_MEDIUM_TALL
+__global__ void __launch_bounds__(MT, PCX_TALL_WAVES) tall_round_kernel(BatchArgs a, int64_t b0, double* Fscr, double* Cscr,
+                                                                        double* Xscr) {
+#else
 __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(BatchArgs a, int64_t b0, double* Fscr, double* Cscr,
                                                                             double* Xscr) {
+#endif
     extern __shared__ __attribute__((aligned(16))) double mlds[];
     __shared__ double sh[MT];
     __shared__ double scal[16];
     const int64_t b = b0 + blockIdx.x;  // round; scratch slot blockIdx.x
     const int N = a.N, E = a.E, ES = E + 1;
+#if PCX_MEDIUM_TALL
+    const TallPlan tplan = tall_plan(N, E, a.algorithm);  // (uniform: scalar registers)
+#endif
 #endif
     const int tid = threadIdx.x;
     double* M = mlds;
     double* Tm = M + E * ES;
     // work region: M and Tm in the power iteration / Jacobi, per wave the median operands and
     // sort scratch in the interpolation, the outcomes and the certainty
-    double* vN = mlds + medium_region(N, E, a.algorithm);
+    double* vN = mlds + PCX_MROUND_REGION;
     double* vE = vN + VN_COUNT * N;
     // NA flags [N][E], two bits per element (bit 0 NaN, bit 1 zero), sixteen to a word
     uint32_t* flw = (uint32_t*)(vE + VE_COUNT * E);
@@ -205,7 +231,7 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(Batc
         const bool need = act && nmiss > 0;
         double g = 0.0;
         if (__syncthreads_or(need)) {
-            int CR = medium_work(N, E, a.algorithm) / E;
+            int CR = PCX_MROUND_WORK / E;
             CR = CR > 64 ? 64 : CR;
             double* st = mlds;
             for (int c0 = 0; c0 < N; c0 += CR) {
@@ -242,7 +268,7 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(Batc
     }
     MSTAMP(2);
     const int nscl = nscl_s;
-    for (int c = wv; c < nscl; c += MT / 64) {  // one wave per scaled column
+    for (int c = PCX_MROUND_WV0(nscl); c < nscl; c += PCX_MROUND_MWAVES) {  // one wave per scaled column
         const int j = scl[c];
         // present values and their reputations in row order (wave compaction), then the
         // sequential present total on lane 0 and the weights rep / total
@@ -275,7 +301,7 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(Batc
     __syncthreads();
     MSTAMP(3);
     // old = np.dot(rep, F) (:489)
-    bvecmat([&](int i) { return rep[i]; }, F, N, E, VEp(VE_OLD), mlds);
+    PCX_MROUND_VECMAT([&](int i) { return rep[i]; }, VEp(VE_OLD));
     double* loading = VEp(VE_LD);
     double* s = VNp(VN_S);
     double* nc = VNp(VN_U);  // nc, then u
@@ -319,7 +345,7 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(Batc
             for (int p = 0; p < 4; p++)
 #pragma unroll
                 for (int q = 0; q < 4; q++) acc[p][q] = 0.0;
-            int CR = medium_work(N, E, a.algorithm) / (2 * E);
+            int CR = PCX_MROUND_WORK / (2 * E);
             CR = CR > 32 ? 32 : CR;
             double* Al = mlds;
             double* Dl = mlds + CR * E;
@@ -549,6 +575,7 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(Batc
     __syncthreads();
     MSTAMP(8);
     if (clustering) {
+#if !PCX_MEDIUM_TALL
         // --- nc from the clusters (SPEC hier_nc / kmeans_nc / feck_nc); the work region is free
         double* X = Xscr + PCX_MROUND_XSLOT;
         if (alg == PCX_ALG_HIERARCHICAL)
@@ -562,6 +589,7 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(Batc
 #endif
         else
             mfeck_nc(a, F, tok, N, E, X, mlds, nc, scal);
+#endif
     } else if (alg != PCX_ALG_ABSOLUTE) {
         // --- a8/a9: nonconformity_rank (:487-500), tie -> nonconformity (:475-485)
         double* set1 = VNp(VN_SET1);
@@ -610,9 +638,9 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(Batc
         __syncthreads();
         double* old = VEp(VE_OLD);
         MSTAMP(25);
-        bvecmat([&](int i) { return n1[i]; }, F, N, E, VEp(VE_D1), mlds);
+        PCX_MROUND_VECMAT([&](int i) { return n1[i]; }, VEp(VE_D1));
         __syncthreads();
-        bvecmat([&](int i) { return n2[i]; }, F, N, E, VEp(VE_D2), mlds);
+        PCX_MROUND_VECMAT([&](int i) { return n2[i]; }, VEp(VE_D2));
         __syncthreads();
         for (int j = tid; j < E; j += MT) {
             const double a1 = VEp(VE_D1)[j], a2 = VEp(VE_D2)[j];
@@ -710,7 +738,7 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(Batc
     double* raw = VEp(VE_RAW);
     double* adj = VEp(VE_ADJ);
     double* fin = VEp(VE_FIN);
-    bvecmat([&](int i) { return smooth[i]; }, F, N, E, raw, mlds);
+    PCX_MROUND_VECMAT([&](int i) { return smooth[i]; }, raw);
     __syncthreads();
     for (int j = tid; j < E; j += MT) {
         if (!scaled(j)) {
@@ -720,7 +748,7 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(Batc
     }
     __syncthreads();
     MSTAMP(11);
-    for (int c = wv; c < nscl; c += MT / 64) {  // one wave per scaled column
+    for (int c = PCX_MROUND_WV0(nscl); c < nscl; c += PCX_MROUND_MWAVES) {  // one wave per scaled column
         const int j = scl[c];
         for (int i = lane; i < N; i += 64) wb[i] = F[i * E + j];
         mwsync();
@@ -737,7 +765,7 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(Batc
     MSTAMP(12);
     // --- a14: certainty (:540-546): sum of smooth over the matching rows (pairwise), per event
     double* cert = VEp(VE_CERT);
-    for (int j = wv; j < E; j += MT / 64) {  // one wave per event: the matching rows' weights in row order
+    for (int j = PCX_MROUND_WV0(E); j < E; j += PCX_MROUND_MWAVES) {  // one wave per event: the matching rows' weights in row order
         const double aj = adj[j];
         int m = 0;
         for (int i0 = 0; i0 < N; i0 += 64) {
@@ -852,3 +880,8 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) medium_round_kernel(Batc
 #undef PCX_MROUND_CSLOT
 #undef PCX_MROUND_XSLOT
 #undef PCX_MROUND_ARGS
+#undef PCX_MROUND_REGION
+#undef PCX_MROUND_WORK
+#undef PCX_MROUND_MWAVES
+#undef PCX_MROUND_WV0
+#undef PCX_MROUND_VECMAT

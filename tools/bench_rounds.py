@@ -3,9 +3,11 @@ pcx_consensus_batched_f64 on the workgroup-per-round kernel (csrc/pcx_medium.hip
 worker-stream scheduler (csrc/pcx_rounds.cpp, PCX_NO_MEDIUM=1) at several pool sizes.
 
 usage: python tools/bench_rounds.py [B] [N] [E] [wg] [--algorithm NAME] [--reps R]
-                                    [--sched-rounds S] [--workers 1,4,8,16,32]
+                                    [--sched-rounds S] [--workers 1,4,8,16,32] [--tall]
 One JSON line per path / pool size, with every timed repetition, their median and spread
-(max - min); "wg": the workgroup kernel only.  The scheduler runs S rounds (default B).  k-means
+(max - min); "wg": the workgroup kernel only.  --tall: rounds of 257 to 1024 reporters on the tall
+form of the workgroup kernel (csrc/pcx_tall.hip, tall=True) where the route takes them, then the
+scheduler as the default route runs them.  The scheduler runs S rounds (default B).  k-means
 draws its kmeans_init once, outside the timed region.
 """
 import argparse
@@ -28,6 +30,7 @@ def main():
     ap.add_argument("--reps", type=int, default=1, help="timed repetitions per line")
     ap.add_argument("--sched-rounds", type=int, default=None, help="rounds the scheduler runs (default B)")
     ap.add_argument("--workers", default="1,4,8,16,32", help="scheduler pool sizes")
+    ap.add_argument("--tall", action="store_true", help="time the tall route (tall=True) before the scheduler")
     a = ap.parse_args()
     B, N, E = a.B, a.N, a.E
     import numpy as np
@@ -47,17 +50,17 @@ def main():
     if a.algorithm == "hierarchical":
         kw["hierarchy_threshold"] = 1.5 if E >= 33 else 0.5
 
-    def run(nb):
+    def run(nb, **more):
         if kinit is not None:
             kw["kmeans_init"] = kinit[:nb]
-        consensus_batched(Rt[:nb], rt[:nb], sct[:nb], lot[:nb], hit[:nb], **kw)
+        consensus_batched(Rt[:nb], rt[:nb], sct[:nb], lot[:nb], hit[:nb], **kw, **more)
         torch.cuda.synchronize()
 
-    def timed(nb):
+    def timed(nb, **more):
         ts = []
         for _ in range(a.reps):
             t0 = time.perf_counter()
-            run(nb)
+            run(nb, **more)
             ts.append(time.perf_counter() - t0)
         med = statistics.median(ts)
         return {"rounds": nb, "N": N, "E": E, "algorithm": a.algorithm, "seconds": med, "rounds_per_s": nb / med,
@@ -68,6 +71,10 @@ def main():
         for _ in range(2):
             run(B)
         print(json.dumps(dict(timed(B), path="workgroup kernel")), flush=True)
+    if a.tall and route(N, E, a.algorithm, tall=True) == "tall":
+        for _ in range(2):
+            run(B, tall=True)
+        print(json.dumps(dict(timed(B, tall=True), path="tall kernel")), flush=True)
     if a.mode == "wg":
         return
     os.environ["PCX_NO_MEDIUM"] = "1"  # the worker-stream scheduler (csrc/pcx_rounds.cpp)
