@@ -3369,6 +3369,22 @@ __global__ void __launch_bounds__(BT) k_gemv2_mf(pcx_mat m) {
     }
 }
 
+// PCA: a NaN total of |u| leaves the reference's this_rep / smooth_rep fully MASKED, and
+// participation_columns, reporter_bonus and author_bonus are then numpy.ma's data of fully masked
+// results (oracle/pcx_oracle_batched.c rep_masked)
+__device__ __forceinline__ bool rep_fully_masked(const pcx_mat& m) {
+    return m.algorithm == 0 && __builtin_isnan(dd_to_double(scl(m, SC_U)));
+}
+// ... but np.dot(smooth_rep, X) (:510, :559) hands smooth_rep's mask on to its result only when the
+// result has smooth_rep's shape, i.e. N == E (the 4 x 4 golden case).  At N != E the result is the
+// plain product of smooth_rep's DATA, which under the mask is alpha in every row (numpy.ma keeps the
+// first operand of alpha * this_rep): outcomes_raw = alpha * sum_i F_ic, participation_columns =
+// 1 - alpha * (missing reports of c), percent_na and participation plain numbers, reporter_bonus the
+// data of its first operand relative_part * percent_na, author_bonus NaN through the NaN reward.
+__device__ __forceinline__ bool rep_masked_plain_dot(const pcx_mat& m) {
+    return rep_fully_masked(m) && m.n_total != m.n_events;
+}
+
 // certainty of an event no reporter matched (:542): NaN on the PCA path (smooth_rep is a
 // MaskedArray, Q11), 0.0 for the other algorithms (plain ndarray, builtin sum of nothing)
 __device__ __forceinline__ double empty_certainty(const pcx_mat& m) {
@@ -3381,10 +3397,17 @@ __global__ void __launch_bounds__(BT) k_events(pcx_mat m) {
     const int E = (int)m.n_events;
     if (c >= E) return;
     const bool sc = m.scaled && m.scaled[c];
-    m.ev[EV_PC * E + c] = 1.0 - dd_to_double(cst(m, c, 7));
+    const bool plain = rep_masked_plain_dot(m);
+    m.ev[EV_PC * E + c] = 1.0 - (plain ? m.alpha * m.ev[EV_MISS * E + c] : dd_to_double(cst(m, c, 7)));
     if (sc) return;  // scaled events: phase-2 median
     // np.dot(smooth_rep, F) (:510)
-    const double raw = m.ob_order ? ob_col_dot(m, m.rowv + RV_SMOOTH * m.n_rows, c) : dd_to_double(cst(m, c, 6));
+    double raw = m.ob_order ? ob_col_dot(m, m.rowv + RV_SMOOTH * m.n_rows, c) : dd_to_double(cst(m, c, 6));
+    if (plain) {
+        // alpha * sum_i F_ic from the certainty bins' counts: a binary event's filled reports are 1, 1.5
+        // or 2 (a column with any other report value keeps the NaN of the masked weights)
+        const double n1 = dd_to_double(cst(m, c, 11)), n15 = dd_to_double(cst(m, c, 12)), n2 = dd_to_double(cst(m, c, 13));
+        if (n1 + n15 + n2 == (double)m.n_total) raw = m.alpha * (n1 + 1.5 * n15 + 2.0 * n2);
+    }
     const double adj = catch_value(raw, m.catch_tolerance);
     const int slot = adj == 1.0 ? 8 : (adj == 1.5 ? 9 : 10);
     const double cnt = dd_to_double(cst(m, c, slot + 3));
@@ -3439,13 +3462,6 @@ __global__ void __launch_bounds__(BT) k_scaled_cert(pcx_mat m) {
     }
 }
 
-// PCA: a NaN total of |u| leaves the reference's this_rep / smooth_rep fully MASKED, and
-// participation_columns, reporter_bonus and author_bonus are then numpy.ma's data of fully masked
-// results (oracle/pcx_oracle_batched.c rep_masked)
-__device__ __forceinline__ bool rep_fully_masked(const pcx_mat& m) {
-    return m.algorithm == 0 && __builtin_isnan(dd_to_double(scl(m, SC_U)));
-}
-
 // PCX_M_FINAL: certainty of scaled events, consensus_reward, participation, author bonus
 __global__ void __launch_bounds__(1024) k_final(pcx_mat m) {
     __shared__ dd lds[16];
@@ -3489,7 +3505,7 @@ __global__ void __launch_bounds__(1024) k_final(pcx_mat m) {
     }
     __syncthreads();
     const double pna = pv_s(m)[PS_PNA];
-    const bool rep_masked = rep_fully_masked(m);
+    const bool rep_masked = rep_fully_masked(m) && !rep_masked_plain_dot(m);
     for (int c = threadIdx.x; c < E; c += 1024) {
         const double cert = m.ev[EV_CERT * E + c];
         const double reward = nweight(fabs(cert), sh[0], sh[1]);
@@ -3532,7 +3548,7 @@ __global__ void __launch_bounds__(BT) k_agents(pcx_mat m) {
     const int E = (int)m.n_events;
     const double S = dd_to_double(scl(m, SC_AR)), Sp = dd_to_double(scl(m, SC_ARP));
     const double pna = pv_s(m)[PS_PNA];
-    const bool rep_masked = rep_fully_masked(m);
+    const bool rep_masked = rep_fully_masked(m), plain = rep_masked_plain_dot(m);
     for (int64_t i = blockIdx.x * (int64_t)BT + threadIdx.x; i < m.n_rows; i += (int64_t)gridDim.x * BT) {
         const bool masked = (int)m.rowstat[2 * i] == E;
         const double narow = (double)m.rowstat[2 * i + 1];
@@ -3546,7 +3562,8 @@ __global__ void __launch_bounds__(BT) k_agents(pcx_mat m) {
         if (m.na_row) m.na_row[i] = narow;
         if (m.participation_rows) m.participation_rows[i] = pr;
         if (m.relative_part) m.relative_part[i] = rel;
-        if (m.reporter_bonus) m.reporter_bonus[i] = (masked || rep_masked) ? rel : rel * pna + sm * (1.0 - pna);
+        if (m.reporter_bonus)
+            m.reporter_bonus[i] = (masked || rep_masked) ? (plain && !masked ? rel * pna : rel) : rel * pna + sm * (1.0 - pna);
     }
 }
 

@@ -624,7 +624,17 @@ void hard_replay(Run& R, pcx_mat& m, pcx_workspace* w, pcx_result* res, int64_t 
     }
     if (H <= 0) return;
     res->n_hard += (int32_t)H;
-    const int64_t N = m.n_total, cap = std::max<int64_t>(1, m.n_rows);
+    const int64_t N = m.n_total;
+    int64_t cap = std::max<int64_t>(1, m.n_rows);
+    if (R.comm) {
+        // the all-gathers below take one block size from every rank and k_hard_prep strides the
+        // gathered rows by it: the LARGEST shard's rows, not this rank's (N % world != 0 leaves the
+        // shards unequal; with its own n_rows each rank sent and strode a different block).  H is
+        // the same on every rank, so all of them are here; info[IN_HARD] has been read.
+        R.hip(hipMemcpyAsync(m.info + IN_HARD, &cap, sizeof(cap), hipMemcpyHostToDevice, R.st), "H2D");
+        R.allreduce(m.info + IN_HARD, 1, PCX_U64, PCX_MAX);
+        cap = R.read(m.info + IN_HARD);
+    }
     const int64_t P_max = pow2_at_least(N);
     // batch size: keep the batch's scratch near 2 GB
     const int64_t per = cap * 16 * (1 + R.world) + P_max * 16 + N * 16 + 64;

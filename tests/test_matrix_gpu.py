@@ -4,6 +4,10 @@
   the matrix path, north_star tolerances, near-tie rounds counted separately;
 * larger matrices against the numpy CPU oracle run on the box;
 * virtual row shards (2 and 3 ranks in one process) against the 1-rank result.
+
+The golden cases are all far below SEL_EXACT_MAX rows on one rank: of the weighted medians' code they reach
+only k_sel_exact; the histogram tiers, the exchanged passes and the hard replay are covered branch by branch
+by test_matrix_median_gpu.py (crafted columns, matrix_median_cases.py).
 """
 import numpy as np
 import pytest
@@ -161,8 +165,9 @@ def _flat_gpu(ev, ag, meta):
     return out
 
 
-def _sharded(R, rep, sc, lo, hi, world):
-    """consensus_matrix over `world` virtual ranks (ThreadComm, one GPU); rows concatenated."""
+def _sharded(R, rep, sc, lo, hi, world, **kw):
+    """consensus_matrix over `world` virtual ranks (ThreadComm, one GPU); rows concatenated.
+    (kw: further arguments of consensus_matrix -- test_matrix_median_gpu.py passes alpha, int_dtype.)"""
     import threading
 
     import torch
@@ -178,7 +183,7 @@ def _sharded(R, rep, sc, lo, hi, world):
             off, cnt = shard_rows(N, world, r)
             comm = ThreadComm(grp, r)
             ev, ag, meta = consensus_matrix(R[off:off + cnt], rep, sc, lo, hi, comm=comm, n_total=N, row_offset=off,
-                                            matrices=True)
+                                            matrices=True, **kw)
             res[r] = (_flat_gpu(ev, ag, meta), meta)
             comm.close()
         except Exception as e:  # pragma: no cover
