@@ -572,6 +572,50 @@ int pcx_simulate_study_kmeans_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, cons
                                   const int32_t* pair_base, int32_t restarts, pcx_sim_result* result,
                                   pcx_sim_study_result* study);
 
+/* Tall rounds in ragged batches and the simulator (added under ABI 9; detect by symbol; DESIGN.md
+ * 5.5.3).  The entries above keep their [1, 256] x [1, 64] limits and words; these take rounds and
+ * cells within [1, 1024] x [1, 64].  A round of N_b > 256 reporters is taken if and only if
+ * pcx_tall_route(N_b, E_b, its set's algorithm, 1) == PCX_ROUTE_TALL; otherwise the call is refused
+ * (PCX_EINVAL) with the round and the reason named -- a clustering above 256 reporters, or big-five /
+ * fixed-variance whose LDS plan does not fit (e.g. 1024 x 64).  Nothing falls to the round scheduler.
+ * Such rounds form one more segment of the call's launch plan, behind the others: one workgroup per
+ * round of the tall kernel's per-round form, one launch class whatever the algorithms, with scratch
+ * slot strides and a chunk of its own.  k-means is refused as by pcx_ragged_plan_params.
+ *
+ * pcx_ragged_plan_tall is pure: pcx_ragged_plan_params with those limits, *n_tall = the rounds of the
+ * tall segment, *tall_lds_bytes = its launches' dynamic LDS (the largest pcx_tall_lds_bytes of its
+ * rounds; 0 without one); *n_launches counts the tall segment.
+ * pcx_consensus_ragged_tall_f64: a batch without a round above 256 reporters gives the bytes of
+ * pcx_consensus_ragged_params_f64; round b above 256 reporters gives, in every output, the bytes of
+ * pcx_consensus_batched_tall_f64 on that round alone with params[param_of[b]] shared.  Asynchronous,
+ * no host wait of its own. */
+int pcx_ragged_plan_tall(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
+                         const pcx_round_params* params, const int32_t* param_of, int64_t totals[3],
+                         int64_t* n_launches, int64_t* bad_round, int64_t* bad_param, int64_t* n_tall,
+                         int64_t* tall_lds_bytes);
+int pcx_consensus_ragged_tall_f64(pcx_ctx* ctx, const pcx_ragged* in, int64_t n_params,
+                                  const pcx_round_params* params, const int32_t* param_of, pcx_batch_result* out);
+/* pcx_simulate_f64 whose consensus step is pcx_consensus_batched_tall_f64: shapes of the tall route
+ * run one asynchronous launch per timestep instead of the round scheduler; every other shape gives
+ * pcx_simulate_f64's bytes.  The equal-shape twin of a tall cell. */
+int pcx_simulate_tall_f64(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* result);
+/* pcx_simulate_study_params_f64 with cells up to 1024 reporters.  cell_params may be NULL (the
+ * sweep's shared parameters as every cell's set); study may be NULL (the sweep alone).  Cell c's
+ * slice of every output is byte for byte what pcx_simulate_tall_f64 gives for that cell alone; a call
+ * without a cell above 256 reporters gives the bytes of pcx_simulate_study_params_f64 /
+ * pcx_simulate_study_f64 / pcx_simulate_sweep_f64.  A cell is refused by index for what the ragged
+ * tall plan refuses of its rounds; cokurtosis and k-means stay "not simulated".
+ * pcx_sim_study_tall_check is pure: what the call refuses.  pcx_sim_sweep_plan_tall is pure too:
+ * pcx_sim_sweep_plan's figures under those checks (cell_params NULL or [C]) -- totals over every cell;
+ * counts / lds_bytes over the cells up to 256 reporters, each by its own algorithm: a cell above
+ * counts in no launch class (it is the tall segment; pcx_tall_lds_bytes has a round's LDS). */
+int pcx_sim_sweep_plan_tall(const pcx_sim_sweep* sweep, const pcx_round_params* cell_params, int64_t totals[4],
+                            int64_t counts[4], int64_t lds_bytes[4], int64_t* bad_cell);
+int pcx_sim_study_tall_check(const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,
+                             const int32_t* pair_base, int64_t* bad_cell);
+int pcx_simulate_study_tall_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,
+                                const int32_t* pair_base, pcx_sim_result* result, pcx_sim_study_result* study);
+
 /* ------------------------------------------------------------------------ */
 /* Single-matrix regime: one N x E report matrix, optionally sharded by        */
 /* contiguous reporter rows over several GPUs (one process -- or one thread --  */

@@ -123,6 +123,16 @@ def _declare(lib):
         ("pcx_tall_route", i32, [i32, i32, i32, i32]),
         ("pcx_tall_lds_bytes", i64, [i32, i32, i32]),
         ("pcx_tall_plan", i32, [i32, i32, i32, C.POINTER(C.c_int32)]),
+        ("pcx_ragged_plan_tall", i32, [i64, vp, vp, i64, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64),
+                                       C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+        ("pcx_consensus_ragged_tall_f64", i32, [vp, C.POINTER(_abi.Ragged), i64, vp, vp,
+                                                C.POINTER(_abi.BatchResult)]),
+        ("pcx_simulate_tall_f64", i32, [vp, C.POINTER(_abi.Sim), C.POINTER(_abi.SimResult)]),
+        ("pcx_sim_study_tall_check", i32, [C.POINTER(_abi.SimSweep), vp, vp, C.POINTER(i64)]),
+        ("pcx_sim_sweep_plan_tall", i32, [C.POINTER(_abi.SimSweep), vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64),
+                                          C.POINTER(i64)]),
+        ("pcx_simulate_study_tall_f64", i32, [vp, C.POINTER(_abi.SimSweep), vp, vp, C.POINTER(_abi.SimResult),
+                                              C.POINTER(_abi.SimStudyResult)]),
     ]:
         if (name in ("pcx_batched_lds_bytes", "pcx_medium_lds_bytes", "pcx_batched_route", "pcx_ragged_plan",
                      "pcx_consensus_ragged_f64", "pcx_ragged_plan_wide", "pcx_consensus_ragged_wide_f64",
@@ -136,7 +146,9 @@ def _declare(lib):
                      "pcx_consensus_ragged_kmeans_f64", "pcx_sim_kmeans_books_host", "pcx_sim_kmeans_books_f64",
                      "pcx_sim_sweep_kmeans_books_host", "pcx_sim_sweep_kmeans_books_f64", "pcx_simulate_kmeans_f64",
                      "pcx_sim_study_kmeans_check", "pcx_simulate_study_kmeans_f64",
-                     "pcx_consensus_batched_tall_f64", "pcx_tall_route", "pcx_tall_lds_bytes", "pcx_tall_plan")
+                     "pcx_consensus_batched_tall_f64", "pcx_tall_route", "pcx_tall_lds_bytes", "pcx_tall_plan",
+                     "pcx_ragged_plan_tall", "pcx_consensus_ragged_tall_f64", "pcx_simulate_tall_f64",
+                     "pcx_sim_study_tall_check", "pcx_sim_sweep_plan_tall", "pcx_simulate_study_tall_f64")
                 and os.environ.get("PCX_LIB") and not hasattr(lib, name)):
             continue  # an A/B build of a revision before these queries (tools/ab_build.sh)
         f = getattr(lib, name)

@@ -376,6 +376,24 @@ def ragged_plan_params(shapes, sets, param_of):
     return tuple(int(x) for x in totals), int(nl.value)
 
 
+def ragged_plan_tall(shapes, sets, param_of):
+    """:func:`ragged_plan_params` with rounds up to 1024 x 64 (pcx_ragged_plan_tall): (totals,
+    n_launches, n_tall, tall_lds_bytes).  A round above 256 reporters must be of the tall route under
+    its set's algorithm (:func:`route` with ``tall=True``, :func:`tall_plan`); such rounds form one
+    more launch segment, whose dynamic LDS is the largest round's plan.  Needs no GPU; raises PcxError
+    naming the first offending round or parameter set."""
+    sh = np.ascontiguousarray(np.asarray(shapes, dtype=np.int32).reshape(-1, 2))
+    n, e = np.ascontiguousarray(sh[:, 0]), np.ascontiguousarray(sh[:, 1])
+    of = np.ascontiguousarray(param_of, dtype=np.int32)
+    arr = _params_array(sets)
+    totals, nl, bad_r, bad_p = (C.c_int64 * 3)(), C.c_int64(0), C.c_int64(-1), C.c_int64(-1)
+    nt, lds = C.c_int64(0), C.c_int64(0)
+    _lib.check(_lib.lib().pcx_ragged_plan_tall(len(sh), n.ctypes.data, e.ctypes.data, len(sets),
+                                               C.cast(arr, C.c_void_p), of.ctypes.data, totals, C.byref(nl),
+                                               C.byref(bad_r), C.byref(bad_p), C.byref(nt), C.byref(lds)))
+    return tuple(int(x) for x in totals), int(nl.value), int(nt.value), int(lds.value)
+
+
 def ragged_plan_kmeans(shapes, sets, param_of, restarts, k=None):
     """:func:`ragged_plan_params` with k-means allowed in a set (pcx_ragged_plan_kmeans): (totals,
     n_launches, book_offsets).  book_offsets is int64 [B + 1] and counts only the k-means rounds'
@@ -456,7 +474,7 @@ def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *,
                      int_dtype=False, algorithm="PCA", outputs=None, device=None, filled=False, original=False,
                      max_components=5, variance_threshold=0.9, aux_scores=None, hierarchy_threshold=0.5,
                      cluster_threshold=None, wide=False, per_round=None, kmeans_init=None, kmeans_restarts=None,
-                     kmeans_k=None):
+                     kmeans_k=None, tall=False):
     """Run B rounds of DIFFERENT shapes in one launch of the one-wave round kernel.
 
     reports:    a sequence of B arrays, round b an (N_b, E_b) matrix with N_b <= 64, E_b <= 32
@@ -465,6 +483,14 @@ def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *,
                 launch class (:func:`ragged_plan`); the others on the one-wave kernel as before.
                 Every round equals its own ``consensus_batched`` run.  Calls share one per-context
                 scratch: keep them on one stream
+    tall:       True: rounds up to 1024 x 64 (pcx_consensus_ragged_tall_f64), with or without
+                ``per_round``.  A round above 256 reporters runs one workgroup of the tall kernel's
+                per-round form, all of them in one more launch segment behind the others, and equals
+                ``consensus_batched(..., tall=True)`` on that round alone; it must be of the tall
+                route under its algorithm (:func:`route` with ``tall=True``, :func:`tall_plan`: no
+                clustering, and big-five / fixed-variance only where the plan fits) or the call is
+                refused by round.  The other rounds are those of the ``wide=True`` call.  Not with
+                ``kmeans_init``
     reputation: a sequence of B vectors (N_b,) or None (uniform in every round)
     scaled/lo/hi: sequences of B vectors (E_b,) or None (every event binary)
     aux_scores: cokurtosis: a sequence of B vectors (N_b,)
@@ -517,8 +543,10 @@ def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *,
     alg = _abi.ALGORITHMS.get(algorithm)
     if alg is None:
         raise NotImplementedError("algorithm %r is not on the GPU path" % (algorithm,))
+    if tall and (kmeans_init is not None or kmeans_restarts is not None):
+        raise ValueError("tall=True does not take k-means code books (kmeans_init / kmeans_restarts)")
     sets = param_of = None
-    if per_round is not None or kmeans_init is not None:  # (the k-means entry takes parameter sets)
+    if per_round is not None or kmeans_init is not None or tall:  # (the k-means and tall entries take parameter sets)
         if per_round is not None and len(per_round) != B:
             raise ValueError("per_round must hold one entry per round (%d), got %d" % (B, len(per_round)))
         sets, param_of = param_sets([None] * B if per_round is None else per_round, dict(
@@ -548,6 +576,8 @@ def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *,
         if len(km_books) < int(km_offsets[-1]):
             raise ValueError("kmeans_init holds %d rows, the k-means rounds' code books %d"
                              % (len(km_books), int(km_offsets[-1])))
+    elif tall:
+        totals = ragged_plan_tall(shapes, sets, param_of)[0]  # refuses by round or by parameter set
     else:
         if not wide:
             ragged_plan(shapes, "PCA", wide=False)  # the one-wave limits, by index
@@ -597,8 +627,8 @@ def consensus_ragged(reports, reputation=None, scaled=None, lo=None, hi=None, *,
         outs["_kmeans_offsets"], outs["_kmeans_restarts"], outs["_kmeans_init"] = km_offsets, km_restarts, km_d
     else:
         arr = _params_array(sets)
-        _lib.check(_lib.lib().pcx_consensus_ragged_params_f64(h, C.byref(inp), len(sets), C.cast(arr, C.c_void_p),
-                                                              param_of.ctypes.data, C.byref(res)))
+        entry = _lib.lib().pcx_consensus_ragged_tall_f64 if tall else _lib.lib().pcx_consensus_ragged_params_f64
+        _lib.check(entry(h, C.byref(inp), len(sets), C.cast(arr, C.c_void_p), param_of.ctypes.data, C.byref(res)))
         outs["_param_sets"], outs["_param_of"] = sets, param_of
     zero = np.zeros(1, dtype=np.int64)
     outs["_packed"] = buf

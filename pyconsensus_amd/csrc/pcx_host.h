@@ -157,6 +157,14 @@ struct RaggedPlan {
     int64_t stride[3] = {0, 0, 0}, chunk = 0;
     double *Fscr = nullptr, *Cscr = nullptr, *Xscr = nullptr;
     bool filled = false;  // the caller gives `filled`: no N x E scratch of the library's
+    // The tall segment of a table plan built with tall = true: the rounds above 256
+    // reporters, their descriptors behind the nine segments' at tall_first, one launch class whatever
+    // their algorithms (a tall round's LDS leaves one round per CU), tall_lds the largest round's
+    // plan.  Slot strides and a chunk of its own -- a 1024 x 64 round must not shrink the chunks of
+    // the call's 100 x 50 rounds -- over the same scratch: the stream runs the segments one after
+    // another.  All zero without a tall round, and every other field is then what it was.
+    int64_t n_tall = 0, tall_first = 0, tall_lds = 0, tall_stride[2] = {0, 0}, tall_chunk = 0;
+    double *tall_Fscr = nullptr, *tall_Cscr = nullptr;
 
     // The launches over the uploaded tables: wave rounds first (shared: then their scatter), then the
     // workgroup rounds in chunks of the scratch.  books (table layout; NULL: none): the per-round book
@@ -171,6 +179,11 @@ int plan_shared(pcx_ctx* ctx, int64_t B, const int32_t* n_reporters, const int32
                 bool wave_table_alone, RaggedPlan* plan);
 int plan_table(pcx_ctx* ctx, int64_t B, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
                const pcx_round_params* params, const int32_t* param_of, bool filled, size_t extra, RaggedPlan* plan);
+
+// Why a round of N > 256 reporters is refused by the entries that take rounds up to 1024 (the ragged
+// tall entry, the tall study): "N x E under <algorithm>; <reason>" where pcx_tall_route is not
+// PCX_ROUTE_TALL -- a clustering, or an LDS plan that does not fit; empty where the round is taken.
+std::string tall_round_refusal(int N, int E, int algorithm);
 
 }  // namespace host
 }  // namespace pcx

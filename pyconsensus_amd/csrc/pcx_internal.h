@@ -303,6 +303,12 @@ hipError_t launch_ragged_medium_params(const BatchArgs& a, const MediumDesc* des
                                        bool clus, size_t lds, const int64_t s[3], double* Fscr, double* Cscr,
                                        double* Xscr, hipStream_t st);
 
+// the tall segment of a table plan (pcx_tall_ragged.hip: ragged_params_tall_kernel):
+// `nb` workgroups over desc[0 .. nb), rounds of 256 < N <= 1024 reporters whose set's algorithm is of
+// the tall route; lds = the largest tall_lds_bytes(N_b, E_b, algorithm_b), s = {max N E, max E E}
+hipError_t launch_ragged_tall_params(const BatchArgs& a, const MediumDesc* desc, const RoundParams* params, int64_t nb,
+                                     size_t lds, const int64_t s[2], double* Fscr, double* Cscr, hipStream_t st);
+
 // k-means in ragged batches (pcx_consensus_ragged_kmeans_f64): round b's entry of a
 // device table [B] -- where its restarts x k code-book rows start in the call's flat book array, and
 // k ({0, 0} for a round of another algorithm, unread).  The clustering launches of that call run the

@@ -32,6 +32,12 @@
 // 5.3.1): rounds of one shape with 256 < N <= 1024.  The work region, the number of waves that run
 // medians and certainties side by side, and the np.dot partials' chunks come from the round's LDS
 // plan (tall_plan) in place of medium_region / medium_work / MT / 64; no clustering.
+//
+// Tall rounds with a shape and a parameter set per round (PCX_MEDIUM_TALL 1 with PCX_MEDIUM_RAGGED 2,
+// pcx_tall_ragged.hip: ragged_params_tall_kernel, DESIGN.md 5.5.3): the per-round-parameter form whose
+// plan is the round's own -- tall_plan of the descriptor's N and E and the set's algorithm, computed
+// once they sit in scalar registers.  The launch's dynamic LDS is its largest round's plan; the
+// scratch slots are blockIdx.x at the launch's strides sF, sC; no clustering, so no third slot.
 #if PCX_MEDIUM_TALL
 #define PCX_MROUND_REGION tplan.region
 #define PCX_MROUND_WORK tplan.region
@@ -55,7 +61,11 @@
 #define PCX_MROUND_XSLOT ((int64_t)blockIdx.x * sX)
 #define PCX_MROUND_ARGS ar
 template <bool CLUS>
-#if PCX_MEDIUM_RAGGED == 3
+#if PCX_MEDIUM_TALL  // (with PCX_MEDIUM_RAGGED 2 alone)
+__global__ void __launch_bounds__(MT, PCX_TALL_WAVES) ragged_params_tall_kernel(
+    BatchArgs ka, const MediumDesc* __restrict__ rag, const RoundParams* __restrict__ ptab, int64_t sF, int64_t sC,
+    double* Fscr, double* Cscr) {
+#elif PCX_MEDIUM_RAGGED == 3
 __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) ragged_kmeans_medium_kernel(
     BatchArgs ka, const MediumDesc* __restrict__ rag, const RoundParams* __restrict__ ptab,
     const KmeansEntry* __restrict__ ktab, int64_t sF, int64_t sC, int64_t sX, double* Fscr, double* Cscr, double* Xscr) {
@@ -95,6 +105,9 @@ __global__ void __launch_bounds__(MT, PCX_MEDIUM_WAVES) ragged_medium_kernel(Bat
     ar.N = N;
     ar.E = E;
     ar.max_components = a.max_components < E ? a.max_components : E;
+#if PCX_MEDIUM_TALL
+    const TallPlan tplan = tall_plan(N, E, a.algorithm);  // (the round's own, uniform like its descriptor)
+#endif
 #else
 #define PCX_MROUND_CELL0 (b * N * E)
 #define PCX_MROUND_ROW0 (b * N)

@@ -131,15 +131,31 @@ static int shared_plan_pass(int64_t n_rounds, const int32_t* n_reporters, const 
 // The workgroup scratch of a plan with workgroup rounds: the rounds per chunk that fit the cap
 // (pcx_test_scratch_cap's where set) at the plan's slot strides, the context's scratch reserved,
 // and its three parts.  0 = ok.
+// The tall segment (table plans; n_tall > 0) has strides and a chunk of its own under the same cap and
+// lies over the same bytes: the stream runs its launches after the workgroup segments'.
 static int plan_scratch(pcx_ctx* ctx, RaggedPlan& p) {
-    if (p.nm == 0) return PCX_OK;
+    if (p.nm == 0 && p.n_tall == 0) return PCX_OK;
     const size_t cap = ctx->test_scratch_cap > 0 ? (size_t)ctx->test_scratch_cap : MEDIUM_SCRATCH_CAP;
-    const size_t per = (size_t)((p.filled ? 0 : p.stride[0]) + p.stride[1] + p.stride[2]) * sizeof(double);
-    p.chunk = std::min<int64_t>(std::max<int64_t>((int64_t)(cap / per), 1), p.nm);
-    if (const int rc = medium_scratch_reserve(ctx, per * (size_t)p.chunk)) return rc;
-    p.Fscr = (double*)ctx->mscr;
-    p.Cscr = p.Fscr + (p.filled ? 0 : (size_t)p.chunk * p.stride[0]);
-    p.Xscr = p.Cscr + (size_t)p.chunk * p.stride[1];  // the clusterings' cluster sums / observations
+    size_t per = 0, tper = 0;
+    if (p.nm > 0) {
+        per = (size_t)((p.filled ? 0 : p.stride[0]) + p.stride[1] + p.stride[2]) * sizeof(double);
+        p.chunk = std::min<int64_t>(std::max<int64_t>((int64_t)(cap / per), 1), p.nm);
+    }
+    if (p.n_tall > 0) {
+        tper = (size_t)((p.filled ? 0 : p.tall_stride[0]) + p.tall_stride[1]) * sizeof(double);
+        p.tall_chunk = std::min<int64_t>(std::max<int64_t>((int64_t)(cap / tper), 1), p.n_tall);
+    }
+    if (const int rc = medium_scratch_reserve(ctx, std::max(per * (size_t)p.chunk, tper * (size_t)p.tall_chunk)))
+        return rc;
+    if (p.nm > 0) {
+        p.Fscr = (double*)ctx->mscr;
+        p.Cscr = p.Fscr + (p.filled ? 0 : (size_t)p.chunk * p.stride[0]);
+        p.Xscr = p.Cscr + (size_t)p.chunk * p.stride[1];  // the clusterings' cluster sums / observations
+    }
+    if (p.n_tall > 0) {
+        p.tall_Fscr = (double*)ctx->mscr;
+        p.tall_Cscr = p.tall_Fscr + (p.filled ? 0 : (size_t)p.tall_chunk * p.tall_stride[0]);
+    }
     return PCX_OK;
 }
 
@@ -210,8 +226,10 @@ struct SegmentOf {
         fresh = n != N || e != E || a != alg;
         if (fresh) {
             N = n, E = e, alg = a;
-            seg = table_segment(n, e, a);
-            lds = (int64_t)(seg < 3 ? pcx::ragged_lds_bytes(n, e, a) : pcx::medium_lds_bytes(n, e, a));
+            seg = n > 256 ? PLAN_SEGMENTS : table_segment(n, e, a);  // (PLAN_SEGMENTS: the tall segment)
+            lds = (int64_t)(seg == PLAN_SEGMENTS ? pcx::tall_lds_bytes(n, e, a)
+                            : seg < 3            ? pcx::ragged_lds_bytes(n, e, a)
+                                                 : pcx::medium_lds_bytes(n, e, a));
         }
         return seg;
     }
@@ -228,24 +246,38 @@ static void table_count(int64_t B, const int32_t* n_reporters, const int32_t* n_
     for (int64_t b = 0; b < B; b++) {
         const int N = n_reporters[b], E = n_events[b], alg = params[param_of[b]].algorithm;
         const int s = run.at(N, E, alg);
+        if (s == PLAN_SEGMENTS) {  // a tall round (an entry that takes them has checked its route)
+            p.n_tall++;
+            if (!run.fresh) continue;
+            p.tall_lds = std::max(p.tall_lds, run.lds);
+            p.tall_stride[0] = std::max<int64_t>(p.tall_stride[0], (int64_t)N * E);
+            p.tall_stride[1] = std::max<int64_t>(p.tall_stride[1], (int64_t)E * E);
+            continue;
+        }
         p.cnt[s]++;
         if (s >= 3) p.nm++;
         if (!run.fresh) continue;
         p.lds[s] = std::max(p.lds[s], run.lds);
         if (s >= 3) pcx::medium_slot_strides(N, E, alg, p.stride);
     }
-    p.nw = B - p.nm;
+    p.nw = B - p.nm - p.n_tall;
     for (int s = 1; s < PLAN_SEGMENTS; s++) p.first[s] = p.first[s - 1] + p.cnt[s - 1];
+    p.tall_first = B - p.n_tall;  // behind the nine segments
 }
 
-// the launches of a table plan over these checked rounds: its segments that hold a round
+// the launches of a counted table plan with nothing chunked: its segments that hold a round
+static int64_t plan_n_launches(const RaggedPlan& p) {
+    int64_t n = p.n_tall > 0;
+    for (int s = 0; s < PLAN_SEGMENTS; s++) n += p.cnt[s] > 0;
+    return n;
+}
+
+// the launches of a table plan over these checked rounds
 static int64_t table_n_launches(int64_t B, const int32_t* n_reporters, const int32_t* n_events,
                                 const pcx_round_params* params, const int32_t* param_of) {
     RaggedPlan p;
     table_count(B, n_reporters, n_events, params, param_of, &p);
-    int64_t n = 0;
-    for (int s = 0; s < PLAN_SEGMENTS; s++) n += p.cnt[s] > 0;
-    return n;
+    return plan_n_launches(p);
 }
 
 int plan_table(pcx_ctx* ctx, int64_t B, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
@@ -259,8 +291,9 @@ int plan_table(pcx_ctx* ctx, int64_t B, const int32_t* n_reporters, const int32_
     if (const int rc = ragged_slot_take(ctx, p.bytes, &p.slot)) return rc;
     char* pin = static_cast<char*>(p.slot->pin);
     pcx::MediumDesc* d = reinterpret_cast<pcx::MediumDesc*>(pin);
-    int64_t at[PLAN_SEGMENTS];
+    int64_t at[PLAN_SEGMENTS + 1];
     for (int s = 0; s < PLAN_SEGMENTS; s++) at[s] = p.first[s];
+    at[PLAN_SEGMENTS] = p.tall_first;
     SegmentOf run;
     for (RoundWalk r(B, n_reporters, n_events); r.round(); r.step()) {
         const int s = run.at(r.N, r.E, params[param_of[r.b]].algorithm);
@@ -288,6 +321,9 @@ hipError_t RaggedPlan::launch(pcx_ctx* ctx, const pcx::BatchArgs& a, const pcx::
                                     : pcx::launch_ragged_medium_params(a, d + first[s] + b0, tab, nb, s >= 6, (size_t)lds[s],
                                                                        stride, Fscr, Cscr, Xscr, st);
             }
+        for (int64_t b0 = 0; b0 < n_tall && e == hipSuccess; b0 += tall_chunk)  // the tall segment
+            e = pcx::launch_ragged_tall_params(a, d + tall_first + b0, tab, std::min<int64_t>(tall_chunk, n_tall - b0),
+                                               (size_t)tall_lds, tall_stride, tall_Fscr, tall_Cscr, st);
         return e;
     }
     const pcx::RaggedDesc* dw = reinterpret_cast<const pcx::RaggedDesc*>(dev);
@@ -364,9 +400,23 @@ static int param_of_refusal(int64_t b, int32_t of, int64_t n_params, int64_t* ba
                                 ", outside [0, " + std::to_string(n_params) + ")");
 }
 
+std::string tall_round_refusal(int N, int E, int algorithm) {
+    if (pcx_tall_route(N, E, algorithm, 1) == PCX_ROUTE_TALL) return std::string();
+    static const char* const names[] = {"PCA",        "absolute", "big-five",     "fixed-variance",
+                                        "cokurtosis", "k-means",  "hierarchical", "clusterfeck"};
+    const std::string shape = std::to_string(N) + " x " + std::to_string(E);
+    if (algorithm >= PCX_ALG_KMEANS)
+        return shape + " under " + names[algorithm] + "; the clusterings stay within 256 reporters";
+    return shape + " under " + names[algorithm] +
+           "; the round's LDS plan does not fit a workgroup (pcx_tall_route, pcx_tall_plan)";
+}
+
+// tall: the entries that take rounds up to 1024 reporters -- [1, 1024] x [1, 64], and a round above
+// 256 reporters must be of the tall route under its set's algorithm
 static int params_plan_check(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
                              const pcx_round_params* params, const int32_t* param_of, int64_t totals[3],
-                             int64_t* bad_round, int64_t* bad_param, bool kmeans_ok = false) {
+                             int64_t* bad_round, int64_t* bad_param, bool kmeans_ok = false, bool tall = false) {
+    const int max_n = tall ? 1024 : 256;
     if (bad_round) *bad_round = -1;
     if (bad_param) *bad_param = -1;
     if (n_rounds < 0 || n_rounds > 0x7fffffff) return fail(PCX_EINVAL, "ragged: n_rounds must be in [0, 2^31)");
@@ -383,8 +433,15 @@ static int params_plan_check(int64_t n_rounds, const int32_t* n_reporters, const
     int64_t tot[3] = {0, 0, 0};
     for (int64_t b = 0; b < n_rounds; b++) {
         const int32_t N = n_reporters[b], E = n_events[b];
-        if (!round_fits(N, E, 256, 64)) return round_refusal(b, N, E, 256, 64, bad_round);
+        if (!round_fits(N, E, max_n, 64)) return round_refusal(b, N, E, max_n, 64, bad_round);
         if (param_of[b] < 0 || param_of[b] >= n_params) return param_of_refusal(b, param_of[b], n_params, bad_round);
+        if (N > 256) {
+            const std::string why = tall_round_refusal(N, E, params[param_of[b]].algorithm);
+            if (!why.empty()) {
+                if (bad_round) *bad_round = b;
+                return fail(PCX_EINVAL, "ragged: round " + std::to_string(b) + " is " + why);
+            }
+        }
         tot[0] += N, tot[1] += E, tot[2] += (int64_t)N * E;
     }
     for (int k = 0; k < 3 && totals; k++) totals[k] = tot[k];
@@ -543,6 +600,31 @@ int pcx_consensus_ragged_params_f64(pcx_ctx* ctx, const pcx_ragged* in, int64_t 
         return rc;
     if (in->n_rounds == 0) return PCX_OK;
     return table_entry(ctx, in, n_params, params, param_of, nullptr, false, false, out, "ragged params launch");
+}
+
+int pcx_ragged_plan_tall(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, int64_t n_params,
+                         const pcx_round_params* params, const int32_t* param_of, int64_t totals[3],
+                         int64_t* n_launches, int64_t* bad_round, int64_t* bad_param, int64_t* n_tall,
+                         int64_t* tall_lds_bytes) {
+    if (const int rc = params_plan_check(n_rounds, n_reporters, n_events, n_params, params, param_of, totals, bad_round,
+                                         bad_param, false, true))
+        return rc;
+    RaggedPlan p;
+    table_count(n_rounds, n_reporters, n_events, params, param_of, &p);
+    if (n_launches) *n_launches = plan_n_launches(p);
+    if (n_tall) *n_tall = p.n_tall;
+    if (tall_lds_bytes) *tall_lds_bytes = p.tall_lds;
+    return PCX_OK;
+}
+
+int pcx_consensus_ragged_tall_f64(pcx_ctx* ctx, const pcx_ragged* in, int64_t n_params,
+                                  const pcx_round_params* params, const int32_t* param_of, pcx_batch_result* out) {
+    if (!ctx || !in || !out) return fail(PCX_EINVAL, "pcx_consensus_ragged_tall_f64: null argument");
+    if (const int rc = params_plan_check(in->n_rounds, in->n_reporters, in->n_events, n_params, params, param_of,
+                                         nullptr, nullptr, nullptr, false, true))
+        return rc;
+    if (in->n_rounds == 0) return PCX_OK;
+    return table_entry(ctx, in, n_params, params, param_of, nullptr, false, false, out, "ragged tall launch");
 }
 
 int pcx_kmeans_plan(int64_t n_rounds, const int32_t* n_reporters, const int32_t* n_events, const int32_t* k,

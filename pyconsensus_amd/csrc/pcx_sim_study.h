@@ -77,7 +77,8 @@ PCX_SIM_HD void detail_round(int64_t N, int64_t E, double scaled_tol, const uint
     d[7] = FN;
     d[8] = FP;
     d[9] = TN;
-    // with N <= 256 every product is an exact integer below 2^32: the sqrt and the division round
+    // with N <= 1024 every product is an exact integer (a, b, p, q <= 2^20, pq <= 2^40 < 2^53): the
+    // sqrt and the division round
     const double a = TP * TN, b = FP * FN;
     const double p = (TP + FP) * (TP + FN), q = (TN + FP) * (TN + FN);
     const double pq = p * q;

@@ -46,8 +46,10 @@ __device__ __forceinline__ int sweep_cell_of(const int64_t* __restrict__ prefix,
     return lo;
 }
 
-// one timestep's rounds of every cell, flat layout (any pointer of `out` may be NULL)
-hipError_t launch_sim_sweep_generate(const SweepTables& s, uint32_t t, const pcx_sim_rounds& out, hipStream_t st);
+// one timestep's rounds of every cell, flat layout (any pointer of `out` may be NULL).  tall: a cell
+// has more than 256 reporters (up to 1024) -- the instantiation with that many reporter flags in LDS
+hipError_t launch_sim_sweep_generate(const SweepTables& s, uint32_t t, const pcx_sim_rounds& out, hipStream_t st,
+                                     bool tall = false);
 // the same on the host: `cells` is a HOST table
 void sim_sweep_generate_host(const SweepCell* cells, int64_t C, uint32_t t, const pcx_sim_rounds& out);
 // metrics [B][PCX_SIM_NMETRICS] of the sweep's scored rounds

@@ -30,6 +30,7 @@ constexpr int SW_TB = 256;     // threads per workgroup
 constexpr int SW_WAVE = 64;    // a wave takes a round
 constexpr int SW_WAVES = SW_TB / SW_WAVE;
 constexpr int SW_MAXN = 256;   // the wide ragged entry's limits
+constexpr int SW_TALLN = 1024;  // the tall study's (a sweep with a cell above SW_MAXN reporters)
 constexpr int SW_MAXE = 64;    // (<= SW_WAVE: one lane draws one event)
 constexpr int SW_GRID = 4096;  // workgroups at most; the rounds beyond are taken grid-stride
 
@@ -48,11 +49,13 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// MAXN: the reporters a round may have (its flags' LDS): SW_MAXN, or SW_TALLN for a tall study
+template <int MAXN>
 __global__ __launch_bounds__(SW_TB) void k_sim_sweep_generate(const SweepTables s, const uint32_t t,
                                                               const pcx_sim_rounds out) {
     __shared__ double s_lo[SW_WAVES][SW_MAXE], s_hi[SW_WAVES][SW_MAXE], s_truth[SW_WAVES][SW_MAXE],
         s_lie[SW_WAVES][SW_MAXE];
-    __shared__ uint8_t s_scaled[SW_WAVES][SW_MAXE], s_who[SW_WAVES][SW_MAXN];
+    __shared__ uint8_t s_scaled[SW_WAVES][SW_MAXE], s_who[SW_WAVES][MAXN];
     const int lane = threadIdx.x & (SW_WAVE - 1);
     const int w = suniform32(threadIdx.x / SW_WAVE);
     const int64_t step = (int64_t)gridDim.x * SW_WAVES;
@@ -181,11 +184,15 @@ __global__ __launch_bounds__(SW_TB) void k_sim_sweep_summary(const SweepTables s
 }
 }  // namespace
 
-hipError_t launch_sim_sweep_generate(const SweepTables& s, uint32_t t, const pcx_sim_rounds& out, hipStream_t st) {
+hipError_t launch_sim_sweep_generate(const SweepTables& s, uint32_t t, const pcx_sim_rounds& out, hipStream_t st,
+                                     bool tall) {
     if (s.B <= 0) return hipSuccess;
     const unsigned grid = (unsigned)std::min<int64_t>((s.B + SW_WAVES - 1) / SW_WAVES, SW_GRID);
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_sim_sweep_generate, dim3(grid), dim3(SW_TB), 0, st, s, t, out);
+    if (tall)
+        hipLaunchKernelGGL(k_sim_sweep_generate<SW_TALLN>, dim3(grid), dim3(SW_TB), 0, st, s, t, out);
+    else
+        hipLaunchKernelGGL(k_sim_sweep_generate<SW_MAXN>, dim3(grid), dim3(SW_TB), 0, st, s, t, out);
     return hipGetLastError();
 }
 

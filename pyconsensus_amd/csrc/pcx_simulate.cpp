@@ -208,7 +208,9 @@ static int sim_books_check(int64_t B, int restarts, const std::string& who) {
 // The loop of pcx_simulate_f64 and pcx_simulate_kmeans_f64 (`who`).  restarts > 0: the latter, under
 // k-means -- every timestep's books are drawn into the workspace between the generator and the
 // batched launch, which reads them as kmeans_init.
-static int simulate_run(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* res, int restarts, const char* who) {
+// tall (pcx_simulate_tall_f64): the consensus step is pcx_consensus_batched_tall_f64.
+static int simulate_run(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* res, int restarts, const char* who,
+                        bool tall = false) {
     if (const int rc = sim_check(sim, who, restarts > 0)) return rc;
     const bool km = restarts > 0 && sim->algorithm == PCX_ALG_KMEANS;
     const int64_t kk = km ? kmeans_rule(sim->n_reporters) : 0;
@@ -253,7 +255,8 @@ static int simulate_run(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* res, i
             in.kmeans_restarts = restarts;
             in.kmeans_init = w.books;
         }
-        if (const int rc = pcx_consensus_batched_f64(ctx, &in, &o)) return rc;
+        if (const int rc = tall ? pcx_consensus_batched_tall_f64(ctx, &in, &o) : pcx_consensus_batched_f64(ctx, &in, &o))
+            return rc;
         if (res->metrics || res->summary) {
             double* m = res->metrics ? res->metrics + (size_t)t * B * PCX_SIM_NMETRICS : w.metrics;
             e = pcx::launch_sim_metrics(B, N, E, sim->scaled_tol, r, o.old_rep, o.smooth_rep, o.outcomes_final, m,
@@ -274,6 +277,11 @@ static int simulate_run(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* res, i
 int pcx_simulate_f64(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* res) {
     if (!ctx || !sim || !res) return fail(PCX_EINVAL, "pcx_simulate_f64: null argument");
     return simulate_run(ctx, sim, res, 0, "pcx_simulate_f64");
+}
+
+int pcx_simulate_tall_f64(pcx_ctx* ctx, const pcx_sim* sim, pcx_sim_result* res) {
+    if (!ctx || !sim || !res) return fail(PCX_EINVAL, "pcx_simulate_tall_f64: null argument");
+    return simulate_run(ctx, sim, res, 0, "pcx_simulate_tall_f64", true);
 }
 
 int pcx_simulate_kmeans_f64(pcx_ctx* ctx, const pcx_sim* sim, int32_t restarts, pcx_sim_result* res) {
@@ -319,8 +327,13 @@ int sweep_fail(int64_t* bad_cell, int64_t c, const char* who, const std::string&
 // cp: per-cell parameter sets [C] (NULL: the shared parameters) -- the shared ones are then neither
 // read nor checked, each cell's set is checked with the cell, and its rounds count by its algorithm.
 // kmeans_ok: an entry that draws the code books on the device -- k-means passes, shared or in a set.
+// tall: the tall study's entries -- cells within [1, 1024] x [1, 64]; a cell above 256 reporters must
+// be of the tall route under its algorithm and counts in no launch class (*any_tall: there is one).
 int sweep_check(const pcx_sim_sweep* s, const char* who, int64_t totals[4], int64_t counts[4], int64_t lds_bytes[4],
-                int64_t* bad_cell, const pcx_round_params* cp = nullptr, bool kmeans_ok = false) {
+                int64_t* bad_cell, const pcx_round_params* cp = nullptr, bool kmeans_ok = false, bool tall = false,
+                bool* any_tall = nullptr) {
+    const int max_n = tall ? 1024 : 256;
+    if (any_tall) *any_tall = false;
     if (bad_cell) *bad_cell = -1;
     if (s->n_cells < 0) return sweep_fail(bad_cell, -1, who, "n_cells must be >= 0");
     if (s->n_cells > 0 && !s->cells) return sweep_fail(bad_cell, -1, who, "cells is NULL");
@@ -334,10 +347,10 @@ int sweep_check(const pcx_sim_sweep* s, const char* who, int64_t totals[4], int6
     size_t lds[4] = {0, 0, 0, 0};
     for (int64_t c = 0; c < s->n_cells; c++) {
         const pcx_sim_cell& k = s->cells[c];
-        if (k.n_reporters < 1 || k.n_reporters > 256 || k.n_events < 1 || k.n_events > 64)
+        if (k.n_reporters < 1 || k.n_reporters > max_n || k.n_events < 1 || k.n_events > 64)
             return sweep_fail(bad_cell, c, who,
                               "is " + std::to_string(k.n_reporters) + " x " + std::to_string(k.n_events) +
-                                  "; a cell's rounds must be within [1, 256] x [1, 64]");
+                                  "; a cell's rounds must be within [1, " + std::to_string(max_n) + "] x [1, 64]");
         if (k.n_rounds < 1 || k.n_rounds > 0x7fffffff)
             return sweep_fail(bad_cell, c, who, "n_rounds must be in [1, 2^31)");
         if (const char* name = bad_probability(k))
@@ -352,6 +365,12 @@ int sweep_check(const pcx_sim_sweep* s, const char* who, int64_t totals[4], int6
         tot[1] += R * N;
         tot[2] += R * E;
         tot[3] += R * N * E;
+        if (N > 256) {  // (tall)
+            const std::string why = tall_round_refusal((int)N, (int)E, algorithm);
+            if (!why.empty()) return sweep_fail(bad_cell, c, who, "is " + why);
+            if (any_tall) *any_tall = true;
+            continue;
+        }
         const int slot = wide_slot((int)N, (int)E, algorithm, false);
         cnt[slot] += R;
         lds[slot] = std::max(lds[slot], slot ? pcx::medium_lds_bytes((int)N, (int)E, algorithm)
@@ -503,15 +522,18 @@ static void sweep_shapes(const pcx_sim_sweep* s, int32_t* nrep, int32_t* nev, in
 // shared parameters as every cell's set where cp is NULL), every timestep's books of the k-means
 // cells' rounds are drawn into the workspace behind the generator, and the consensus launches are
 // those of pcx_consensus_ragged_kmeans_f64.
+// tall (pcx_simulate_study_tall_f64, with a cell above 256 reporters): cells up to 1024 reporters; the
+// call runs on parameter sets likewise, its consensus launches are those of
+// pcx_consensus_ragged_tall_f64, and the generator runs its 1024-reporter instantiation.
 static int sweep_run(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* res, const int32_t* pair_base,
                      const pcx_sim_study_result* study, const char* who, const pcx_round_params* cp = nullptr,
-                     int restarts = 0) {
+                     int restarts = 0, bool tall = false) {
     const std::string name(who);
     int64_t tot[4], cnt[4], lds[4];
     const bool km = restarts > 0;
-    if (const int rc = sweep_check(sweep, who, tot, cnt, lds, nullptr, cp, km)) return rc;
+    if (const int rc = sweep_check(sweep, who, tot, cnt, lds, nullptr, cp, km, tall)) return rc;
     std::vector<pcx_round_params> own_cp;
-    if (km && !cp) {
+    if ((km || tall) && !cp) {
         own_cp.assign((size_t)sweep->n_cells, shared_set(sweep));
         cp = own_cp.data();
     }
@@ -584,7 +606,7 @@ static int sweep_run(pcx_ctx* ctx, const pcx_sim_sweep* sweep, pcx_sim_result* r
         pcx_sim_rounds r;
         pcx_batch_result o;
         w.at(t, t == T - 1, res, &r, &o);
-        e = pcx::launch_sim_sweep_generate(tab, (uint32_t)t, r, ctx->stream);
+        e = pcx::launch_sim_sweep_generate(tab, (uint32_t)t, r, ctx->stream, tall);
         if (e != hipSuccess) return hip_fail(e, "k_sim_sweep_generate launch");
         pcx_ragged in{};
         in.n_rounds = B;
@@ -668,6 +690,32 @@ int pcx_simulate_study_params_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, cons
     if (!cell_params)  // the existing entries, the same bytes
         return study ? pcx_simulate_study_f64(ctx, sweep, pair_base, res, study) : pcx_simulate_sweep_f64(ctx, sweep, res);
     return sweep_run(ctx, sweep, res, study ? pair_base : nullptr, study, "pcx_simulate_study_params_f64", cell_params);
+}
+
+int pcx_sim_sweep_plan_tall(const pcx_sim_sweep* sweep, const pcx_round_params* cell_params, int64_t totals[4],
+                            int64_t counts[4], int64_t lds_bytes[4], int64_t* bad_cell) {
+    if (!sweep) return fail(PCX_EINVAL, "pcx_sim_sweep_plan_tall: null argument");
+    return sweep_check(sweep, "pcx_sim_sweep_plan_tall", totals, counts, lds_bytes, bad_cell, cell_params, false, true);
+}
+
+int pcx_sim_study_tall_check(const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,
+                             const int32_t* pair_base, int64_t* bad_cell) {
+    const char* who = "pcx_sim_study_tall_check";
+    if (!sweep) return fail(PCX_EINVAL, std::string(who) + ": null argument");
+    if (const int rc = sweep_check(sweep, who, nullptr, nullptr, nullptr, bad_cell, cell_params, false, true)) return rc;
+    return study_check(sweep, pair_base, who, bad_cell);
+}
+
+int pcx_simulate_study_tall_f64(pcx_ctx* ctx, const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,
+                                const int32_t* pair_base, pcx_sim_result* res, pcx_sim_study_result* study) {
+    const char* who = "pcx_simulate_study_tall_f64";
+    if (!ctx || !sweep || !res) return fail(PCX_EINVAL, std::string(who) + ": null argument");
+    bool any_tall = false;
+    if (const int rc = sweep_check(sweep, who, nullptr, nullptr, nullptr, nullptr, cell_params, false, true, &any_tall))
+        return rc;
+    if (!any_tall)  // the existing entries, the same bytes
+        return pcx_simulate_study_params_f64(ctx, sweep, cell_params, pair_base, res, study);
+    return sweep_run(ctx, sweep, res, study ? pair_base : nullptr, study, who, cell_params, 0, true);
 }
 
 int pcx_sim_study_kmeans_check(const pcx_sim_sweep* sweep, const pcx_round_params* cell_params,

@@ -134,7 +134,8 @@ def metrics(rounds, old_rep, smooth_rep, outcomes_final, scaled_tol=0.1, device=
 def simulate(B, N=50, E=20, T=1, seed=0, liar_frac=0.3, collude_frac=0.5, distort=0.1, na_frac=0.1,
              scaled_frac=0.25, scaled_tol=0.1, reputation=None, algorithm="PCA", catch_tolerance=0.1,
              alpha=0.1, max_components=5, variance_threshold=0.9, hierarchy_threshold=0.5,
-             cluster_threshold=None, keep_rounds=False, keep_outputs=False, device=None, kmeans_restarts=None):
+             cluster_threshold=None, keep_rounds=False, keep_outputs=False, device=None, kmeans_restarts=None,
+             tall=False):
     """T timesteps of B random N x E rounds on the GPU: generate, consensus, score, carry.
 
     Timestep t draws its rounds (liars stay the same people through the trajectory), runs the
@@ -155,7 +156,15 @@ def simulate(B, N=50, E=20, T=1, seed=0, liar_frac=0.3, collude_frac=0.5, distor
     ``kmeans_restarts`` (an int >= 1; None = today's refusal): "k-means" runs, its initial code books
     drawn on the device every timestep from a further stream of the generator
     (``pcx_simulate_kmeans_f64``) -- :func:`kmeans_books` shows them, and timestep t
-    equals ``consensus_batched(kmeans_init=kmeans_books(...))`` on :func:`generate`'s rounds."""
+    equals ``consensus_batched(kmeans_init=kmeans_books(...))`` on :func:`generate`'s rounds.
+
+    ``tall=True`` (``pcx_simulate_tall_f64``): the consensus step is
+    ``consensus_batched(..., tall=True)`` -- rounds of 257..1024 reporters that ``batched.route(N, E,
+    algorithm, tall=True)`` calls ``"tall"`` run one asynchronous launch per timestep, with no host in
+    the loop, instead of the round scheduler.  It is what a tall cell of ``sweep(..., tall=True)`` is
+    compared against.  Not with ``kmeans_restarts``."""
+    if tall and kmeans_restarts is not None:
+        raise ValueError("tall=True does not take kmeans_restarts (k-means stays within 256 reporters)")
     tc = _device.require_gpu()
     dev = tc.device(device) if device is not None else tc.device("cuda", tc.cuda.current_device())
     rep = _device.as_device(reputation, tc.float64, dev)
@@ -183,7 +192,9 @@ def simulate(B, N=50, E=20, T=1, seed=0, liar_frac=0.3, collude_frac=0.5, distor
             setattr(res.last_out, name, outs[name].data_ptr())
         out["outputs"] = outs
     h = _lib.bind_stream(dev.index, _device.current_stream_handle(dev))
-    if kmeans_restarts is None:
+    if tall:
+        _lib.check(_lib.lib().pcx_simulate_tall_f64(h, C.byref(s), C.byref(res)))
+    elif kmeans_restarts is None:
         _lib.check(_lib.lib().pcx_simulate_f64(h, C.byref(s), C.byref(res)))
     else:
         _lib.check(_lib.lib().pcx_simulate_kmeans_f64(h, C.byref(s), int(kmeans_restarts), C.byref(res)))
@@ -283,16 +294,25 @@ def _cell_params(norm, algorithm="PCA", catch_tolerance=0.1, alpha=0.1, max_comp
     return (_abi.RoundParams * len(sets))(*[_abi.round_params(q) for q in sets])
 
 
-def sweep_plan(cells, T=1, algorithm="PCA", **params):
+def sweep_plan(cells, T=1, algorithm="PCA", tall=False, **params):
     """Validate a sweep without a device (``pcx_sim_sweep_plan``): ``(totals, counts, lds_bytes)`` as int64
     arrays of four: totals = (B, sum R N, sum R E, sum R N E); counts / lds_bytes are
     ``ragged_plan(wide=True)``'s for the sweep's rounds.  Raises with the cell's index on refusal.
     With cells that carry parameters of their own (``pcx_sim_study_params_check``) counts / lds_bytes
-    are summed / the maximum over the cells, each by its own algorithm."""
+    are summed / the maximum over the cells, each by its own algorithm.
+
+    ``tall=True`` (``pcx_sim_sweep_plan_tall``): cells up to 1024 x 64, refused by index for what
+    ``batched.ragged_plan_tall`` refuses of their rounds.  The cells above 256 reporters count in
+    totals and in no launch class: they are one more launch segment (``batched.tall_plan`` has a
+    round's LDS plan)."""
     s, arr, norm, _ = _sweep(cells, T, algorithm=algorithm, **params)
     out = [(C.c_int64 * 4)() for _ in range(3)]
     bad = C.c_int64(-2)
     cp = _cell_params(norm, algorithm=algorithm, **params)
+    if tall:
+        _lib.check(_lib.lib().pcx_sim_sweep_plan_tall(C.byref(s), None if cp is None else C.cast(cp, C.c_void_p),
+                                                      out[0], out[1], out[2], C.byref(bad)))
+        return tuple(np.array(list(x), dtype=np.int64) for x in out)
     if cp is None:
         _lib.check(_lib.lib().pcx_sim_sweep_plan(C.byref(s), out[0], out[1], out[2], C.byref(bad)))
         return tuple(np.array(list(x), dtype=np.int64) for x in out)
@@ -416,7 +436,7 @@ def sweep_metrics(cells, rounds, old_rep, smooth_rep, outcomes_final, scaled_tol
 
 def sweep(cells, T=1, scaled_tol=0.1, algorithm="PCA", catch_tolerance=0.1, alpha=0.1, max_components=5,
           variance_threshold=0.9, hierarchy_threshold=0.5, cluster_threshold=None, reputation=None,
-          keep_rounds=False, keep_outputs=False, device=None, kmeans_restarts=None):
+          keep_rounds=False, keep_outputs=False, device=None, kmeans_restarts=None, tall=False):
     """T timesteps of a whole study in one call: C cells, each with its own rounds, shape, rates and seed.
 
     ``cells`` is a list of dicts (or tuples, from the left) with ``rounds``, ``reporters``, ``events``,
@@ -447,18 +467,28 @@ def sweep(cells, T=1, scaled_tol=0.1, algorithm="PCA", catch_tolerance=0.1, alph
     k-means cells' rounds are drawn on the device every timestep, under the cell's seed, and a k-means
     cell is byte for byte its own ``simulate(..., algorithm="k-means", kmeans_restarts=...)``.
 
+    ``tall=True`` (``pcx_simulate_study_tall_f64``): shapes go up to 1024 x 64, so a
+    ``grid(reporters=[128, 256, 512, 1024], ...)`` is one call.  A cell above 256 reporters must be of
+    the tall route under its algorithm (``batched.route(N, E, algorithm, tall=True) == "tall"``,
+    ``batched.tall_plan``: no clustering; big-five / fixed-variance where the plan fits) or the call
+    is refused by cell; its rounds run one workgroup each in one more launch per timestep, and its
+    slice is byte for byte ``simulate(R_c, N_c, E_c, T, seed_c, ..., tall=True)``.  Without such a
+    cell the call is the one without ``tall``.  Not with ``kmeans_restarts``.
+
     Asynchronous on torch's current stream, with no host wait between the timesteps.  A sweep runs
     the generic ragged kernels: a study of ONE shape belongs on :func:`simulate`, whose compiled
     equal-shape kernel is faster."""
     return _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_components, variance_threshold,
                       hierarchy_threshold, cluster_threshold, reputation, keep_rounds, keep_outputs, device,
-                      kmeans_restarts=kmeans_restarts)
+                      kmeans_restarts=kmeans_restarts, tall=tall)
 
 
 def _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_components, variance_threshold,
                hierarchy_threshold, cluster_threshold, reputation, keep_rounds, keep_outputs, device,
-               with_study=False, pair_with=None, keep_detail=False, kmeans_restarts=None):
+               with_study=False, pair_with=None, keep_detail=False, kmeans_restarts=None, tall=False):
     """:func:`sweep` (``pcx_simulate_sweep_f64``) or, ``with_study``, :func:`study` (``pcx_simulate_study_f64``)."""
+    if tall and kmeans_restarts is not None:
+        raise ValueError("tall=True does not take kmeans_restarts (k-means stays within 256 reporters)")
     tc = _device.require_gpu()
     dev = tc.device(device) if device is not None else tc.device("cuda", tc.cuda.current_device())
     rep = _device.as_device(reputation, tc.float64, dev)
@@ -475,6 +505,11 @@ def _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_comp
         _lib.check(_lib.lib().pcx_sim_study_kmeans_check(C.byref(s), None if cp is None else C.cast(cp, C.c_void_p),
                                                          None if base is None else base.ctypes.data,
                                                          int(kmeans_restarts), C.byref(C.c_int64(-2))))
+    elif tall:  # one check of the cells up to 1024 reporters, their sets and the pairing
+        base = pair_base(norm, pair_with) if with_study else None
+        _lib.check(_lib.lib().pcx_sim_study_tall_check(C.byref(s), None if cp is None else C.cast(cp, C.c_void_p),
+                                                       None if base is None else base.ctypes.data,
+                                                       C.byref(C.c_int64(-2))))
     elif cp is None:
         sweep_plan(cells, T, scaled_tol=scaled_tol, **shared)  # refuses by cell
     else:  # one check of the cells, their parameter sets and the pairing
@@ -502,7 +537,7 @@ def _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_comp
             setattr(res.last_out, name, outs[name].data_ptr())
         out["outputs"] = outs
     if with_study:
-        if cp is None and not km:
+        if cp is None and not km and not tall:
             base = study_check(norm, pair_with, T, algorithm=algorithm, scaled_tol=scaled_tol,
                                max_components=max_components)  # refuses by cell
         st = _abi.SimStudyResult()
@@ -520,6 +555,10 @@ def _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_comp
         _lib.check(_lib.lib().pcx_simulate_study_kmeans_f64(
             h, C.byref(s), None if cp is None else C.cast(cp, C.c_void_p), None if base is None else base.ctypes.data,
             int(kmeans_restarts), C.byref(res), None if st is None else C.byref(st)))
+    elif tall:
+        _lib.check(_lib.lib().pcx_simulate_study_tall_f64(
+            h, C.byref(s), None if cp is None else C.cast(cp, C.c_void_p), None if base is None else base.ctypes.data,
+            C.byref(res), None if st is None else C.byref(st)))
     elif cp is not None:
         _lib.check(_lib.lib().pcx_simulate_study_params_f64(
             h, C.byref(s), C.cast(cp, C.c_void_p), None if base is None else base.ctypes.data, C.byref(res),
@@ -557,15 +596,19 @@ def pair_base(cells, pair_with):
     return base.astype(np.int32)
 
 
-def study_check(cells, pair_with=None, T=1, algorithm="PCA", **params):
+def study_check(cells, pair_with=None, T=1, algorithm="PCA", tall=False, **params):
     """Validate a study without a device (``pcx_sim_study_check``): what :func:`sweep_plan` refuses, then
     a base outside the cell list, a cell that is its own base, a base with another number of rounds.
-    Raises with the cell's index; returns the ``pair_base`` array (or None)."""
+    Raises with the cell's index; returns the ``pair_base`` array (or None).  ``tall`` as in
+    :func:`sweep_plan` (``pcx_sim_study_tall_check``)."""
     s, arr, norm, _ = _sweep(cells, T, algorithm=algorithm, **params)
     base = pair_base(cells, pair_with)
     bad = C.c_int64(-2)
     cp = _cell_params(norm, algorithm=algorithm, **params)
-    if cp is None:
+    if tall:
+        _lib.check(_lib.lib().pcx_sim_study_tall_check(C.byref(s), None if cp is None else C.cast(cp, C.c_void_p),
+                                                       None if base is None else base.ctypes.data, C.byref(bad)))
+    elif cp is None:
         _lib.check(_lib.lib().pcx_sim_study_check(C.byref(s), None if base is None else base.ctypes.data, C.byref(bad)))
     else:  # cells with parameters of their own
         _lib.check(_lib.lib().pcx_sim_study_params_check(C.byref(s), C.cast(cp, C.c_void_p),
@@ -729,7 +772,7 @@ def sweep_stats(cells, metrics, detail, pair_with=None, device=None):
 
 def study(cells, T=1, pair_with=None, keep_detail=False, scaled_tol=0.1, algorithm="PCA", catch_tolerance=0.1,
           alpha=0.1, max_components=5, variance_threshold=0.9, hierarchy_threshold=0.5, cluster_threshold=None,
-          reputation=None, keep_rounds=False, keep_outputs=False, device=None, kmeans_restarts=None):
+          reputation=None, keep_rounds=False, keep_outputs=False, device=None, kmeans_restarts=None, tall=False):
     """:func:`sweep` with a study's result (``pcx_simulate_study_f64``): every key of
     :func:`sweep`'s dict, byte for byte, plus
 
@@ -749,10 +792,12 @@ def study(cells, T=1, pair_with=None, keep_detail=False, scaled_tol=0.1, algorit
     statistics by one launch after the last timestep; the call stays asynchronous on torch's current
     stream with no host wait.  Refusals are :func:`sweep`'s and :func:`study_check`'s.
     ``kmeans_restarts`` as in :func:`sweep`: with it a cell may be k-means, and ``pair_with="first"``
-    pairs a PCA cell and a k-means cell of one seed and shape on the same drawn rounds."""
+    pairs a PCA cell and a k-means cell of one seed and shape on the same drawn rounds.
+    ``tall`` as in :func:`sweep`: cells up to 1024 reporters, scored, paired and summarised like the others."""
     return _run_sweep(cells, T, scaled_tol, algorithm, catch_tolerance, alpha, max_components, variance_threshold,
                       hierarchy_threshold, cluster_threshold, reputation, keep_rounds, keep_outputs, device,
-                      with_study=True, pair_with=pair_with, keep_detail=keep_detail, kmeans_restarts=kmeans_restarts)
+                      with_study=True, pair_with=pair_with, keep_detail=keep_detail, kmeans_restarts=kmeans_restarts,
+                      tall=tall)
 
 
 def stderr(stats_or_paired):
@@ -817,6 +862,8 @@ def main(argv=None):
                     help="a comma list runs every cell under each algorithm, in one call")
     ap.add_argument("--kmeans-restarts", type=int, default=None,
                     help="restarts of every k-means round (default 20 where --algorithm names k-means)")
+    ap.add_argument("--tall", action="store_true",
+                    help="rounds and cells up to 1024 reporters (those above 256 on the tall workgroup kernel)")
     ap.add_argument("--alpha", type=flt, default=None, help="the reputation smoothing (or a comma list)")
     ap.add_argument("--catch", type=flt, default=None, help="catch_tolerance (or a comma list)")
     ap.add_argument("--stats", action="store_true",
@@ -838,6 +885,8 @@ def main(argv=None):
             a.shared[key] = values[0]
     if a.kmeans_restarts is not None or "k-means" in a.algorithm:  # naming k-means enables it
         a.shared["kmeans_restarts"] = _abi.KMEANS_RESTARTS if a.kmeans_restarts is None else a.kmeans_restarts
+    if a.tall:
+        a.shared["tall"] = True
     a.algorithm = ",".join(a.algorithm)
     if a.stats or a.paired:
         return _main_study(a, lists)
